@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- particle-steps/s of the MI355X hot path on BASELINE.json's workloads.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5] [--particles P]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5] [--particles P] [--dump-outputs DIR]
 
 A "step" is one pass of the per-timestep hot path over all particles of this rank with the
 inputs already resident in HBM (field blocks uploaded, particle SoA on device):
@@ -640,6 +640,33 @@ def plumbing_only(a):
     return 0 if all_ok else 1
 
 
+DUMP_SAMPLE = 1_000_000     # particle IDs in the --dump-outputs sample: 5 arrays x 1 M x <= 8 B = 36 MB
+
+
+def dump_outputs(out_dir, P, n_total, lo, hi, rank, world):
+    """--dump-outputs: what the timed path leaves its caller after its last step -- position, depth, status and moving flag of
+    every element, the active ones and the ones compaction moved out (Particles.download / download_deactivated) -- for a
+    fixed, seeded sample of the global particle IDs, in ID order: the re-sort and the compaction permute the device arrays,
+    so the sample is indexed by ID, not by slot.  An ID of the sample that neither download holds is NaN."""
+    ids = np.sort(np.random.default_rng(20240611).choice(n_total, size=min(n_total, DUMP_SAMPLE), replace=False))
+    ids = ids[(ids >= lo) & (ids < hi)]            # this rank's shard
+    act, dead = P.download(), P.download_deactivated()
+    got = {k: np.concatenate([act[k], dead[k]]) if k in dead else np.concatenate([act[k], np.zeros(len(dead['ID']), act[k].dtype)])
+           for k in ('lon', 'lat', 'z', 'status', 'moving')}
+    pos = np.full(hi - lo, -1, np.int64)
+    pos[np.concatenate([act['ID'], dead['ID']]).astype(np.int64) - lo] = np.arange(len(act['ID']) + len(dead['ID']))
+    at = pos[ids - lo]
+    found = at >= 0
+    arrays = {'id': ids.astype(np.float64)}
+    for k, dt in (('lon', np.float64), ('lat', np.float64), ('z', np.float64), ('status', np.float32), ('moving', np.float32)):
+        v = np.full(ids.size, np.nan, dt)
+        v[found] = got[k][at[found]]
+        arrays[k] = v
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ('_rank%d' % rank if world > 1 else '') + '.npy'), v)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
@@ -662,6 +689,9 @@ def main():
                     help="arithmetic of the Runge-Kutta stage evaluations (odr_ctx_set_stage_math): 'fast' is the headline -- its "
                          "parity gate is tests/test_gpu_stage_math.py -- 'exact' keeps every float32 rounding point of the "
                          "reference inside a stage; the line carries the other mode's rate as `stage_math_exact` / `_fast`")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the particle state of the last step as DIR/<name>.npy (a fixed, '
+                         'seeded sample of the particle IDs, at most 64 MB; N ranks: DIR/<name>_rank<r>.npy)')
     ap.add_argument('--plumbing-only', action='store_true',
                     help='rendezvous, shards, block broadcast and the reductions of the N-rank run without the device path '
                          '(no GPU needed; value is null)')
@@ -841,6 +871,8 @@ def main():
         timed_loop(2 * max(sharded.block_every, 3) + 1, spin + a.warmup)
         sharded.collectives, sharded.collective_s, sharded.levels, sharded.level_stall_s = 0, 0.0, 0, 0.0
     el, units_rank = timed_loop(a.steps, spin + a.warmup, max(a.block_every, 0), a.block_async, pinned)
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, P, n * world, lo, hi, rank, world)
     sharded_report = sharded.report(a.steps) if sharded is not None else None
     sharded = None               # the legs below (kernel timings, the other stage arithmetic) time this rank's device step alone
     el_max = float(D.allreduce_scalars([el], 'max')[0])

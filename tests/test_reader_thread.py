@@ -29,20 +29,27 @@ class SlowReader:
 def test_next_level_is_read_off_the_calling_thread_and_is_ready_when_due():
     r = SlowReader()
     a = ReadAhead(r, ['u'])
-    x, y = np.array([0.0, 1.0]), np.array([2.0, 3.0])
-    b0 = a.read(0, x, y)                       # nothing read ahead yet: inline
-    assert b0['u'][0, 0] == 0.0 and a.misses == 1 and a.hits == 0
-    t0 = time.perf_counter()
-    a.start(1, x, y)
-    assert time.perf_counter() - t0 < 0.05     # returns at once
-    time.sleep(0.3)                            # "the steps of this period"
-    t0 = time.perf_counter()
-    b1 = a.read(1, x, y)
-    assert time.perf_counter() - t0 < 0.05     # no wait: it was read meanwhile
-    assert b1['u'][0, 0] == 1.0 and a.hits == 1
-    assert r.calls[0][1] == threading.current_thread().name and r.calls[1][1].startswith('odr-reader')
-    assert a.worker_s >= 0.14
-    a.close()
+    try:
+        x, y = np.array([0.0, 1.0]), np.array([2.0, 3.0])
+        b0 = a.read(0, x, y)                       # nothing read ahead yet: inline
+        assert b0['u'][0, 0] == 0.0 and a.misses == 1 and a.hits == 0
+        t0 = time.perf_counter()
+        a.start(1, x, y)
+        assert time.perf_counter() - t0 < 0.05     # returns at once
+        # "the steps of this period": the caller does its own work until the level is due.  Waited for until the worker is
+        # done (not a fixed sleep: on a busy host the worker thread may be scheduled late), with a deadline
+        deadline = time.perf_counter() + 10.0
+        while not a._fut.done() and time.perf_counter() < deadline:
+            time.sleep(0.01)
+        assert a._fut.done(), 'the read-ahead did not finish within 10 s'
+        t0 = time.perf_counter()
+        b1 = a.read(1, x, y)
+        assert time.perf_counter() - t0 < 0.05     # no wait: it was read meanwhile
+        assert b1['u'][0, 0] == 1.0 and a.hits == 1
+        assert r.calls[0][1] == threading.current_thread().name and r.calls[1][1].startswith('odr-reader')
+        assert a.worker_s >= 0.14
+    finally:
+        a.close()                                  # (also when an assertion failed: no worker outlives the test)
 
 
 def test_a_read_ahead_for_another_level_or_window_is_dropped():
