@@ -485,9 +485,13 @@ int odr_scan_status(odr_ctx *ctx, odr_particles *p, int64_t *n_kept, uint64_t *s
  * the mixing of the step (oceandrift.py:397-571) is enqueued BEFORE the host knows whether remove_deactivated_elements
  * (basemodel/__init__.py:2284) has anything to remove -- in the common step it has not, and the device goes from the step
  * launch into the mixing launch without waiting for the host; otherwise the host compacts and calls odr_vmix again, unguarded
- * (the guarded launch has not touched anything).  A guarded odr_vmix that cannot honour the guard (another kernel family than
- * the reader-profile fast path) launches nothing and returns 1.  odr_scan_status_end waits for the fold only (not for the
- * mixing launch behind it) and hands out what odr_scan_status would have. */
+ * (the guarded launch has not touched anything, and odr_scan_status_end re-arms the odr_vmix_fuse_vertical_advection setting it
+ * took, for that call: the retry is expected -- a caller that skips it leaves the setting armed for its next odr_vmix).  A guarded odr_vmix that cannot honour the guard (host-drawn numbers, or
+ * another kernel family than the reader-profile fast path: OpenOil's loop, profiles sampled in the float32 position class, a
+ * level cut) launches nothing, leaves the one-shot settings of odr_vmix_fuse_vertical_advection, odr_vmix_set_profile_levels
+ * and odr_oil_prepare_mixing armed for the unguarded call, and returns 1.  odr_vmix_wind_profile carries no guard: it drops an
+ * armed one.  odr_scan_status_end waits for the fold only (not for the mixing launch behind it) and hands out what
+ * odr_scan_status would have. */
 int odr_scan_status_begin(odr_ctx *ctx, odr_particles *p);
 int odr_scan_status_end(odr_ctx *ctx, odr_particles *p, int64_t *n_kept, uint64_t *status_flags);
 int odr_ctx_guard_next_vmix(odr_ctx *ctx, int on);

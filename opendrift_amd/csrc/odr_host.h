@@ -58,6 +58,10 @@ struct odr_ctx {
   hipEvent_t scan_ev = nullptr;     // behind the fold of odr_scan_status_begin
   bool scan_open = false;
   int guard_next_vmix = 0;          // odr_ctx_guard_next_vmix
+  // the guarded odr_vmix launch enqueued behind the open fold, and the fuse_vadv it took: odr_scan_status_end hands that back to the
+  // unguarded call that follows when the fold finds that the launch does nothing
+  const odr_particles *guarded_vmix = nullptr;
+  int guarded_vadv = -1;
   int vmix_levels = 0;              // odr_vmix_set_profile_levels: one-shot, taken by the next odr_vmix (0 = every level of the reader)
   unsigned long long *scan_host = nullptr;   // page-locked: what odr_scan_status reads (written by k_cmp_total itself)
   // page-locked copies of `hw` the device image is refreshed from (flush_world): three in turn, each guarded by an event

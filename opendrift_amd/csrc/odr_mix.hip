@@ -7,9 +7,26 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
              const double *huni, uint64_t step) {
   const bool guarded = c->guard_next_vmix != 0;     // odr_ctx_guard_next_vmix: THIS call only, however it ends
   c->guard_next_vmix = 0;
-  // a guarded call that cannot honour the guard (host-drawn numbers, OpenOil's loop: other kernel families) launches nothing and
-  // consumes nothing: the caller calls again, unguarded
-  if (guarded && (rng_mode == ODR_RNG_HOST || c->oil_owner == p)) return 1;
+  // the kernel family, decided before any one-shot setting is taken.  Fast column kernel (the only one that carries the guard): K
+  // from one gridded reader, plain z-innermost array on every resident level.  The generic kernel: OpenOil's loop (terminal
+  // velocities, slick and wave entrainment inside it), profiles sampled in the float32 position class (a run's first
+  // get_environment, odr_ctx_set_position_class) and columns cut at a level (odr_vmix_set_profile_levels: a reader that cut its
+  // block at the depth asked of it)
+  const bool oil = c->oil_owner == p;
+  const bool f32prof = p->profiles_f32;
+  const int cut = c->vmix_levels;
+  VMixDesc D;
+  const bool fast = !oil && !f32prof && cut <= 0 && !getenv("ODR_NO_FAST_PATH") && build_vmix_desc(c, t, D);
+  // a guarded call that cannot honour the guard (host-drawn numbers, another kernel family) launches nothing and consumes
+  // nothing -- the one-shot settings stay armed, DevWorld::f32pos is not touched --: the caller calls again, unguarded
+  if (guarded && (rng_mode == ODR_RNG_HOST || !fast)) return 1;
+  // the one-shot settings (odr_vmix_fuse_vertical_advection, odr_vmix_set_profile_levels, odr_oil_prepare_mixing) belong to THIS
+  // call, however it ends
+  const int vadv = c->fuse_vadv;
+  c->fuse_vadv = -1;
+  c->oil_owner = nullptr;
+  c->vmix_levels = 0;
+  c->guarded_vmix = nullptr;
   p->status_epoch++;
   p->epoch++;  // invalidates the cached reductions (reduce())
   REQUIRE(dt_mix > 0 && dt != 0, "bad time steps");
@@ -38,30 +55,23 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
   dim3 g(nblk(p->n)), b(BLOCK);
   PView v = view(p);
   unsigned long long st = (unsigned long long)step;
-  int vadv = c->fuse_vadv;
-  c->fuse_vadv = -1;
   if (vadv >= 0 && !p->env[VAR_W]) return fail(ODR_ERR_STATE, "upward_sea_water_velocity has not been sampled");
-  // fast column kernel: K from one gridded reader, plain z-innermost array on every resident level
-  const bool oil = c->oil_owner == p;   // OpenOil: terminal velocities, slick and wave entrainment inside the loop
-  c->oil_owner = nullptr;
-  VMixDesc D;
-  // the step's profiles were sampled in the float32 position class (a run's first get_environment, odr_ctx_set_position_class):
-  // the generic kernel forms the column's footprint with float32 index maps (DevWorld::f32pos bit 1, set for this launch)
-  // odr_vmix_set_profile_levels: the columns end at that level (a reader that cut its block at the depth asked of it): generic kernel
-  const int cut = c->vmix_levels;
-  c->vmix_levels = 0;
-  if (cut > 0 && guarded) return 1;
-  const bool f32prof = p->profiles_f32;
-  if (f32prof) { c->hw.f32pos |= 2; c->dirty = true; if ((rc = flush_world(c))) return rc; }
-  const bool fast = !oil && !f32prof && cut <= 0 && !getenv("ODR_NO_FAST_PATH") && build_vmix_desc(c, t, D);
+  // bit 1 of DevWorld::f32pos: the generic kernel forms the column's footprint with float32 index maps.  Set for this launch
+  // only: cleared on every way out of this call (an error return included), or every later launch would take the generic
+  // kernels with float32 footprints
+  struct F32ProfileClass {
+    odr_ctx *c;
+    bool on;
+    ~F32ProfileClass() { if (on) { c->hw.f32pos &= ~2; c->dirty = true; } }
+  } f32bit{c, false};
+  if (f32prof) { c->hw.f32pos |= 2; c->dirty = true; f32bit.on = true; if ((rc = flush_world(c))) return rc; }
   if (cut > 0) {
     REQUIRE(cut >= 2 && cut <= 255, "odr_vmix_set_profile_levels: 2 .. 255 levels");
     if (cut < nzp) nzp = cut;
   }
   const int sfl_cut = c->seafloor | ((cut > 0 ? nzp : 0) << 16);     // (the generic kernels read the cut from bits 16 .. 23)
-  if (guarded && !fast) { c->fuse_vadv = vadv; return 1; }   // (the generic kernel carries no guard) nothing launched
   if (fast) {
-    if (guarded) D.guard = c->counter + 4;
+    if (guarded) { D.guard = c->counter + 4; c->guarded_vmix = p; c->guarded_vadv = vadv; }
     const int nq = (nzp + 3) / 4;
     const bool tl = D.ka != nullptr;
     // k_vmix_win (five levels per particle in registers: cost independent of the number of reader levels) from 13 levels
@@ -104,7 +114,6 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
   else if (nzp <= 32) hipLaunchKernelGGL(k_vmix<32>, g, b, lds, c->stream, c->dw, v, t, dt, dt_mix, mix_at_surface, rng_mode, du, c->seed, st, vadv, sfl_cut);
   else hipLaunchKernelGGL(k_vmix<1>, g, b, lds, c->stream, c->dw, v, t, dt, dt_mix, mix_at_surface, rng_mode, du, c->seed, st, vadv, sfl_cut);
   HIPCHK(hipGetLastError());
-  if (f32prof) { c->hw.f32pos &= ~2; c->dirty = true; }
   return 0;
 }
 
@@ -121,6 +130,7 @@ int odr_vmix_set_profile_levels(odr_ctx *c, int32_t n) {
 
 int odr_vmix_wind_profile(odr_ctx *c, odr_particles *p, int model, double background_diffusivity, double dt,
                           double dt_mix, int mix_at_surface, int rng_mode, const double *huni, uint64_t step) {
+  c->guard_next_vmix = 0;   // (no guard here: an armed one is dropped, not left for a later odr_vmix)
   p->status_epoch++;
   p->epoch++;
   REQUIRE(model == ODR_DIFFUSIVITY_LARGE1994 || model == ODR_DIFFUSIVITY_SUNDBY1983, "Unknown diffusivity model: %d", model);

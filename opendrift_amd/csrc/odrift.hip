@@ -148,6 +148,7 @@ int odr_particles_create(odr_ctx *c, int64_t capacity, odr_particles **out) {
 int odr_particles_destroy(odr_ctx *c, odr_particles *p) {
   if (c->red_owner == p) c->red_owner = nullptr;
   if (c->noise_owner == p) c->noise_owner = nullptr;
+  if (c->guarded_vmix == p) c->guarded_vmix = nullptr;
   if (!p) return 0;
   (void)hipStreamSynchronize(c->stream);
   auto fr = [](void *q) { if (q) (void)hipFree(q); };
@@ -2213,6 +2214,10 @@ int odr_scan_status_end(odr_ctx *c, odr_particles *p, int64_t *n_kept, uint64_t 
   if (n_kept) *n_kept = (int64_t)c->scan_host[0];
   if (flags) *flags = c->scan_host[1];
   p->scan_kept = (long long)c->scan_host[0];
+  if (c->guarded_vmix == p) {   // the guarded mixing launch behind the fold: it does nothing unless every element stays
+    c->guarded_vmix = nullptr;
+    if (p->scan_kept != p->n) c->fuse_vadv = c->guarded_vadv;   // then the unguarded call that follows fuses what it would have
+  }
   p->scan_epoch = p->status_epoch;   // (a guarded mixing launch between the halves deactivates nothing the fold has not seen: it
                                      // runs only when every element stays, and then there is nothing to compact)
   return 0;

@@ -820,9 +820,11 @@ class OpenDriftSimulation(Configurable):
         of its last level.  The device block holds every level: the number of levels of the reference's block, for the step's
         mixing launch (odr_vmix_set_profile_levels); 0 = whole columns (no truncation, or a reader that says
         `always_delivers_all_levels`).  Evaluated per step from the elements' depths (the reference keeps a cached block while it
-        covers the request: the same whenever some element is below the truncation depth, the case the option is for)."""
+        covers the request: the same whenever some element is below the truncation depth, the case the option is for).
+        Sharded: only rank-invariant inputs (the option, the reader and its levels) decide whether the allreduce is made -- a rank
+        without elements takes part with a depth of 0, or the ranks would run different sequences of collectives."""
         T = self._config.get('drift:truncate_ocean_model_below_m', {}).get('value')
-        if T is None or self.P is None or len(self.P) == 0:
+        if T is None or self.P is None:
             return 0
         for n in self.priority_list.get('ocean_vertical_diffusivity', []):
             b = self.readers.get(n)
@@ -835,7 +837,7 @@ class OpenDriftSimulation(Configurable):
             if not zlev[0] > zlev[-1]:
                 raise NotImplementedError('drift:truncate_ocean_model_below_m with diffusivity profiles from reader "%s": ascending '
                                           'z levels' % n)
-            deepest = float(self.P.reduce_local()[5])            # max(-z) over the active elements of this rank
+            deepest = float(self.P.reduce_local()[5]) if len(self.P) else 0.0     # max(-z) over the active elements of this rank
             if self._world > 1:
                 from . import distributed as D
                 self._timing_collectives += 1

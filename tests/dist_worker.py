@@ -66,6 +66,30 @@ def main():
         o.seed_elements(lon=rng.uniform(4.4, 5.34, n), lat=rng.uniform(59.3, 60.7, n), time=[T0, T0 + timedelta(seconds=2700)],
                         wind_drift_factor=0.0)
         o.run(time_step=900, steps=8)
+    elif scenario == 'empty_rank':
+        # drift:truncate_ocean_model_below_m with reader diffusivity profiles (the all-rank depth of the deepest element decides
+        # where the columns end): the second shard's elements are seeded east of drift:deactivate_east_of and are all gone after
+        # the first step -- that rank goes on taking part in every collective of the step
+        g = np.load(os.path.join(gold, 'c24_profiles.npz'))
+        names = ['x_sea_water_velocity', 'y_sea_water_velocity', 'upward_sea_water_velocity', 'ocean_vertical_diffusivity',
+                 'sea_floor_depth_below_sea_level', 'land_binary_mask']
+        times = [T0 + timedelta(seconds=float(t)) for t in g['a_g_t']]
+        o = OceanDrift(loglevel=50, seed=0)
+        o.add_reader(readers.GridReader(g['a_g_x'], g['a_g_y'], times, {k: g['a_g_' + k] for k in names}, z=g['a_g_z']))
+        o.set_config('drift:advection_scheme', 'runge-kutta4')
+        o.set_config('drift:vertical_mixing', True)
+        o.set_config('vertical_mixing:timestep', 60)
+        o.set_config('drift:vertical_advection', True)
+        o.set_config('general:coastline_action', 'previous')
+        o.set_config('drift:truncate_ocean_model_below_m', 20.0)
+        o.set_config('drift:deactivate_east_of', 8.0)
+        n = 2000
+        rng = np.random.default_rng(6)
+        lon = np.concatenate([rng.uniform(0.5, 7.0, n // 2), rng.uniform(8.5, 9.5, n - n // 2)])
+        lat = rng.uniform(60.5, 65.5, n)
+        z = -rng.uniform(0, 60, n)
+        o.seed_elements(lon=lon, lat=lat, z=z, time=T0)
+        o.run(time_step=600, steps=6)
     else:
         # OpenOil: np.mean(dV_50) and np.mean(1.5 Hs) over all elements, wave entrainment, default uncertainties
         g = np.load(os.path.join(gold, 'c9_openoil_mixing.npz'))

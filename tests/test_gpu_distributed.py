@@ -34,7 +34,14 @@ def _run(scenario, world, out):
                    MASTER_PORT=str(port), ODR_DIST_BACKEND='gloo', HSA_ENABLE_IPC_MODE_LEGACY='0')
         procs.append(subprocess.Popen([sys.executable, os.path.join(HERE, 'dist_worker.py'), scenario, out], env=env,
                                       stdout=subprocess.PIPE, stderr=subprocess.STDOUT))
-    outs = [p.communicate(timeout=600)[0].decode() for p in procs]
+    try:
+        outs = [p.communicate(timeout=600)[0].decode() for p in procs]
+    except subprocess.TimeoutExpired:
+        for p in procs:      # (a rank left waiting in a collective: no worker outlives the test holding the GPU)
+            p.kill()
+        for p in procs:
+            p.communicate()
+        raise
     assert all(p.returncode == 0 for p in procs), '\n'.join('--- rank %d (rc %s)\n%s' % (r, p.returncode, o[-2500:])
                                                              for r, (p, o) in enumerate(zip(procs, outs)))
     parts = [np.load(out + '.rank%d.npz' % r) for r in range(world)]
@@ -47,7 +54,7 @@ def _run(scenario, world, out):
     return res, cats[0], [tuple(q['shard']) for q in parts]
 
 
-@pytest.mark.parametrize('scenario', ['oceandrift', 'openoil', 'ensemble'])
+@pytest.mark.parametrize('scenario', ['oceandrift', 'openoil', 'ensemble', 'empty_rank'])
 def test_two_ranks_equal_one_rank(tmp_path, scenario):
     one, cats1, _ = _run(scenario, 1, str(tmp_path / 'w1'))
     two, cats2, shards = _run(scenario, 2, str(tmp_path / 'w2'))
@@ -68,11 +75,14 @@ def test_two_ranks_equal_one_rank(tmp_path, scenario):
     # holds only its own ID range of the schedule
     for q in two['_parts']:
         steps, ncoll = int(q['timing'][0]), int(q['timing'][1])
-        per_step = 2 if scenario == 'openoil' else 1
+        per_step = 2 if scenario in ('openoil', 'empty_rank') else 1     # (empty_rank: the depth of the deepest element)
         assert ncoll <= per_step * steps + 4, (steps, ncoll)
         assert int(q['n_sched_local']) == int(q['shard'][1] - q['shard'][0]) and int(q['n_total']) == len(one['ID'])
     if scenario == 'oceandrift':
         assert 'outside' in cats1 and (one['status'] != 0).sum() > 10
+    if scenario == 'empty_rank':     # the second shard held no element after the first step
+        second = two['_parts'][1]
+        assert 'outside' in cats1 and len(second['ID']) > 0 and (second['status'] != 0).all()
     if scenario == 'ensemble':
         # (ensemble members: the rank of an element among the present ones of ALL ranks selects the member --
         # odr_particles_set_rank_offset from the step's collective; stranded elements shift the ranks during the run)

@@ -41,10 +41,19 @@ def _leeway_props(P, n, ids):
         P.set_property(slot, v[ids].astype(np.float32))
 
 
-@pytest.mark.parametrize('name,n,steps,stride', [('c3', 10_000_000, 3, 499), ('c4', 6_250_000, 3, 311),
-                                                 ('c5', 10_000_000, 3, 499), ('c2', 1_000_000, 20, 97)])
-def test_subsample_is_bit_identical_to_the_full_size_run(name, n, steps, stride):
+_SIZES = [('c3', 10_000_000, 3, 499), ('c4', 6_250_000, 3, 311), ('c5', 10_000_000, 3, 499), ('c2', 1_000_000, 20, 97)]
+# EXACT under the ids the cases always had; FAST (bench.py's --stage-math default) for the Runge-Kutta workloads.  C5 has no FAST
+# case: the Leeway step is Euler, and its launch (odr_env_coast_leeway -> k_step_leeway, opendrift_amd/csrc/odrift.hip:1678-1682)
+# never reads the context's stage arithmetic -- stage_math is read by the Runge-Kutta launches only (odr_step.hip:63,
+# odr_step_mix.hip:24).
+_CASES = [c + ('exact',) for c in _SIZES] + [c + ('fast',) for c in _SIZES if c[0] != 'c5']
+
+
+@pytest.mark.parametrize('name,n,steps,stride,stage_math', _CASES,
+                         ids=['%s-%d-%d-%d' % c[:4] + ('' if c[4] == 'exact' else '-fast') for c in _CASES])
+def test_subsample_is_bit_identical_to_the_full_size_run(name, n, steps, stride, stage_math):
     ctx = Context(0, seed=0)
+    ctx.set_stage_math(stage_math)
     fields = bench.make_fields(name)
     wl = bench.Workload(name, ctx, fields, (0, 0, 1), via_torch=False)
     lon, lat, z = bench.seed_particles(name, fields, n, np.random.default_rng(1))
@@ -113,6 +122,50 @@ def test_c3_rk4_subsample_against_the_cpu_oracle():
     orc.advect_ocean_current(w, 2, lo, la, zz, np.ones(m, np.int32), np.ones(m, np.float32), u, v, t, wl.dt)
     assert np.abs(got['lon'] - lo).max() < 1e-10 and np.abs(got['lat'] - la).max() < 1e-10
     P.close(); ctx.close()
+
+
+# FAST: its per-step bound of 3e-9 deg is that of C3's 600 s step; the stage positions' direct move errs with the square of the
+# displacement, so C4's 900 s step takes 3e-9 * (900 / 600)^2 = 6.75e-9 deg
+@pytest.mark.parametrize('stage_math,bound', [('exact', 2e-9), ('fast', 3e-9 * (900.0 / 600.0) ** 2)])
+def test_c4_rk4_subsample_against_the_cpu_oracle(stage_math, bound):
+    """6.25 M elements, one fused RK4 launch on the full-size polar-stereographic block; every 3001st element against the C
+    oracle (exact arithmetic) on the world of tests/replay.py's C4 scenario.  EXACT at the polar-stereographic tolerance of the
+    C4 golden parity (test_gpu_parity.py::test_c4_golden_device, 2e-9 deg): the device's and the oracle's projections agree to
+    float64 round-off, not bit for bit, and a stage sample then rounds a float32 velocity the other way now and then (one
+    float32 ulp of 0.5 m/s over 900 s is 5e-10 deg) -- all but a few elements in a thousand agree to 1e-10 deg.  FAST at its
+    per-step bound (test_gpu_stage_math.py) scaled to the 900 s step."""
+    import replay
+    from oracle import oracle as orc
+    name, n = 'c4', 6_250_000
+    ctx = Context(0, seed=0)
+    ctx.set_stage_math(stage_math)
+    fields = bench.make_fields(name)
+    wl = bench.Workload(name, ctx, fields, (0, 0, 1), via_torch=False)
+    lon, lat, z = bench.seed_particles(name, fields, n, np.random.default_rng(5))
+    P = ctx.particles(n)
+    P.append(lon, lat, z=z)
+    P.sort_by_cell(wl.sid)
+    t = 1234.0
+    P.env_coast_advect(wl.vars, t, 'runge-kutta4', wl.dt, coastline='none', store_previous=True, count=False)
+    sub = np.arange(0, n, 3001)
+    got, ok = _state_by_id(P, sub.astype(np.int32))
+    assert ok.all()
+    P.close(); ctx.close()
+    g = fields['g']
+    scen = replay.scenario_c4({'g_' + k: g[k] for k in ['x', 'y', 't'] + fields['names']})
+    w = scen.oracle_world()          # (the world points into arrays the scenario keeps: `scen` must stay alive)
+    lo, la, zz = lon[sub].copy(), lat[sub].copy(), z[sub].copy()
+    u, v = orc.get_environment(w, [orc.VAR[U], orc.VAR[V]], lo, la, zz, t)
+    m = len(sub)
+    orc.advect_ocean_current(w, 2, lo, la, zz, np.ones(m, np.int32), np.ones(m, np.float32), u, v, t, wl.dt)
+    err = np.maximum(np.abs(got['lon'] - lo), np.abs(got['lat'] - la))
+    moved = np.hypot(got['lon'] - lon[sub], got['lat'] - lat[sub])
+    print('C4 6.25 M %s launch vs oracle: %.2e deg worst, %d of %d elements above 1e-10 deg' %
+          (stage_math.upper(), err.max(), (err > 1e-10).sum(), m))
+    assert (moved > 0).mean() > 0.9
+    assert err.max() < bound
+    if stage_math == 'exact':
+        assert (err > 1e-10).sum() <= m // 200
 
 
 def test_c2_time_reversal_one_million():
