@@ -513,6 +513,11 @@ int odr_sort_particles_ex(odr_ctx *ctx, odr_particles *p, int32_t source_id, int
  *         workgroup's rectangle), workgroups whose rectangle was cut to the LDS capacity, ranges in the current table}.
  * Synchronises the context's stream. */
 int odr_particles_tile_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out4);
+/* The fused step launch of odr_env_coast_advect (csrc/odr_kernels.hip.h k_step_grid) since the set was created:
+ * out2 = {launches that read the group's slot layout from its descriptors at run time, launches of an instantiation whose
+ *         layout is a compile-time constant (the C3 group under ODR_STAGE_FAST: csrc/odr_field.hip.h LayoutC3)}.
+ * The environment variable ODR_NO_LAYOUT_SPEC=1 keeps every launch on the run-time layout. */
+int odr_particles_step_layout_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out2);
 /* counts and min/max used for the per-step log line and early-outs (:2212-2233):
  * out16 = {n_active, lon_min, lon_max, lat_min, lat_max, z_min, z_max, D_max, stokes_sum_max,
  *          wind_speed_max, wdf_surface_max, n_surface, hs_max, tp_max, 0, 0} */

@@ -1765,6 +1765,29 @@ struct EnvGroupDesc {
 // 2 / 3 = 2-D / z-interpolated; S3I = one component of an interleaved 3-D pair on its own
 enum { ENV_S2 = 0, ENV_S3 = 1, ENV_S3I = 2, ENV_P2 = 3, ENV_P3 = 4, ENV_LAND = 5, ENV_SKIP = 6 };
 
+// The slot layout of the burst sampler and of the step launch's bookkeeping, as a template parameter.  LayoutRT reads it
+// from the EnvGroupDesc / StepDesc at run time (every group).  A static layout fixes it at compile time: the slot -> group
+// index maps, the gather modes, the Kelvin and rotation flags and the static-slot bits fold away (select chains over MAXG,
+// mode branches, scalar loads of the descriptors).  The host launches a static layout only when the group it built is
+// exactly that layout (layout_matches), otherwise LayoutRT; the arithmetic and its rounding points are the same.
+struct LayoutRT {
+  static constexpr bool STATIC = false;
+  __host__ __device__ static int nv_of(const EnvGroupDesc &G) { return G.nv; }
+  __host__ __device__ static int offA_of(const EnvGroupDesc &G) { return G.ps_off[0]; }
+};
+// the C3 group (odr_env_coast_advect of OceanDrift with sea floor and coastline, one 3-D lat/lon reader): u, v, land, depth, w
+// -- A = (u, v) interleaved 3-D pair at record offset 0, B = w (3-D), C = depth (2-D), D empty, L = land mask; depth and land
+// the same at both time levels (content ids); no Kelvin conversion; a lat / lon reader (no rotation); ssh is not in the
+// group (p.env[ssh])
+struct LayoutC3 {
+  static constexpr bool STATIC = true;
+  static constexpr int nv = 5, kA = 0, kB = 4, kC = 3, kD = -1, kL = 2;
+  static constexpr int mA = ENV_P3, mB = ENV_S3, mC = ENV_S2, offA = 0, ps_static = 4 | 16;
+  static constexpr int land_slot = 2, depth_slot = 3, ssh_slot = -1;
+  __host__ __device__ static constexpr int nv_of(const EnvGroupDesc &) { return nv; }
+  __host__ __device__ static constexpr int offA_of(const EnvGroupDesc &) { return offA; }
+};
+
 // one scalar variable at one time level -> value in the reference's dtype class; d = address of
 // the variable in node record 0
 __device__ __forceinline__ double var_level(const float *__restrict__ d, int var, int nzv, int es, int snz,
@@ -1864,28 +1887,26 @@ __device__ __forceinline__ void burst_math(int m, Get get, const Foot &ft, const
 struct EnvExport { float b[16], a[16]; unsigned n00, n11; int iz0; bool valid; bool combine = false; };   // combine: b[4c..4c+3] = uv_combine_z of corner c (ODR_STAGE_FAST, 3-D), a[] unused   // (plain floats: arrays of structs behind a pointer stay in scratch memory)
 // L: the loader of the node records (time 0 = the level before, 1 = the level after, or the same level when !tl); ft and
 // near_off hold ITS byte offsets (LdGlobal::foot / LdTile::foot)
-template <int PROJ, class LD>
+template <int PROJ, class LY, class LD>
 __device__ __forceinline__ void env_burst(const DevSource &s, const EnvGroupDesc &G, const LD &L, const Foot &ft, const ZBracket &zb,
                                           unsigned near_off, bool tl, double x, double y, float *out /*[MAXG]*/, EnvExport *X ODR_PT_PARAM) {
+  constexpr bool ST = LY::STATIC;
   const unsigned o[4] = {ft.o00, ft.o01, ft.o10, ft.o11};
   const unsigned iz0 = (unsigned)zb.iz0;
+  int kA, kB, kC, kD, kL, mA, mB, mC, temp_mask, ps_static, offA;
+  if constexpr (ST) {
+    kA = LY::kA; kB = LY::kB; kC = LY::kC; kD = LY::kD; kL = LY::kL;
+    mA = LY::mA; mB = LY::mB; mC = LY::mC; temp_mask = 0; ps_static = LY::ps_static; offA = LY::offA;
+  } else {
+    kA = G.bs[0]; kB = G.bs[1]; kC = G.bs[2]; kD = G.bs[3]; kL = G.bs[4];
+    mA = G.ps_mode[0]; mB = G.ps_mode[1]; mC = G.ps_mode[2]; temp_mask = G.temp_mask; ps_static = G.ps_static; offA = G.ps_off[0];
+  }
 #ifdef ODR_WHATIF_NO_BURST2   // what-if build (wrong values): slots B, C, D are not sampled -- what a fifth wave per SIMD buys
-  const int kA = G.bs[0], kB = -1, kC = -1, kD = -1, kL = G.bs[4];
-#elif defined(ODR_WHATIF_C3SPEC)   // what-if build (bench C3 only): the group's layout as compile-time constants
-  constexpr int kA = 0, kB = 2, kC = 3, kD = -1, kL = 4;
-#else
-  const int kA = G.bs[0], kB = G.bs[1], kC = G.bs[2], kD = G.bs[3], kL = G.bs[4];
+  kB = kC = kD = -1;
 #endif
-#ifdef ODR_WHATIF_C3SPEC
-  constexpr int mA = ENV_P3, mB = ENV_S3, mC = ENV_S2;
   double cs = 1, sn = 0;
-  constexpr int temp_mask = 0;
-#else
-  const int mA = G.ps_mode[0], mB = G.ps_mode[1], mC = G.ps_mode[2];
-  double cs = 1, sn = 0;
-  if (ODR_PROJ_ROTATES(PROJ) && G.rotates) rotation_cs<PROJ == PROJ_STERE_POLAR, PROJ == PROJ_EXT>(s.proj, x, y, cs, sn);
-  const int temp_mask = G.temp_mask;
-#endif
+  if (ODR_PROJ_ROTATES(PROJ) && !ST && G.rotates) rotation_cs<PROJ == PROJ_STERE_POLAR, PROJ == PROJ_EXT>(s.proj, x, y, cs, sn);
+  auto rot_of = [&](int q) { return ST ? 0 : G.ps_rot[q]; };
   auto finish = [&](int k, double v) {      // masked_invalid(...).astype('float32'), fallback, Kelvin -> Celsius
     float f = (float)v;
     if (!isfinite(f)) { const float fb = G.fallback[k]; f = isfinite(fb) ? fb : f; }   // rare: the scalar load stays in here
@@ -1927,7 +1948,6 @@ __device__ __forceinline__ void env_burst(const DevSource &s, const EnvGroupDesc
     // (a slot whose variable holds the same values at both time levels -- ps_static, from the blocks' content ids -- is
     // gathered once: four 32-cycle gathers less; the copies sit behind the slot's own last load, where the arithmetic
     // waits anyway)
-    const int ps_static = G.ps_static;
 #pragma unroll
     for (int c = 0; c < 4; ++c) Cb[c] = L.template ld<F2>(0, o[c] + dC);
     if (ps_static & 4) {
@@ -1946,15 +1966,19 @@ __device__ __forceinline__ void env_burst(const DevSource &s, const EnvGroupDesc
 #pragma unroll
       for (int c = 0; c < 4; ++c) Da[c] = L.template ld<float>(1, o[c] + dD);
     }
+    // (a static layout leaves no uniform branch between these gathers, their arithmetic and slot A's gathers: without this
+    // fence the scheduler mixes the three, slot A's records are requested while these returns are in flight, and the kernel
+    // spills (64-80 B of scratch at 96 registers).  With it: this burst, its arithmetic, then slot A's burst -- no spill.)
+    if constexpr (ST) __builtin_amdgcn_sched_barrier(0);
     if (kB >= 0) {
       double v0, v1;
       burst_math<2>(mB, [&](int t, int c, int q) { const F2 &r = t ? Ba[c] : Bb[c]; return q == 0 ? r.x : r.y; }, ft, zb, s.nz, tl, w, v0, v1);
-      emit(kB, mB, G.ps_rot[1], v0, v1);
+      emit(kB, mB, rot_of(1), v0, v1);
     }
     if (kC >= 0) {
       double v0, v1;
       burst_math<2>(mC, [&](int t, int c, int q) { const F2 &r = t ? Ca[c] : Cb[c]; return q == 0 ? r.x : r.y; }, ft, zb, s.nz, tl, w, v0, v1);
-      emit(kC, mC, G.ps_rot[2], v0, v1);
+      emit(kC, mC, rot_of(2), v0, v1);
     }
     if (kD >= 0) {
       double v0, v1;
@@ -1965,7 +1989,7 @@ __device__ __forceinline__ void env_burst(const DevSource &s, const EnvGroupDesc
 #endif
   // ---- burst 1: slot A and the land mask (34 registers in flight), then their arithmetic
   {
-    const unsigned dA = (unsigned)G.ps_off[0] + ((mA == ENV_P3 || mA == ENV_S3I) ? iz0 * 8u : mA == ENV_S3 ? iz0 * 4u : 0u);
+    const unsigned dA = (unsigned)offA + ((mA == ENV_P3 || mA == ENV_S3I) ? iz0 * 8u : mA == ENV_S3 ? iz0 * 4u : 0u);
     const unsigned dL = kL >= 0 ? near_off + (unsigned)G.ps_off[4] : 0u;
     F4 Ab[4], Aa[4];
 #pragma unroll
@@ -1988,7 +2012,6 @@ __device__ __forceinline__ void env_burst(const DevSource &s, const EnvGroupDesc
       }
       X->n00 = ft.n00; X->n11 = ft.n11; X->iz0 = zb.iz0; X->valid = true;
     }
-    const int ps_static = G.ps_static;
     const float Lb = L.template ld<float>(0, dL);
     float La;
     if (ps_static & 16) La = Lb; else La = L.template ld<float>(1, dL);   // same values at both levels: one gather less
@@ -1996,7 +2019,7 @@ __device__ __forceinline__ void env_burst(const DevSource &s, const EnvGroupDesc
       double v0, v1;
       burst_math<4>(mA, [&](int t, int c, int q) { const F4 &r = t ? Aa[c] : Ab[c]; return q == 0 ? r.x : q == 1 ? r.y : q == 2 ? r.z : r.w; },
                     ft, zb, s.nz, tl, w, v0, v1);
-      emit(kA, mA, G.ps_rot[0], v0, v1);
+      emit(kA, mA, rot_of(0), v0, v1);
     }
     if (kL >= 0)
       finish(kL, tl ? (double)__fadd_rn(__fmul_rn(Lb, (float)(1 - w)), __fmul_rn(La, (float)w)) : (double)Lb);
@@ -2091,7 +2114,7 @@ __device__ __forceinline__ EnvFront env_front(const DevSource &s, const DevBlock
 // BURST_ONLY: the caller guarantees G.burst (the fused step kernel: groups that do not fit the slots take the separate launches)
 // L: the loader of the node records (LdGlobal of G.bb / G.ba, or the workgroup's LDS tile); returns false when the
 // footprint or the land mask's nearest node is outside the loader's image (LdTile) -- `out` is then meaningless.
-template <int PROJ, bool BURST_ONLY, bool ZT, class LD>
+template <int PROJ, bool BURST_ONLY, bool ZT, class LY = LayoutRT, class LD>
 __device__ __forceinline__ bool env_group_sample(const DevWorld &W, const EnvGroupDesc &G, const LD &L, const EnvFront &fr,
                                                  double z, float *out /*[MAXG]*/, const double *zt,
                                                  ZBracket &zb_out, EnvExport *X = nullptr ODR_PT_PARAM) {
@@ -2108,9 +2131,9 @@ __device__ __forceinline__ bool env_group_sample(const DevWorld &W, const EnvGro
     if (!covered) {     // NaN -> fallback (rare: the scalar loads of the fallbacks stay in here)
 #pragma unroll
       for (int k = 0; k < MAXG; ++k) {
-        if (k >= G.nv) break;
+        if (k >= LY::nv_of(G)) break;
         const float fb = G.fallback[k];
-        out[k] = !isfinite(fb) ? __builtin_nanf("") : ((G.temp_mask >> k & 1) ? kelvin_to_celsius(fb) : fb);
+        out[k] = !isfinite(fb) ? __builtin_nanf("") : ((!LY::STATIC && (G.temp_mask >> k & 1)) ? kelvin_to_celsius(fb) : fb);
       }
     }
   }
@@ -2135,7 +2158,7 @@ __device__ __forceinline__ bool env_group_sample(const DevWorld &W, const EnvGro
     if (!(ok && ok_near)) return false;
     const bool tl = G.ba != nullptr && !G.all_static;
     ODR_PT_USE(ft.o00); ODR_PT_USE(ft.o11); ODR_PT_USE(near_off); ODR_PT(14);
-    if (burst) env_burst<PROJ>(s, G, L, ft, zb, near_off, tl, x, y, out, X ODR_PT_ARG);
+    if (burst) env_burst<PROJ, LY>(s, G, L, ft, zb, near_off, tl, x, y, out, X ODR_PT_ARG);
     else if constexpr (!BURST_ONLY) {
     static_assert(BURST_ONLY || sizeof(LD) == sizeof(LdGlobal), "the serial sampler reads the blocks in HBM");
 #pragma unroll
@@ -2208,14 +2231,14 @@ __device__ __forceinline__ LdGlobal env_global(const EnvGroupDesc &G) {
   return g;
 }
 // front door + sample from the blocks in HBM
-template <int PROJ, bool BURST_ONLY, bool ZT>
+template <int PROJ, bool BURST_ONLY, bool ZT, class LY = LayoutRT>
 __device__ __forceinline__ void env_group_fast(const DevWorld &W, const EnvGroupDesc &G, double lon,
                                                double lat, double z, float *out /*[MAXG]*/, const double *zt,
                                                ZBracket &zb_out, EnvExport *X = nullptr ODR_PT_PARAM, int f32idx = 0,
                                                const ProjStart ps = ProjStart()) {
   const DevSource &s = W.src[G.sid];
   const EnvFront fr = env_front<PROJ>(s, s.slot[G.geo_slot], lon, lat, z, f32idx, ps);
-  env_group_sample<PROJ, BURST_ONLY, ZT>(W, G, env_global(G), fr, z, out, zt, zb_out, X ODR_PT_ARG);
+  env_group_sample<PROJ, BURST_ONLY, ZT, LY>(W, G, env_global(G), fr, z, out, zt, zb_out, X ODR_PT_ARG);
 }
 // The records the main-loop sample fetched for slot A, as the kept footprint of the stage samples -- valid when slot A holds
 // the current (an interleaved pair of the stage samples' dimensionality) and the sample's time bracket is that of the
@@ -2239,16 +2262,17 @@ __device__ __forceinline__ UVKeep<IS3D> uv_keep_from(const EnvGroupDesc &G, cons
 // ODR_STAGE_FAST, 3-D: the same hand-over with the records combined over the bracket of the main-loop sample (uv_combine_z);
 // z_unchanged: the stages sample at the depth of the main-loop sample (false when the sea floor lifted the element in between:
 // another bracket, the kept values do not apply)
-template <bool IS3D, int SM>
+template <bool IS3D, int SM, class LY = LayoutRT>
 __device__ __forceinline__ UVKeep<IS3D> uv_keep_from_sm(const EnvGroupDesc &G, const EnvExport &X, const UVTime &th, const ZBracket &zb,
                                                         int nz, bool z_unchanged) {
   if constexpr (!(IS3D && SM == 1)) return uv_keep_from<IS3D>(G, X, th);
   else {
     UVKeep<IS3D> K;
     const bool tl = G.ba != nullptr && !G.all_static;
-    const float *mb = (const float *)((const char *)G.bb + G.ps_off[0]);
-    const float *ma = tl ? (const float *)((const char *)G.ba + G.ps_off[0]) : nullptr;
-    const bool fits = G.bs[0] == 0 && G.var[0] == VAR_U && G.ps_mode[0] == ENV_P3 && mb == th.b && ma == th.a;
+    const int offA = LY::offA_of(G);
+    const float *mb = (const float *)((const char *)G.bb + offA);
+    const float *ma = tl ? (const float *)((const char *)G.ba + offA) : nullptr;
+    const bool fits = (LY::STATIC || (G.bs[0] == 0 && G.var[0] == VAR_U && G.ps_mode[0] == ENV_P3)) && mb == th.b && ma == th.a;
     K.valid = fits && X.valid && z_unchanged;
     K.n00 = X.n00; K.n11 = X.n11; K.kb = (unsigned)X.iz0 * 8u;
     // X.combine: the burst already combined the corners over the bracket (time level `a` = `b` when the sample is on a level:

@@ -1088,7 +1088,8 @@ struct StepMix {
 #else
 #define ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) ((SCHEME) > 0 && (MIXQ) == 0 && ((PROJ) == PROJ_LATLONG || (PROJ) == PROJ_CURVILINEAR))
 #endif
-template <int SCHEME, int PROJ, bool IS3D, bool NOISE, int MIXQ = 0, bool MIXTL = false, int SM = 0>
+// LY: the slot layout of the group and of the bookkeeping below (odr_field.hip.h LayoutRT / LayoutC3)
+template <int SCHEME, int PROJ, bool IS3D, bool NOISE, int MIXQ = 0, bool MIXTL = false, int SM = 0, class LY = LayoutRT>
 __global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) ? ODR_PARK_WAVES_OF(PROJ, IS3D, SM) : ((MIXQ > 0 && ODR_STEP_WAVES(PROJ) < ODR_MIX_WAVES) ? ODR_MIX_WAVES : ODR_STEP_WAVES(PROJ))) void k_step_grid(const DevWorld *__restrict__ W, PView p, EnvGroupDesc G,
                                                      StepDesc S, double dt, float factor, UVTime th, UVTime tf,
                                                      unsigned long long *n_hit, StageNoise N,
@@ -1174,22 +1175,17 @@ __global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) ? ODR_PAR
       ps0 = proj_start(s0.proj, lw, lat);
     }
 #endif
-    env_group_fast<PROJ, true, IS3D>(*W, G, lon, lat, z, out, zt, zb_env, &X ODR_PT_ARG, 0, ps0);
-    UVKeep<IS3D> K = uv_keep_from_sm<IS3D, SM>(G, X, th, zb_env, W->src[G.sid].nz, true);   // (FAST, 3-D: combined over the bracket's levels)
+    env_group_fast<PROJ, true, IS3D, LY>(*W, G, lon, lat, z, out, zt, zb_env, &X ODR_PT_ARG, 0, ps0);
+    UVKeep<IS3D> K = uv_keep_from_sm<IS3D, SM, LY>(G, X, th, zb_env, W->src[G.sid].nz, true);   // (FAST, 3-D: combined over the bracket's levels)
     if constexpr (STATE_LATE) load_state();
     ODR_PT_USE(out[0]); ODR_PT_USE(out[1]); ODR_PT_USE(out[2]); ODR_PT_USE(out[3]); ODR_PT_USE(out[4]); ODR_PT(2);
     const int id = (NOISE || MIXQ > 0) ? p.id[i] : 0;
     if (MIXQ > 0) vmix_col_fill<(MIXQ > 0 ? MIXQ : 1), MIXTL>(W->src[M.D.sid], M.D, lon, lat, Kp, threadIdx.x);
     if (NOISE && S.main_noise) add_current_noise(N, 0, i, p.n, id, out[0], out[1]);
 #ifndef ODR_ABLATE_STORES   // what-if build (tools/ab_bench.sh)
-#ifdef ODR_WHATIF_C3SPEC
-#pragma unroll
-    for (int k = 0; k < 5; ++k) G.out_ptr[k][i] = out[k];
-#else
 #pragma unroll
     for (int k = 0; k < MAXG; ++k)
-      if (k < G.nv) G.out_ptr[k][i] = out[k];
-#endif
+      if (k < LY::nv_of(G)) G.out_ptr[k][i] = out[k];
     if (MIXQ == 0) {   // the sample position is what odr_vmix gathers its profiles at: not needed when the mixing is in here
       p.slon[i] = lon;
       p.slat[i] = lat;
@@ -1219,11 +1215,9 @@ __global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) ? ODR_PAR
       }
     }
     if (S.coast_action) {  // k_coast
-#ifdef ODR_WHATIF_C3SPEC
-      const float land = out[4];
-#else
-      const float land = S.land_slot == 2 ? out[2] : p.env[VAR_LAND][i];
-#endif
+      float land;
+      if constexpr (LY::STATIC) land = out[LY::land_slot];
+      else land = S.land_slot == 2 ? out[2] : p.env[VAR_LAND][i];
       if (land == 1.0f) {
         hit = true;
         if (S.coast_action == 1) {
@@ -1244,13 +1238,14 @@ __global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) ? ODR_PAR
       }
     }
     if (S.seafloor) {  // k_seafloor
-#ifdef ODR_WHATIF_C3SPEC
-      const float dep = out[3];
-      const float floorz = -__fadd_rn(dep, ssh0);
-#else
-      const float dep = S.depth_slot == 2 ? out[2] : (S.depth_slot == 3 ? out[3] : p.env[VAR_DEPTH][i]);
-      const float floorz = -__fadd_rn(dep, S.ssh_slot >= 0 ? pick_slot(out, S.ssh_slot) : ssh0);
-#endif
+      float floorz;
+      if constexpr (LY::STATIC) {
+        static_assert(LY::depth_slot >= 0 && LY::ssh_slot < 0, "a static layout holds the depth and not the ssh");
+        floorz = -__fadd_rn(out[LY::depth_slot], ssh0);
+      } else {
+        const float dep = S.depth_slot == 2 ? out[2] : (S.depth_slot == 3 ? out[3] : p.env[VAR_DEPTH][i]);
+        floorz = -__fadd_rn(dep, S.ssh_slot >= 0 ? pick_slot(out, S.ssh_slot) : ssh0);
+      }
       if (zz < (double)floorz) { zz = (double)floorz; if (MIXQ == 0) p.z[i] = zz; }
     }
     if (S.age_dt != 0.0f) {  // k_age

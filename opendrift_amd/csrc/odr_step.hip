@@ -350,3 +350,9 @@ int odr_env_coast_advect(odr_ctx *c, odr_particles *p, int nvars, const int32_t 
   if ((rc = coast_action ? read_counter(c, n_on_land) : 0)) return rc;
   return want_mix ? mix_after(c, p, t, dt, extras) : 0;
 }
+
+int odr_particles_step_layout_stats(odr_ctx *c, odr_particles *p, uint64_t *out2) {
+  REQUIRE(c && p && out2, "NULL argument");
+  out2[0] = p->step_launches[0]; out2[1] = p->step_launches[1];
+  return 0;
+}

@@ -57,6 +57,16 @@ static bool advect_dispatch(odr_ctx *c, odr_particles *p, int scheme, double t, 
   }
 }
 
+// the group the host built, and the bookkeeping slots of the step, are exactly the static layout LY (odr_field.hip.h).
+// (G.rotates / ps_rot are not compared: the static layouts serve lat / lon readers, which rotate nothing)
+template <class LY>
+static bool layout_matches(const EnvGroupDesc &G, const StepDesc &S) {
+  return G.burst && G.nv == LY::nv && G.bs[0] == LY::kA && G.bs[1] == LY::kB && G.bs[2] == LY::kC && G.bs[3] == LY::kD &&
+         G.bs[4] == LY::kL && G.var[0] == VAR_U && G.var[1] == VAR_V && G.ps_mode[0] == LY::mA && G.ps_mode[1] == LY::mB &&
+         G.ps_mode[2] == LY::mC && G.ps_off[0] == LY::offA && G.ps_static == LY::ps_static && G.temp_mask == 0 &&
+         S.land_slot == LY::land_slot && S.depth_slot == LY::depth_slot && S.ssh_slot == LY::ssh_slot;
+}
+
 // get_environment -> interact_with_coastline -> update_previous_state -> advect_ocean_current in
 // one launch (k_step_grid) when the current comes from one gridded reader; otherwise exactly the
 // four separate entry points, in that order.  Results are bit-identical either way
@@ -74,6 +84,17 @@ static void launch_step_grid(odr_ctx *c, odr_particles *p, const EnvGroupDesc &G
   float f = (float)factor;
   // what-if runs: ODR_OCC_LDS=<bytes> of (unused) dynamic LDS per workgroup caps the workgroups per CU (160 KiB / bytes)
   static const size_t occ_lds = getenv("ODR_OCC_LDS") ? (size_t)atoll(getenv("ODR_OCC_LDS")) : 0;
+  // the C3 group under the FAST stage arithmetic: its layout as compile-time constants (ODR_NO_LAYOUT_SPEC=1: the run-time
+  // layout, for A/B runs and tests)
+  if constexpr (SCHEME == 2 && !NOISE && SM == 1) {
+    if (odr_proj_template(s.proj) == PROJ_LATLONG && is3d && layout_matches<LayoutC3>(G, S) && !getenv("ODR_NO_LAYOUT_SPEC")) {
+      hipLaunchKernelGGL((k_step_grid<SCHEME, PROJ_LATLONG, true, NOISE, 0, false, SM, LayoutC3>), g, b, occ_lds, c->stream, c->dw, v, G, S,
+                         dt, f, th, tf, c->counter, N);
+      p->step_launches[1]++;
+      return;
+    }
+  }
+  p->step_launches[0]++;
 #define ODR_LAUNCH(PROJ, D3) hipLaunchKernelGGL((k_step_grid<SCHEME, PROJ, D3, NOISE, 0, false, SM>), g, b, occ_lds, c->stream, c->dw, v, G, S, dt, f, th, tf, c->counter, N)
   switch (odr_proj_template(s.proj)) {
     case PROJ_LATLONG: if (is3d) ODR_LAUNCH(PROJ_LATLONG, true); else ODR_LAUNCH(PROJ_LATLONG, false); break;

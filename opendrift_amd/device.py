@@ -901,6 +901,14 @@ class Particles:
         check(self.lib.odr_particles_tile_stats(self.ctx.h, self.h, out))
         return dict(launches=int(out[0]), handed_over=int(out[1]), rectangles_cut=int(out[2]), ranges=int(out[3]))
 
+    def step_layout_stats(self):
+        """Launches of the fused step kernel (odr_particles_step_layout_stats): with the run-time slot layout, with a
+        compile-time one."""
+        import ctypes as C
+        out = (C.c_uint64 * 2)()
+        check(self.lib.odr_particles_step_layout_stats(self.ctx.h, self.h, out))
+        return dict(runtime=int(out[0]), static=int(out[1]))
+
     def reduce_global(self, combine, wind_drift_depth=0.1, relative_wind=False):
         """Sharded run: this set's raw reductions -> combine(raw16) over the ranks (counts summed, maxima maximised) ->
         installed for the movers that follow, until reduce_unpin()."""
