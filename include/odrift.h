@@ -292,8 +292,7 @@ typedef struct {              /* optional bookkeeping of the same loop body, bet
   /* OceanDrift.vertical_mixing (+ vertical_advection) of the same step as part of this call: what
    * odr_vmix_fuse_vertical_advection + odr_vmix(t_epoch, dt, vmix_dt_mix, vmix_at_surface, ODR_RNG_DEVICE, NULL,
    * vmix_step) would do after it (vertical mixing reads the environment of the step start and changes z only, so it
-   * commutes with the horizontal movers).  When the diffusivity comes from the gridded reader of the current the
-   * mixing runs inside the same launch (k_step_grid<..., MIXQ>), otherwise the two calls are made in sequence. */
+   * commutes with the horizontal movers).  The mixing runs as a second launch, right after the step's. */
   int32_t vmix;              /* 0: not part of this call */
   int32_t vmix_at_surface;   /* drift:vertical_mixing_at_surface */
   int32_t vmix_vadv;         /* vertical advection after the mixing: -1 none, 0 below the surface, 1 including it */

@@ -772,7 +772,6 @@ __device__ __forceinline__ void rotation_cs(const DevProj &p, double x, double y
     sincos(rot, &sn, &cs);
     return;
   }
-#ifndef ODR_ROT_CS_SERIES   // (-DODR_ROT_CS_SERIES: the difference-of-inverses form of rounds 2-4 for every reader, below)
   if (rot_same_ellipsoid(p)) {
     // Round 5: the map is azimuthal and conformal on the geodesic's ellipsoid -- its +y axis has the azimuth +-(lambda - lambda0)
     // = the direction to the pole in the plane, and the 10 m line of rotate_vectors starts half its change of longitude times
@@ -792,7 +791,6 @@ __device__ __forceinline__ void rotation_cs(const DevProj &p, double x, double y
     else { cs = cD - q * sD; sn = -sD - q * cD; }
     return;
   }
-#endif
   const GeodConst &g = c_geod;
   const double inva = fast_rcp(p.a);
   double X = (x - p.x0) * inva, Y1 = (y - p.y0) * inva, Y2 = (y + 10.0 - p.y0) * inva;
@@ -1225,12 +1223,6 @@ __device__ __forceinline__ ZBracket zbracket(const DevSource &s, double z, const
 
 __device__ __forceinline__ float bil4(double v00, double v01, double v10, double v11, double wy0,
                                       double ty, double wx0, double tx) {
-#ifdef ODR_ABL_BIL4   // what-if build (wrong values): the bilinear layer value without its eleven float64 operations
-  return (float)v00 + (float)v11;
-#endif
-#ifdef ODR_WHATIF_BILW   // what-if build: weights multiplied out once per particle (the products are common subexpressions), fused
-  return (float)__builtin_fma(v11, ty * tx, __builtin_fma(v10, ty * wx0, __builtin_fma(v01, wy0 * tx, v00 * (wy0 * wx0))));
-#endif
   double t = __dmul_rn(__dmul_rn(v00, wy0), wx0);
   t = __dadd_rn(t, __dmul_rn(__dmul_rn(v01, wy0), tx));
   t = __dadd_rn(t, __dmul_rn(__dmul_rn(v10, ty), wx0));
@@ -1260,27 +1252,13 @@ struct __attribute__((aligned(4))) F2 { float x, y; };
 // load at a 32-bit byte offset from a wave-uniform base (scalar base + vector offset addressing)
 template <typename T>
 __device__ __forceinline__ T ld_off(const float *__restrict__ base, unsigned byte_off) {
-#ifdef ODR_ABLATE_LOADS   // what-if build: no field gathers (tools/ab_bench.sh)
-  T t;
-  float *f = (float *)&t;
-  for (unsigned k = 0; k < sizeof(T) / 4; ++k) f[k] = (float)(byte_off & 1023u) * 1e-4f + (float)k;
-  return t;
-#else
-#ifdef ODR_FLAT_GATHERS
-  return *(const T *)((const char *)base + byte_off);
-#else
   // buffer addressing: descriptor of the wave-uniform base in scalar registers + the 32-bit offset as it is -- no
   // 64-bit address arithmetic per gather (the flat form costs one v_lshl_add_u64 per load: 503 in k_step_grid<RK4>)
   static_assert(sizeof(T) == 4 || sizeof(T) == 8 || sizeof(T) == 16, "gather width");
-#ifdef ODR_ABLATE_UNIFORM_GATHER   // what-if build: every lane reads lane 0's address (one L1 access per gather instead of up to 64; wrong values)
-  byte_off = (unsigned)__builtin_amdgcn_readfirstlane((int)byte_off);
-#endif
   const __amdgpu_buffer_rsrc_t r = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, 0xffffffff, 0x00020000);
   if constexpr (sizeof(T) == 4) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b32(r, byte_off, 0, 0));
   else if constexpr (sizeof(T) == 8) return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b64(r, byte_off, 0, 0));
   else return __builtin_bit_cast(T, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, 0));
-#endif
-#endif
 }
 
 // ------------------------------------------------------------------ where a sample reads its node records
@@ -1399,7 +1377,7 @@ __device__ __forceinline__ void uv_fetch(const LD &ld, bool has_a, const Foot &f
 template <bool IS3D, bool KEEPS, class LD>
 __device__ __forceinline__ const UVRec<IS3D> &uv_records(const LD &ld, bool has_a, const Foot &ft, unsigned kb, UVKeep<IS3D> &K, bool keep,
                                                          UVRec<IS3D> &scratch) {
-#if defined(ODR_NO_KEEP) || defined(ODR_TU_TILE)   // A/B build; the LDS-tile kernels (their records are two cycles away, the registers are not there)
+#ifdef ODR_TU_TILE   // the LDS-tile kernels (their records are two cycles away, the registers are not there)
   keep = false;
 #endif
   if constexpr (KEEPS) {
@@ -1540,9 +1518,7 @@ __device__ __forceinline__ bool uv_sample_fast(const DevSource &s, const DevBloc
   double x, y;
   if (PROJ == PROJ_LATLONG) { x = lon; y = lat; }
   else if (PROJ == PROJ_CURVILINEAR) curvi_locate(s.proj, lon, lat, x, y);
-#ifndef ODR_FULL_STAGE_PROJECTION
   else if (ps.ok) proj_fwd_near<PROJ == PROJ_STERE_POLAR, PROJ == PROJ_EXT>(s.proj, ps, lon, lat, x, y);   // (by value: a pointer would pin the struct to scratch memory)
-#endif
   else proj_fwd<PROJ == PROJ_STERE_POLAR, PROJ == PROJ_EXT>(s.proj, lon, lat, x, y);
   const double xchk = cover_x<PROJ>(s.proj.kind, s.lon_mode, x);
   float fu = __builtin_nanf(""), fv = __builtin_nanf("");
@@ -1635,17 +1611,11 @@ __device__ __forceinline__ bool uv_sample_stage_f32(const DevSource &s, const De
   if (PROJ == PROJ_LATLONG) { x = lon; y = lat; }
   else if (PROJ == PROJ_CURVILINEAR) curvi_locate(s.proj, lon, lat, x, y);
   else if (ps.ok) {
-#ifdef ODR_NO_STAGE_ROT_CLOSED_FORM   // A/B build: the rotation of every stage sample from rotation_cs, as in rounds 3-4
-    proj_fwd_near<PROJ == PROJ_STERE_POLAR, PROJ == PROJ_EXT>(s.proj, ps, lon, lat, x, y);
-#else
     proj_fwd_near<PROJ == PROJ_STERE_POLAR, PROJ == PROJ_EXT>(s.proj, ps, lon, lat, x, y, rot);
     have_rot = rot[0] <= 1.5;
-#endif
   } else {
     proj_fwd<PROJ == PROJ_STERE_POLAR, PROJ == PROJ_EXT>(s.proj, lon, lat, x, y);
-#ifndef ODR_NO_STAGE_ROT_CLOSED_FORM
     if (ODR_PROJ_ROTATES(PROJ) && PROJ != PROJ_STERE_POLAR && PROJ != PROJ_EXT) have_rot = rot_closed_form(s.proj, x, y, lat, rot);
-#endif
   }
   const double xchk = cover_x<PROJ>(s.proj.kind, s.lon_mode, x);
   float fu = __builtin_nanf(""), fv = __builtin_nanf("");
@@ -1665,7 +1635,7 @@ __device__ __forceinline__ bool uv_sample_stage_f32(const DevSource &s, const De
     if constexpr (IS3D) {
       // the footprint's records combined over the bracket's two levels (uv_fetch_combined): kept in K when the reader keeps
       bool kp = keep;
-#if defined(ODR_NO_KEEP) || defined(ODR_TU_TILE)
+#ifdef ODR_TU_TILE
       kp = false;
 #endif
       const unsigned kb = (unsigned)zb.iz0 * 8u;
@@ -1901,9 +1871,6 @@ __device__ __forceinline__ void env_burst(const DevSource &s, const EnvGroupDesc
     kA = G.bs[0]; kB = G.bs[1]; kC = G.bs[2]; kD = G.bs[3]; kL = G.bs[4];
     mA = G.ps_mode[0]; mB = G.ps_mode[1]; mC = G.ps_mode[2]; temp_mask = G.temp_mask; ps_static = G.ps_static; offA = G.ps_off[0];
   }
-#ifdef ODR_WHATIF_NO_BURST2   // what-if build (wrong values): slots B, C, D are not sampled -- what a fifth wave per SIMD buys
-  kB = kC = kD = -1;
-#endif
   double cs = 1, sn = 0;
   if (ODR_PROJ_ROTATES(PROJ) && !ST && G.rotates) rotation_cs<PROJ == PROJ_STERE_POLAR, PROJ == PROJ_EXT>(s.proj, x, y, cs, sn);
   auto rot_of = [&](int q) { return ST ? 0 : G.ps_rot[q]; };
@@ -1927,7 +1894,6 @@ __device__ __forceinline__ void env_burst(const DevSource &s, const EnvGroupDesc
   // corner, only the byte offset depends on the mode: a load whose destination registers differ between uniform branches
   // ends in a copy at the join, i.e. in a wait right behind it, and the burst would be gone.  A narrower variable in a
   // wider slot over-reads into its neighbours in the node record (blocks end with 64 spare bytes); empty slots read offset 0.
-#ifndef ODR_BURST_A_FIRST
   // (round 5: the slots B, C, D go FIRST -- their 40 registers of returns are consumed before slot A's records, which the stage
   // samples keep (UVKeep: 32 registers), are requested; with slot A first the kept records and this burst's returns were in
   // flight together, through the phase that set the kernel's register count.  Same gathers, same arithmetic, same bits.)
@@ -1986,7 +1952,6 @@ __device__ __forceinline__ void env_burst(const DevSource &s, const EnvGroupDesc
       emit(kD, ENV_S2, 0, v0, v1);
     }
   }
-#endif
   // ---- burst 1: slot A and the land mask (34 registers in flight), then their arithmetic
   {
     const unsigned dA = (unsigned)offA + ((mA == ENV_P3 || mA == ENV_S3I) ? iz0 * 8u : mA == ENV_S3 ? iz0 * 4u : 0u);
@@ -2025,60 +1990,6 @@ __device__ __forceinline__ void env_burst(const DevSource &s, const EnvGroupDesc
       finish(kL, tl ? (double)__fadd_rn(__fmul_rn(Lb, (float)(1 - w)), __fmul_rn(La, (float)w)) : (double)Lb);
   }
   ODR_PT_USE(out[0]); ODR_PT_USE(out[1]); ODR_PT_USE(out[2]); ODR_PT(15);
-#ifdef ODR_BURST_A_FIRST
-  // ---- burst 2: slots B, C, D (40 registers), then their arithmetic
-  if (kB >= 0 || kC >= 0 || kD >= 0) {
-    const unsigned dB = (unsigned)G.ps_off[1] + (mB == ENV_S3 ? iz0 * 4u : 0u);
-    const unsigned dC = (unsigned)G.ps_off[2] + (mC == ENV_S3 ? iz0 * 4u : 0u);
-    const unsigned dD = (unsigned)G.ps_off[3];
-    F2 Bb[4], Ba[4], Cb[4], Ca[4];
-    float Db[4], Da[4];
-    // (measured, round 4: these gathers issued right behind slot A's, one memory round trip less per particle at the same 126
-    // registers: launch 0.615 -> 0.633 ms, C5 0.776 -> 0.861 -- 74 registers of returns in flight per lane queue behind one another)
-    // (empty slots issue their gathers too, at offset 0.  Measured alternatives, C3: guarding a slot's gathers with the
-    // condition that also guards its arithmetic lets the compiler merge the two blocks -- gathers, wait, arithmetic, slot by
-    // slot -- 1.26 -> 1.45 ms per step; a zero-length buffer descriptor for empty slots 1.26 -> 1.31)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) { Bb[c] = L.template ld<F2>(0, o[c] + dB); Ba[c] = L.template ld<F2>(1, o[c] + dB); }
-    // (a slot whose variable holds the same values at both time levels -- ps_static, from the blocks' content ids -- is
-    // gathered once: four 32-cycle gathers less; the copies sit behind the slot's own last load, where the arithmetic
-    // waits anyway)
-    const int ps_static = G.ps_static;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) Cb[c] = L.template ld<F2>(0, o[c] + dC);
-    if (ps_static & 4) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) Ca[c] = Cb[c];
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) Ca[c] = L.template ld<F2>(1, o[c] + dC);
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) Db[c] = L.template ld<float>(0, o[c] + dD);
-    if (ps_static & 8) {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) Da[c] = Db[c];
-    } else {
-#pragma unroll
-      for (int c = 0; c < 4; ++c) Da[c] = L.template ld<float>(1, o[c] + dD);
-    }
-    if (kB >= 0) {
-      double v0, v1;
-      burst_math<2>(mB, [&](int t, int c, int q) { const F2 &r = t ? Ba[c] : Bb[c]; return q == 0 ? r.x : r.y; }, ft, zb, s.nz, tl, w, v0, v1);
-      emit(kB, mB, G.ps_rot[1], v0, v1);
-    }
-    if (kC >= 0) {
-      double v0, v1;
-      burst_math<2>(mC, [&](int t, int c, int q) { const F2 &r = t ? Ca[c] : Cb[c]; return q == 0 ? r.x : r.y; }, ft, zb, s.nz, tl, w, v0, v1);
-      emit(kC, mC, G.ps_rot[2], v0, v1);
-    }
-    if (kD >= 0) {
-      double v0, v1;
-      burst_math<1>(ENV_S2, [&](int t, int c, int q) { return t ? Da[c] : Db[c]; }, ft, zb, s.nz, tl, w, v0, v1);
-      emit(kD, ENV_S2, 0, v0, v1);
-    }
-  }
-#endif
   ODR_PT_USE(out[3]); ODR_PT_USE(out[4]); ODR_PT(16);
 }
 

@@ -69,15 +69,9 @@ static constexpr double kTiny = 1.4916681462400413e-154;
 // a * b + k for a literal / constant-memory k.  (Tried: VOP3 v_fma_f64 with k as a scalar-register addend via
 // inline asm, which removes the two v_mov_b32 the compiler spends per 64-bit literal -- 12 % fewer vector
 // instructions, but 4 % SLOWER in an A/B run on the same box: the Horner chains are latency-bound at ~4 waves
-// per SIMD and the moves were filling their bubbles.  ODR_SGPR_FMA keeps the experiment buildable.)
+// per SIMD and the moves were filling their bubbles.)
 __device__ __forceinline__ double fma_k(double a, double b, double k) {
-#ifdef ODR_SGPR_FMA
-  double d;
-  asm("v_fma_f64 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "s"(k));
-  return d;
-#else
   return fma(a, b, k);
-#endif
 }
 
 // float64 reciprocal / reciprocal square root from the hardware seeds (v_rcp_f64 / v_rsq_f64)
@@ -247,11 +241,6 @@ __device__ __forceinline__ double atan2_fin(double y, double x) {
   double r = mn * rr;
   r = fma(fma(-mx, r, mn), rr, r);
   const double z = r * r;
-#ifdef ODR_ATAN_HORNER
-  double q = c_atanq[19];
-#pragma unroll
-  for (int k = 18; k >= 0; --k) q = fma_k(q, z, c_atanq[k]);
-#else
   // even / odd halves in w = z^2: two independent Horner chains of depth 9 instead of one of depth 19
   // (the evaluation is latency-bound, not issue-bound)
   const double w = z * z;
@@ -259,7 +248,6 @@ __device__ __forceinline__ double atan2_fin(double y, double x) {
 #pragma unroll
   for (int k = 16; k >= 0; k -= 2) { qe = fma_k(qe, w, c_atanq[k]); qo = fma_k(qo, w, c_atanq[k + 1]); }
   double q = fma(qo, z, qe);
-#endif
   double a = fma(r * z, q, r);
   a = ay > ax ? 1.57079632679489661923 - a : a;
   a = signbit(x) ? 3.14159265358979323846 - a : a;
@@ -321,11 +309,6 @@ __device__ __forceinline__ void geod_direct_sc(const GeodOrigin &o, double salp1
   // reference stay exact; the geodesic series are float64 and may fuse multiply-adds
 #pragma clang fp contract(fast)
   const GeodConst &g = c_geod;
-#ifdef ODR_ABLATE_GEOD   // what-if build: a flat-earth step instead of the geodesic (tools/ab_bench.sh)
-  lat2 = o.lat1 + s12 * calp1 * 8.98e-6;
-  lon2 = o.lon1n + s12 * salp1 * 8.98e-6 * o.cbet1;
-  return;
-#endif
   const double sbet1 = o.sbet1, cbet1 = o.cbet1;
 
   double salp0 = salp1 * cbet1;

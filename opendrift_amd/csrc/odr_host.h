@@ -47,7 +47,6 @@ int odr_i_fail(int code, const char *fmt, ...);   // records the message for odr
 struct Staged { DevBlock blk; float *base; size_t bytes; unsigned long long cid[NVAR]; };   // uploaded, not yet committed (cid: odr_block_set_content_ids)
 struct Retired { void *ptr; size_t bytes; hipEvent_t ev; };       // replaced block, freed once the compute stream passed
 
-constexpr int ODR_MAX_LANES = 8;
 struct odr_ctx {
   int device;
   unsigned long long seed;
@@ -122,15 +121,10 @@ struct odr_ctx {
   bool red_partial = false;  // red[] was formed by the step launch (odr_ctx_set_step_reduce): only the slots the movers' == 0 tests read, R_NSURF as a flag
   int step_reduce_on = 0, step_reduce_rel = 0;
   double step_reduce_wdd = 0.1;
-  // lanes of the fused step (odr_step.hip, step_in_lanes): contiguous particle ranges on streams of their own
-  hipStream_t lane_stream[ODR_MAX_LANES];
-  hipEvent_t lane_step[ODR_MAX_LANES], lane_done[ODR_MAX_LANES], lane_fork;
-  int lanes_ready;
 };
 
 struct odr_particles {
   long long cap, n, ndead, dead_cap;
-  long long win;        // first element of the window that view() exposes (0 except inside step_in_lanes)
   int ice_kind;         // odr_set_element_factor
   // ranks of the present elements in ascending ID (ensemble members, odr_i_ensure_ranks)
   int *rank;
@@ -196,15 +190,14 @@ static inline unsigned nblk(long long n) { return (unsigned)((n + BLOCK - 1) / B
 static inline PView view(const odr_particles *p) {
   PView v;
   v.n = p->n;
-  const long long w = p->win;
-  v.lon = p->d64[0] + w; v.lat = p->d64[1] + w; v.z = p->d64[2] + w; v.plon = p->d64[3] + w; v.plat = p->d64[4] + w;
-  v.slon = p->d64[5] + w; v.slat = p->d64[6] + w;
-  v.id = p->i32[0] + w; v.status = p->i32[1] + w; v.moving = p->i32[2] + w;
-  v.wdf = p->f32[0] + w; v.cdf = p->f32[1] + w; v.tv = p->f32[2] + w; v.age = p->f32[3] + w;
-  for (int k = 0; k < NVAR; ++k) v.env[k] = p->env[k] ? p->env[k] + w : nullptr;
-  for (int k = 0; k < 9; ++k) v.aux[k] = p->aux[k] ? p->aux[k] + w : nullptr;
+  v.lon = p->d64[0]; v.lat = p->d64[1]; v.z = p->d64[2]; v.plon = p->d64[3]; v.plat = p->d64[4];
+  v.slon = p->d64[5]; v.slat = p->d64[6];
+  v.id = p->i32[0]; v.status = p->i32[1]; v.moving = p->i32[2];
+  v.wdf = p->f32[0]; v.cdf = p->f32[1]; v.tv = p->f32[2]; v.age = p->f32[3];
+  for (int k = 0; k < NVAR; ++k) v.env[k] = p->env[k];
+  for (int k = 0; k < 9; ++k) v.aux[k] = p->aux[k];
   v.ice = p->ice_kind; v.pad = 0;
-  v.rank = p->rank_on && p->rank ? p->rank + w : nullptr;
+  v.rank = p->rank_on && p->rank ? p->rank : nullptr;
   return v;
 }
 

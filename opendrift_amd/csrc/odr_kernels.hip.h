@@ -34,22 +34,15 @@ constexpr int BLOCK = ODR_BLOCK;  // threads per workgroup (A/B builds may overr
 #define ODR_LATLONG_WAVES 1
 #endif
 #define ODR_WAVES(PROJ) ((PROJ) == PROJ_LATLONG ? ODR_LATLONG_WAVES : ((PROJ) == PROJ_EXT ? 1 : ODR_POLAR_WAVES))
-#ifndef ODR_MIX_WAVES
-#define ODR_MIX_WAVES 3   // the step kernel with the mixing inside: 167 VGPRs with the kept (u,v) records (3 waves per SIMD); held at 128 it spills
-#endif
 
 // XCD-aware block order.  Workgroups are dispatched round-robin over the 8 XCDs (each with its own L2), so with
 // the natural order the eight L2s all stream the whole (spatially sorted) particle range and every field tile is
 // fetched by all of them.  pid() gives XCD x the x-th contiguous eighth of the range instead: the particles of one
 // region -- and the field records they gather -- stay in one L2.
 __device__ __forceinline__ long long pid() {
-#ifdef ODR_NO_XCD_REMAP
-  return (long long)blockIdx.x * BLOCK + threadIdx.x;
-#else
   const unsigned nb = gridDim.x, b = blockIdx.x, per = nb >> 3, rem = nb & 7u, x = b & 7u, j = b >> 3;
   const unsigned lb = x * per + (x < rem ? x : rem) + j;
   return (long long)lb * BLOCK + threadIdx.x;
-#endif
 }
 
 struct PView {  // device pointers of the active set
@@ -126,22 +119,12 @@ __device__ __forceinline__ void azimuth_sincos_f32(float xv, float yv, double &s
 
 // Start point of the (up to five) geodesics of one particle-step and one step along it.  Default: Legendre series
 // about the start point (odr_geodesic.hip.h), the full Karney solution only for steps it does not cover.
-// -DODR_FULL_GEODESIC: every step through the full solution (A/B measurements, strict build).
-#ifdef ODR_FULL_GEODESIC
-typedef GeodOrigin GeodStart;
-__device__ __forceinline__ GeodStart geod_start(double lat, double lon) { return geod_origin(lat, lon); }
-__device__ __forceinline__ void geod_step(const GeodStart &o, double salp, double calp, double s12, double &lat2,
-                                          double &lon2) {
-  geod_direct_sc(o, salp, calp, s12, lat2, lon2);
-}
-#else
 typedef GeodLocal GeodStart;
 __device__ __forceinline__ GeodStart geod_start(double lat, double lon) { return geod_local_origin(lat, lon); }
 __device__ __forceinline__ void geod_step(const GeodStart &o, double salp, double calp, double s12, double &lat2,
                                           double &lon2) {
   geod_local_move(o, s12 * salp, s12 * calp, lat2, lon2);
 }
-#endif
 
 // The start-point coefficients of the series geodesic (12 doubles = 24 registers) live from the first stage position to the
 // final move, across the three stage samples -- the register peak of k_step_grid.  PARKED: they wait in the workgroup's LDS
@@ -149,7 +132,6 @@ __device__ __forceinline__ void geod_step(const GeodStart &o, double salp, doubl
 // the kernel then fits 96 registers = 5 waves per SIMD without scratch memory (round 3; 111 registers = 4 waves before,
 // 80 B of scratch when merely capped at 96).
 constexpr int GEOD_PARK = 15;   // (round 5: + the start point itself, slots 12 / 13, and the drift factor of the final move, slot 14)
-#ifndef ODR_FULL_GEODESIC
 typedef volatile __attribute__((address_space(3))) double lds_f64;   // explicit LDS pointer: ds_read / ds_write, not flat accesses
 __device__ __forceinline__ void geod_park(const GeodLocal &o, lds_f64 *slot) {
   slot[0 * BLOCK] = o.iN; slot[1 * BLOCK] = o.qs; slot[2 * BLOCK] = o.kphi; slot[3 * BLOCK] = o.klam;
@@ -197,7 +179,6 @@ __device__ __forceinline__ void geod_local_move_parked(lds_f64 *slot, double x, 
   lat2 = fma(kphi, p, lat1);
   lon2 = ang_normalize(fma(klam, l, lon1n));
 }
-#endif
 
 // update_positions (basemodel/__init__.py:4631-4657), float32 velocities
 __device__ __forceinline__ void move_f32_from(const GeodStart &o, double &lon, double &lat, float u,
@@ -217,7 +198,7 @@ __device__ __forceinline__ void move_f32(double &lon, double &lat, float u, floa
 // The series geodesic takes the step by its east / north components distance * sin / cos(azimuth) = u dt, v dt (moving is 0 or
 // 1): formed directly -- no arctan2, no square root, no division.  The reference's own azimuth carries a float64 rounding of up
 // to 180 deg (3e-16 rad of direction = 3e-16 of the step across it); the direct components are inside that.
-// ODR_FULL_GEODESIC builds and non-finite velocities keep azimuth and distance (library semantics).
+// Non-finite velocities keep azimuth and distance (library semantics).
 __device__ __forceinline__ void move_f64_polar(double u, double v, int moving, double dt, double &salp, double &calp, double &s12) {
   const double h2 = fma(u, u, v * v);
   salp = 0.0; calp = 1.0;
@@ -236,11 +217,6 @@ __device__ __forceinline__ void move_f64(double &lon, double &lat, double u, dou
                                          double dt) {
   GeodStart o = geod_start(lat, lon);
   double lo, la;
-#ifdef ODR_FULL_GEODESIC
-  double salp, calp, s12;
-  move_f64_polar(u, v, moving, dt, salp, calp, s12);
-  geod_step(o, salp, calp, s12, la, lo);
-#else
   const double h2 = fma(u, u, v * v);
   if (h2 < 1.7e308) {
     const double hd = (double)moving * dt;
@@ -250,7 +226,6 @@ __device__ __forceinline__ void move_f64(double &lon, double &lat, double u, dou
     move_f64_polar(u, v, moving, dt, salp, calp, s12);
     geod_step(o, salp, calp, s12, la, lo);
   }
-#endif
   lon = lo;
   lat = la;
 }
@@ -261,9 +236,6 @@ struct MoveChain {
   bool next;        // the previous move was a series move from lat0 (sphi / cphi = its sine / cosine)
 };
 __device__ __forceinline__ void move_f64_chain(MoveChain &mc, double &lon, double &lat, double u, double v, int moving, double dt) {
-#ifdef ODR_FULL_GEODESIC
-  move_f64(lon, lat, u, v, moving, dt);
-#else
   const GeodLocal o = mc.next ? geod_local_origin_next(mc.lat0, lat, lon, mc.sphi, mc.cphi) : geod_local_origin_sc(lat, lon, mc.sphi, mc.cphi);
   mc.lat0 = lat;
   double lo, la;
@@ -278,14 +250,10 @@ __device__ __forceinline__ void move_f64_chain(MoveChain &mc, double &lon, doubl
   }
   lon = lo;
   lat = la;
-#endif
 }
 
 // the same for float32 velocities (Leeway.update: the leeway move, then the current's)
 __device__ __forceinline__ void move_f32_chain(MoveChain &mc, double &lon, double &lat, float u, float v, int moving, double dt) {
-#ifdef ODR_FULL_GEODESIC
-  move_f32(lon, lat, u, v, moving, dt);
-#else
   const GeodLocal o = mc.next ? geod_local_origin_next(mc.lat0, lat, lon, mc.sphi, mc.cphi) : geod_local_origin_sc(lat, lon, mc.sphi, mc.cphi);
   mc.lat0 = lat;
   double salp, calp;
@@ -295,7 +263,6 @@ __device__ __forceinline__ void move_f32_chain(MoveChain &mc, double &lon, doubl
   mc.next = geod_local_move_ok(o, s12 * salp, s12 * calp, la, lo);
   lon = lo;
   lat = la;
-#endif
 }
 
 // RK sub-stage position: geod.fwd(lon, lat, az, speed*dt*.5) with az and dist in float32 (physics_methods.py:629-635);
@@ -311,30 +278,22 @@ __device__ __forceinline__ void move_f32_chain(MoveChain &mc, double &lon, doubl
 template <int SM>
 __device__ __forceinline__ void stage_pos(const GeodStart &o, float u, float v, float dtf,
                                           double &lon2, double &lat2) {
-#if defined(ODR_FULL_GEODESIC)
-  constexpr bool direct = false;
-#else
   constexpr bool direct = SM == 1;
-#endif
   if constexpr (!direct) {
     double salp, calp;
     azimuth_sincos_f32(u, v, salp, calp);
     float dist = __fmul_rn(__fmul_rn(speed_f32(u, v), dtf), 0.5f);
     geod_step(o, salp, calp, (double)dist, lat2, lon2);
   } else {
-#ifndef ODR_FULL_GEODESIC
     const double hd = 0.5 * (double)dtf;
     geod_local_move(o, (double)u * hd, (double)v * hd, lat2, lon2);
-#endif
   }
 }
-#ifndef ODR_FULL_GEODESIC
 // ODR_STAGE_FAST with the coefficients parked in LDS
 __device__ __forceinline__ void stage_pos_parked(lds_f64 *slot, float u, float v, float dtf, double &lon2, double &lat2) {
   const double hd = 0.5 * (double)dtf;
   geod_local_move_parked(slot, (double)u * hd, (double)v * hd, lat2, lon2);
 }
-#endif
 // the same with the mode as a (wave-uniform) run-time value: kernels that serve any reader mix
 __device__ __forceinline__ void stage_pos_rt(int sm, const GeodStart &o, float u, float v, float dtf, double &lon2, double &lat2) {
   if (sm == 1) stage_pos<1>(o, u, v, dtf, lon2, lat2);
@@ -439,8 +398,7 @@ __device__ __forceinline__ void add_current_noise(const StageNoise &N, int call,
   }
 }
 
-// ---- vertical mixing on a K column in LDS: device functions shared by k_vmix_col (odr_mix.hip) and the fused
-// step + mixing kernel k_step_grid<..., MIXQ> (odr_step_mix.hip)
+// ---- vertical mixing on a K column in LDS: device functions of k_vmix_col (odr_mix.hip)
 // Philox4x32-10 (Salmon, Moraes, Dror, Shaw: "Parallel random numbers: as easy as 1, 2, 3", SC'11), one 128-bit block
 // from a 128-bit counter and a 64-bit key, evaluated directly: the mixing loop names the block it needs (element, step,
 // block number) instead of advancing a generator state.  (Rounds 1-3 drew the same words through rocrand's state object,
@@ -515,14 +473,11 @@ struct VMixDesc {
 };
 
 // K column of one particle at (lon, lat) -> Kp[level][tid] (LDS), time-interpolated like the ReaderBlock's profiles
-// quads: the 4-level quads of the column to gather (bit q; wave-uniform in k_vmix_col, see vmix_col_particle: a particle only
-// ever reads the levels around its own, and a quad nobody of the wave needs is not fetched)
 // hook: arithmetic of the caller that does not depend on the column (the first Philox block of the particle's stream), run
 // right behind the gathers of the first quad so that it overlaps their flight instead of standing in front of their issue
-struct VMixNoHook { __device__ __forceinline__ void operator()() const {} };
-template <int NQ, bool TL, class HOOK = VMixNoHook>
+template <int NQ, bool TL, class HOOK>
 __device__ __forceinline__ void vmix_col_fill(const DevSource &s, const VMixDesc &D, double lon, double lat, double *Kp,
-                                              int tid, unsigned quads = ~0u, HOOK &&hook = HOOK()) {
+                                              int tid, HOOK &&hook) {
   const double Kfb = (double)D.Kfb;
   double x, y;
   if (s.lon_mode == 1) lon = np_mod(lon + 180.0, 360.0) - 180.0;
@@ -540,21 +495,15 @@ __device__ __forceinline__ void vmix_col_fill(const DevSource &s, const VMixDesc
   // byte offsets of the four node records (blocks of the fast path are `small`: < 2^24 nodes, < 4 GiB; 24-bit multiplies)
   const unsigned recb = (unsigned)bb.rec * 4u;
   const unsigned r0 = __umul24((unsigned)ay.i0, (unsigned)nx), r1 = __umul24((unsigned)ay.i1, (unsigned)nx);
-#ifdef ODR_ABL_VMIX_UNIFORM   // what-if build (wrong values): every lane gathers node 0 -- what the spread of the gathers costs
-  const unsigned o00 = 0u * r0, o01 = 0u * r1, o10 = 0u * recb, o11 = 0u;
-#else
   const unsigned o00 = cov ? __umul24(r0 + (unsigned)ax.i0, recb) : 0u, o01 = cov ? __umul24(r0 + (unsigned)ax.i1, recb) : 0u;
   const unsigned o10 = cov ? __umul24(r1 + (unsigned)ax.i0, recb) : 0u, o11 = cov ? __umul24(r1 + (unsigned)ax.i1, recb) : 0u;
-#endif
   const float *kb = D.kb, *ka = TL ? D.ka : D.kb;
   // horizontal weights multiplied out once for the whole column (float64; the layer value is rounded to float32 like
   // the ReaderBlock's: same bits as (v*wy)*wx summed, but for a float64 round-off that reaches the float32 rounding
   // in ~1e-8 of the values)
   const double w00 = wy0 * wx0, w01 = wy0 * tx, w10 = ty * wx0, w11 = ty * tx;
-  if (!(quads & 1u)) hook();
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
-    if (!((quads >> q) & 1u)) continue;
     // both time levels requested before anything is consumed
     const F4 b00 = ld_off<F4>(kb, o00 + 16u * q), b01 = ld_off<F4>(kb, o01 + 16u * q);
     const F4 b10 = ld_off<F4>(kb, o10 + 16u * q), b11 = ld_off<F4>(kb, o11 + 16u * q);
@@ -565,10 +514,6 @@ __device__ __forceinline__ void vmix_col_fill(const DevSource &s, const VMixDesc
     }
     if (q == 0) hook();
     double v[4];
-#ifdef ODR_ABL_VMIX_FILLMATH   // what-if build (wrong values): the column's layer values without their float64 arithmetic
-    v[0] = (double)(b00.x + b11.x); v[1] = (double)(b00.y + b11.y); v[2] = (double)(b00.z + b11.z); v[3] = (double)(b00.w + b11.w);
-    if (TL) { v[0] += (double)a00.x; v[1] += (double)a01.y; v[2] += (double)a10.z; v[3] += (double)a11.w; }
-#else
     v[0] = (double)bilw(b00.x, b01.x, b10.x, b11.x, w00, w01, w10, w11);
     v[1] = (double)bilw(b00.y, b01.y, b10.y, b11.y, w00, w01, w10, w11);
     v[2] = (double)bilw(b00.z, b01.z, b10.z, b11.z, w00, w01, w10, w11);
@@ -582,7 +527,6 @@ __device__ __forceinline__ void vmix_col_fill(const DevSource &s, const VMixDesc
 #pragma unroll
       for (int j = 0; j < 4; ++j) v[j] = __dadd_rn(__dmul_rn(v[j], 1 - wgt), __dmul_rn(w[j], wgt));
     }
-#endif
 #pragma unroll
     for (int j = 0; j < 4; ++j) Kp[(4 * q + j) * BLOCK + tid] = (cov && isfinite(v[j])) ? v[j] : Kfb;
   }
@@ -603,30 +547,16 @@ __device__ __forceinline__ MixRng mix_rng_begin(const VMixArgs &A, int id) {
   R.key = mix_key(A.seed, A.step, id);
   R.q = make_uint4(0u, 0u, 0u, 0u);
   R.primed = false;
-#ifndef ODR_ABL_VMIX_NORNG
   if (A.rng_mode == 0) {
     R.q = mix_block(R.key, 0u);
     R.primed = true;
   }
-#endif
   return R;
-}
-// Quads on demand (k_vmix_col): `lz` names the quads vmix_col_fill has put into Kp (wave-uniform).  A sub-step that needs the
-// level terms of a level whose neighbours lie in a quad that was not gathered sets `missed`; the caller then gathers the whole
-// column and walks the particle again from its start (same draws: the stream is a function of element, step and sub-step) --
-// rare: the levels a particle reaches within a step are the ones around its own (C3: 0.07 % of the particles per step leave
-// their three-level window at all, none reaches the quad below 100 m).  Level terms are a pure function of the column: same bits.
-struct VMixLazy { unsigned loaded; bool missed; };
-__device__ __forceinline__ unsigned vmix_quads_of(int lo, int hi, int nzp) {   // quads holding levels lo..hi (clamped to the column)
-  lo = lo < 0 ? 0 : lo; hi = hi > nzp - 1 ? nzp - 1 : hi;
-  const unsigned a = (unsigned)lo >> 2, b = (unsigned)hi >> 2;
-  return ((2u << b) - 1u) & ~((1u << a) - 1u);
 }
 template <int NQ>
 __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, const double *Kp, const double *gsh, int tid,
                                                 const VMixArgs &A, long long i, long long n, int id, double z, int &moving,
-                                                float Zmin, float tv, int &sf_flags, const MixRng *pre = nullptr,
-                                                VMixLazy *lz = nullptr) {
+                                                float Zmin, float tv, int &sf_flags, const MixRng *pre) {
   constexpr int NL = 4 * NQ;
   const double dt = A.dt;
   const int mix_at_surface = A.mix_at_surface, rng_mode = A.rng_mode, sfl = A.sfl;
@@ -638,13 +568,7 @@ __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, con
   const double gd0 = s.vg_d[0], gi0 = s.vg_id[0], gd1 = s.vg_d[1], gi1 = s.vg_id[1], gd2 = s.vg_d[2], gi2 = s.vg_id[2];
   const double sgn = dt > 0 ? 1.0 : (dt < 0 ? -1.0 : 0.0);
   const double dt_mix = A.dt_mix_cfg * sgn;
-#ifdef ODR_ABL_VMIX_NOLOOP   // what-if build: no sub-steps, the window's level terms still formed (they flow into z below)
-  const int ntimes = 0;
-#elif defined(ODR_ABL_VMIX_NT)   // what-if build: fewer sub-steps
-  const int ntimes = ODR_ABL_VMIX_NT;
-#else
   const int ntimes = abs((int)(dt / dt_mix));
-#endif
   const double r = 1.0 / 3, ir = 1.0 / r;
   // w*dt_mix*moving: dt_mix is a NumPy float64 scalar (np.sign, oceandrift.py:416) -> float64 product under NumPy 2
   double wstep = __dmul_rn(__dmul_rn((double)tv, dt_mix), (double)moving);
@@ -654,7 +578,6 @@ __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, con
   if (pre) { u4 = pre->q; primed = pre->primed; }
   // -dK/dz * dt_mix and sqrt(K |dt_mix| 2 / r) of one level (oceandrift.py:501-502,527-528)
   auto level_terms = [&](int zl, double &dk_dt, double &sg) {
-    if (lz && (vmix_quads_of(zl - 1, zl + 1, nzp) & ~lz->loaded)) lz->missed = true;   // (the values formed below are dropped)
     const double Kz = Kp[zl * BLOCK + tid];
     double gK;  // np.gradient(Kprofiles, mixing_z, axis=0)[zl]
     if (zl == 0) gK = div_cr(Kp[BLOCK + tid] - Kz, gd0, gi0);
@@ -687,9 +610,6 @@ __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, con
     c_dk[q] = 0; c_sg[q] = 0;
     if (zl >= 0 && zl < nzp) level_terms(zl, c_dk[q], c_sg[q]);
   }
-#ifdef ODR_ABL_VMIX_NOLOOP
-  z += 1e-30 * (c_dk[0] + c_dk[1] + c_dk[2] + c_sg[0] + c_sg[1] + c_sg[2]);
-#endif
   // The level of a sub-step is the number of boundaries below d (odd ones count when d >= zm, even ones when d > zm).
   // Inside the cached window only the window's own four boundaries decide -- lv0 - 2 ... lv0 + 1, per lane, with the
   // ">=" of the odd ones folded into the value (d >= b  <=>  d > the double just below b; b > 0) -- four compares
@@ -708,16 +628,8 @@ __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, con
   // the sub-steps in groups of five = one Philox block: inside the unrolled group the word a sub-step takes from the block is
   // known at compile time (a run-time `it % 5` costs a chain of selects and the fifth word's assembly in every sub-step)
   for (int it0 = 0; it0 < ntimes; it0 += 5) {
-#ifdef ODR_ABL_VMIX_NORNG   // what-if build: no generator (wrong values)
-  u4 = make_uint4(st.id * 2654435761u + (unsigned)it0, st.id ^ 0x9E3779B9u, st.id * 40503u, st.id + (unsigned)it0);
-#else
   if (rng_mode == 0 && !(primed && it0 == 0)) u4 = mix_block(st, (unsigned)it0 / 5u);
-#endif
-#ifdef ODR_VMIX_NO_UNROLL   // A/B build: the word selected at run time, as in rounds 1-3
-#pragma unroll 1
-#else
 #pragma unroll
-#endif
   for (int k5 = 0; k5 < 5; ++k5) {
     const int it = it0 + k5;
     if (it >= ntimes) break;
@@ -907,21 +819,13 @@ __device__ __forceinline__ void advect_grid_body(const DevSource &s, const DevBl
   // the full-step stage may use (and refresh) the kept records when its time bracket is that of the half-step stages
   const bool keep_f = tf.b == th.b && tf.a == th.a;
   GeodStart o0 = geod_start(lat, lon);
-#ifndef ODR_FULL_GEODESIC
   // PARK: the series coefficients wait in LDS between the moves (geod_park); the start point is rebuilt where it is used
   lds_f64 *slot = (lds_f64 *)park;
   if constexpr (PARK) { geod_park(o0, slot); if (SM == 1 && SCHEME == 2) slot[14 * BLOCK] = (double)f; }
   auto O = [&]() { if constexpr (PARK) return geod_unpark(slot[12 * BLOCK], slot[13 * BLOCK], slot); else return o0; };
-#else
-  auto O = [&]() { return o0; };
-#endif
 #define ODR_O O()
-#ifndef ODR_FULL_GEODESIC
 #define ODR_STAGE_POS(U_, V_) do { if constexpr (PARK && SM == 1) stage_pos_parked(slot, U_, V_, dtf, lon2, lat2); \
                                    else stage_pos<SM>(ODR_O, U_, V_, dtf, lon2, lat2); } while (0)
-#else
-#define ODR_STAGE_POS(U_, V_) stage_pos<SM>(ODR_O, U_, V_, dtf, lon2, lat2)
-#endif
   if (SCHEME == 0) {
     fu = __fmul_rn(f, u1);
     fv = __fmul_rn(f, v1);
@@ -963,9 +867,7 @@ __device__ __forceinline__ void advect_grid_body(const DevSource &s, const DevBl
       if (NOISE) add_current_noise(N, 3, i, n, id, u4, v4);
       ODR_PT_USE(u4); ODR_PT_USE(v4); ODR_PT(7);
       float fl = f;
-#ifndef ODR_FULL_GEODESIC
       if constexpr (PARK && SM == 1) fl = (float)slot[14 * BLOCK];   // (parked with the coefficients: one register less through the stages)
-#endif
       fu = __fmul_rn(rk4_mix(u1, u2, u3, u4), fl);
       fv = __fmul_rn(rk4_mix(v1, v2, v3, v4), fl);
     }
@@ -1053,22 +955,9 @@ struct StepDesc {
 };
 
 // (The LDS field tile is a kernel of its own since round 4: k_step_tile, odr_tile.hip.h.)
-// MIXQ > 0: OceanDrift.vertical_mixing (+ vertical_advection) of the same step runs in this launch as well (the body of
-// k_vmix_col<MIXQ, MIXTL>): the K column is gathered at the sample position while the particle is in registers, the
-// random walk follows the horizontal move; z, moving, depth, ssh and the sample position are not written and read
-// again, one launch and one pass over the particle state less.  Same arithmetic, same bits as the two launches.
-struct StepMix {
-  VMixDesc D;
-  VMixArgs A;
-  int vadv, w_slot;   // vertical advection: -1 none | 0 below the surface | 1 including it; slot of W in the group or -1
-};
 // lat / lon and curvilinear readers, Runge-Kutta schemes: geodesic coefficients parked in LDS, 5 waves per SIMD (geod_park)
 #ifndef ODR_PARK_WAVES
-#ifdef ODR_NO_KEEP
-#define ODR_PARK_WAVES 5
-#else
 #define ODR_PARK_WAVES 4   // with the kept (u,v) records of the footprint (UVKeep: 35 registers): 126 registers; 4 and 5 waves per SIMD ran alike before (profiles/r03_ab_variants.txt)
-#endif
 #endif
 // Round 5: the lat / lon 3-D instantiations with the FAST stage arithmetic fit 96 registers without scratch memory -- kept values
 // combined over the vertical bracket (16 registers instead of 32), slots B / C / D sampled before slot A, the start point and the
@@ -1078,27 +967,18 @@ struct StepMix {
 #ifndef ODR_PARK_WAVES_FAST3D
 #define ODR_PARK_WAVES_FAST3D 5
 #endif
-#if defined(ODR_NO_KEEP)
-#define ODR_PARK_WAVES_OF(PROJ, IS3D, SM) ODR_PARK_WAVES
-#else
 #define ODR_PARK_WAVES_OF(PROJ, IS3D, SM) (((PROJ) == PROJ_LATLONG && (IS3D) && (SM) == 1) ? ODR_PARK_WAVES_FAST3D : ODR_PARK_WAVES)
-#endif
-#if defined(ODR_FULL_GEODESIC) || defined(ODR_NO_PARK)
-#define ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) false
-#else
-#define ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) ((SCHEME) > 0 && (MIXQ) == 0 && ((PROJ) == PROJ_LATLONG || (PROJ) == PROJ_CURVILINEAR))
-#endif
+#define ODR_STEP_PARKS(SCHEME, PROJ) ((SCHEME) > 0 && ((PROJ) == PROJ_LATLONG || (PROJ) == PROJ_CURVILINEAR))
 // LY: the slot layout of the group and of the bookkeeping below (odr_field.hip.h LayoutRT / LayoutC3)
-template <int SCHEME, int PROJ, bool IS3D, bool NOISE, int MIXQ = 0, bool MIXTL = false, int SM = 0, class LY = LayoutRT>
-__global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) ? ODR_PARK_WAVES_OF(PROJ, IS3D, SM) : ((MIXQ > 0 && ODR_STEP_WAVES(PROJ) < ODR_MIX_WAVES) ? ODR_MIX_WAVES : ODR_STEP_WAVES(PROJ))) void k_step_grid(const DevWorld *__restrict__ W, PView p, EnvGroupDesc G,
+template <int SCHEME, int PROJ, bool IS3D, bool NOISE, int SM = 0, class LY = LayoutRT>
+__global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ) ? ODR_PARK_WAVES_OF(PROJ, IS3D, SM) : ODR_STEP_WAVES(PROJ)) void k_step_grid(const DevWorld *__restrict__ W, PView p, EnvGroupDesc G,
                                                      StepDesc S, double dt, float factor, UVTime th, UVTime tf,
-                                                     unsigned long long *n_hit, StageNoise N,
-                                                     StepMix M = StepMix()) {
+                                                     unsigned long long *n_hit, StageNoise N) {
   long long i = pid();
   bool hit = false;
   ODR_PT_DECL;
   ODR_PT(0);
-  constexpr bool PARK = ODR_STEP_PARKS(SCHEME, PROJ, MIXQ);
+  constexpr bool PARK = ODR_STEP_PARKS(SCHEME, PROJ);
   __shared__ double s_park[PARK ? GEOD_PARK * BLOCK : 1];
   __shared__ double s_zt[IS3D ? 3 * ZT_STRIDE : 1];   // interp1d tables of the reader's z grid (zinterp)
   const double *zt = nullptr;
@@ -1106,53 +986,29 @@ __global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) ? ODR_PAR
   // life between its entry and the arrival of lon / lat / z -- kernel arguments -> source fields -> table loads -> barrier ->
   // state loads, five dependent round trips; the state loads need the kernel arguments only)
   double lon_e = 0, lat_e = 0, z_e = 0;
-#ifndef ODR_NO_EARLY_STATE
   if (i < p.n) { lon_e = p.lon[i]; lat_e = p.lat[i]; z_e = p.z[i]; }
-#endif
   if (IS3D) { zt_stage(W->src[G.sid], s_zt); zt = s_zt; }
-  double *Kp = nullptr, *gsh = nullptr;
-  if (MIXQ > 0) {
-    extern __shared__ __attribute__((aligned(16))) char mix_mem[];
-    constexpr int NL = 4 * (MIXQ > 0 ? MIXQ : 1);
-    Kp = (double *)mix_mem;                  // [NL][BLOCK]
-    gsh = Kp + (size_t)NL * BLOCK;           // [4][NL]
-    const DevSource &sk = W->src[M.D.sid];
-    if ((int)threadIdx.x < M.D.nzp) {
-      const int t_ = threadIdx.x;
-      gsh[t_] = sk.vg_a[t_]; gsh[NL + t_] = sk.vg_b[t_]; gsh[2 * NL + t_] = sk.vg_c[t_]; gsh[3 * NL + t_] = sk.zmid[t_];
-    }
-    __syncthreads();
-  }
   // this lane's share of the movers' tests (S.red_on): neutral unless it holds an element that stays active
   unsigned r_bits = 0;   // 1 D > 0, 2 D == 0, 4 Stokes sum > 0, 8 == 0, 16 at the surface, 32 wind drift factor > 0, 64 == 0, 128 wind speed > 0, 256 == 0
   if (i < p.n) {
-#ifndef ODR_NO_EARLY_STATE
     double lon = lon_e, lat = lat_e;
     const double z = z_e;
-#else
-    double lon = p.lon[i], lat = p.lat[i];
-    const double z = p.z[i];
-#endif
     // everything the bookkeeping below reads of this particle, requested together with the position: each of these
     // loads after the environment stores is a memory round trip of its own (float stores may alias float loads)
-    // ODR_STATE_LATE (the 3-D lat / lon instantiations of round 5): moving, status, age, drift factor and ssh are requested BEHIND
+    // STATE_LATE (the 3-D lat / lon instantiations of round 5): moving, status, age, drift factor and ssh are requested BEHIND
     // the sample instead of with the position -- one more dependent round trip, five registers less through the main-loop sample,
     // which with the rest of round 5's register work leaves the kernel at <= 96 registers = 5 waves per SIMD
-#ifdef ODR_STATE_EARLY
-    constexpr bool STATE_LATE = false;
-#else
-    constexpr bool STATE_LATE = ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) && IS3D;
-#endif
+    constexpr bool STATE_LATE = ODR_STEP_PARKS(SCHEME, PROJ) && IS3D;
     int moving = 0, st = 0;
     float age0 = 0.f, cdf0 = 0.f, ssh0 = 0.f;
     auto load_state = [&]() {
       moving = p.moving[i];
       st = p.status[i];
       age0 = p.age[i]; cdf0 = p.cdf[i];
-      ssh0 = (S.seafloor || MIXQ > 0) && p.env[VAR_SSH] ? p.env[VAR_SSH][i] : 0.f;
+      ssh0 = S.seafloor && p.env[VAR_SSH] ? p.env[VAR_SSH][i] : 0.f;
     };
     if constexpr (!STATE_LATE) load_state();
-    constexpr bool RED = !IS3D && MIXQ == 0;      // (the movers' tests, below)
+    constexpr bool RED = !IS3D;      // (the movers' tests, below)
     const float wdf0 = (RED && S.red_on && S.red_xw > -2) ? p.wdf[i] : 0.f;
     ODR_PT_USE(lon); ODR_PT_USE(lat); ODR_PT_USE(z); ODR_PT(1);
     float out[MAXG];
@@ -1164,9 +1020,8 @@ __global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) ? ODR_PAR
     // (DevWorld::f32pos -- the float32 element arrays of a run's first get_environment -- never reaches this launch: the host
     // takes the separate launches then, odr_step.hip; three more values live across the sample cost this kernel 0.61 -> 0.79 ms)
     // polar stereographic readers under a Runge-Kutta scheme: sines / cosines of the element's position once for the sample's
-    // projection AND the stage positions (ODR_NO_SHARED_START: formed twice, as before round 6)
+    // projection AND the stage positions
     ProjStart ps0;
-#ifndef ODR_NO_SHARED_START
     if constexpr (PROJ == PROJ_STERE_POLAR && SCHEME != 0) {
       const DevSource &s0 = W->src[G.sid];
       double lw = lon;
@@ -1174,23 +1029,17 @@ __global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) ? ODR_PAR
       else if (s0.lon_mode == 2) lw = np_mod(lw, 360.0);
       ps0 = proj_start(s0.proj, lw, lat);
     }
-#endif
     env_group_fast<PROJ, true, IS3D, LY>(*W, G, lon, lat, z, out, zt, zb_env, &X ODR_PT_ARG, 0, ps0);
     UVKeep<IS3D> K = uv_keep_from_sm<IS3D, SM, LY>(G, X, th, zb_env, W->src[G.sid].nz, true);   // (FAST, 3-D: combined over the bracket's levels)
     if constexpr (STATE_LATE) load_state();
     ODR_PT_USE(out[0]); ODR_PT_USE(out[1]); ODR_PT_USE(out[2]); ODR_PT_USE(out[3]); ODR_PT_USE(out[4]); ODR_PT(2);
-    const int id = (NOISE || MIXQ > 0) ? p.id[i] : 0;
-    if (MIXQ > 0) vmix_col_fill<(MIXQ > 0 ? MIXQ : 1), MIXTL>(W->src[M.D.sid], M.D, lon, lat, Kp, threadIdx.x);
+    const int id = NOISE ? p.id[i] : 0;
     if (NOISE && S.main_noise) add_current_noise(N, 0, i, p.n, id, out[0], out[1]);
-#ifndef ODR_ABLATE_STORES   // what-if build (tools/ab_bench.sh)
 #pragma unroll
     for (int k = 0; k < MAXG; ++k)
       if (k < LY::nv_of(G)) G.out_ptr[k][i] = out[k];
-    if (MIXQ == 0) {   // the sample position is what odr_vmix gathers its profiles at: not needed when the mixing is in here
-      p.slon[i] = lon;
-      p.slat[i] = lat;
-    }
-#endif
+    p.slon[i] = lon;   // the sample position is what odr_vmix gathers its profiles at
+    p.slat[i] = lat;
     // the movers' tests: the five values they need, read back from the arrays (just stored above, or sampled by the launch
     // before this one) -- requested here, used at the very end of the kernel.  Picking them out of the group's registers
     // by run-time slot cost 70 instructions of select chains in a kernel that is bound by instruction issue (C4: +258
@@ -1246,7 +1095,7 @@ __global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) ? ODR_PAR
         const float dep = S.depth_slot == 2 ? out[2] : (S.depth_slot == 3 ? out[3] : p.env[VAR_DEPTH][i]);
         floorz = -__fadd_rn(dep, S.ssh_slot >= 0 ? pick_slot(out, S.ssh_slot) : ssh0);
       }
-      if (zz < (double)floorz) { zz = (double)floorz; if (MIXQ == 0) p.z[i] = zz; }
+      if (zz < (double)floorz) { zz = (double)floorz; p.z[i] = zz; }
     }
     if (S.age_dt != 0.0f) {  // k_age
       const float a = __fadd_rn(age0, S.age_dt);
@@ -1259,9 +1108,7 @@ __global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) ? ODR_PAR
     // deactivated (now or earlier, not yet compacted): the reference removes it before update() -- it does not move
     const bool skip = st != 0;
     if constexpr (IS3D && SM == 1) { if (zz != z) K.valid = false; }   // the sea floor lifted the element: another bracket than the kept values'
-#ifndef ODR_ABLATE_STORES
     if (S.store_previous) { p.plon[i] = lon; p.plat[i] = lat; }
-#endif
     ODR_PT(3);
     if (!skip) {
       const DevSource &s = W->src[G.sid];
@@ -1270,27 +1117,6 @@ __global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) ? ODR_PAR
                                                         W->fallback[VAR_U], W->fallback[VAR_V], N, i, p.n, id, K, zb_env, IS3D && zz == z, PARK ? s_park + threadIdx.x : nullptr ODR_PT_ARG, ps0);
     }
     ODR_PT_USE(lon); ODR_PT_USE(lat); ODR_PT(8);
-    if (MIXQ > 0) {   // vertical_mixing + vertical_advection (oceandrift.py:397-571, :315-350) after the horizontal move
-      double zn = zz;
-      if (!skip) {
-        const float dep = S.depth_slot == 2 ? out[2] : (S.depth_slot == 3 ? out[3] : p.env[VAR_DEPTH][i]);
-        const float Zmin = __fmul_rn(-1.f, __fadd_rn(dep, S.ssh_slot >= 0 ? pick_slot(out, S.ssh_slot) : ssh0));  // float32 (:408)
-        int sf_flags = 0;
-        zn = vmix_col_walk<(MIXQ > 0 ? MIXQ : 1)>(W->src[M.D.sid], M.D.nzp, Kp, gsh, threadIdx.x, M.A, i, p.n, id, zz, moving, Zmin,
-                                                  p.tv[i], sf_flags);
-        if (sf_flags & 1) {   // deactivate_elements(reason='seafloor')
-          if (st == 0) p.status[i] = M.A.sfl >> 8;
-          p.moving[i] = 0;
-        }
-        if (sf_flags & 2) { lon = p.plon[i]; lat = p.plat[i]; }
-        if (M.vadv >= 0 && (M.vadv ? zn <= 0 : zn < 0)) {
-          const float wv = M.w_slot >= 0 ? pick_slot(out, M.w_slot) : p.env[VAR_W][i];
-          const double zq = __dadd_rn(zn, __dmul_rn(__dmul_rn((double)moving, (double)wv), dt));
-          zn = zq < 0 ? zq : 0.0;
-        }
-      }
-      p.z[i] = zn;
-    }
     // (2-D readers only: a 3-D run mixes vertically between this launch and the movers, which changes z and voids the tests;
     // the 3-D instantiations carry no code for it -- k_step_grid<RK4, lat/lon, 3-D> stays at 126 registers)
     if (RED && S.red_on && !skip) {   // k_reduce<false> for this element, as signs: every test is `maximum == 0`
@@ -1332,7 +1158,7 @@ __global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) ? ODR_PAR
     unsigned long long b = __ballot(hit);
     if ((threadIdx.x & 63) == 0 && b) atomicAdd(n_hit, (unsigned long long)__popcll(b));
   }
-  if (!IS3D && MIXQ == 0 && S.red_on) {
+  if (!IS3D && S.red_on) {
     // one record of six doubles per WAVE, written by its lanes 0..5 in one store; k_red_finish folds the records into
     // red[].  A slot holds +1 (some element > 0), 0 (none > 0, some == 0) or -inf: what `maximum == 0` needs, from nine
     // wave votes -- not the maximum itself (the host marks the reduction `partial`; the wind speed slot nobody tests stays
@@ -1351,7 +1177,7 @@ __global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ, MIXQ) ? ODR_PAR
       S.red[((size_t)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6)) * 6 + lane] = v;
     }
   }
-  if (MIXQ == 0 && S.wcount) {
+  if (S.wcount) {
     // (the status read back at the very end: carried through the kernel it would be one more register at its peak)
     int s2 = 1;
     long long i3 = i;
@@ -2042,14 +1868,6 @@ __global__ __launch_bounds__(BLOCK) void k_vmix(const DevWorld *__restrict__ W, 
 #ifndef ODR_VMIX_WAVES
 #define ODR_VMIX_WAVES 6   // 80 registers, no scratch: six workgroups (24.6 KB of LDS each) per CU; unconstrained the allocator took 102 (4 waves)
 #endif
-// one particle of k_vmix_col: column into the thread's LDS slots, sub-steps, stores.
-// LAZY: gather only the quads of the column this WAVE needs -- the union of what its particles' three-level windows (the levels
-// lv0 - 2 .. lv0 + 2 their terms are formed from, vmix_col_walk) touch.  The texture addresser's time goes with the number of
-// gather instructions (profiles/r05_ab_variants.txt section 1: 0.34 instead of 0.41 ms when every lane gathers the same node,
-// 0.26 ms for the launch without its sub-steps), and a particle at 30 m never reads K at 300 m.  Returns true -- nothing stored
-// -- when a sub-step needed a quad that was not gathered: the caller runs the particle again with the whole column (a second
-// copy of this function behind a wave-uniform branch: everything is read again from memory, so nothing of the first pass stays
-// in registers for it; a retry loop around fill + walk spilled 548 B per lane).
 // what the mixing of one particle reads of it -- requested by the kernel in ONE round trip together with its LDS tables
 // (round 5: the tables' loads stood in front of a barrier in front of these, and the ID's load behind a branch in front of the
 // first Philox block in front of the column gathers: three dependent round trips before the first gather was issued)
@@ -2061,44 +1879,23 @@ __device__ __forceinline__ VMixState vmix_load_state(const PView &p, long long i
   S.dep = p.env[VAR_DEPTH][i]; S.ssh = p.env[VAR_SSH][i]; S.tv = p.tv[i];
   return S;
 }
-template <int NQ, bool TL, bool LAZY>
-__device__ __forceinline__ bool vmix_col_particle_pass(const DevSource &s, const PView &p, const VMixDesc &D, const VMixArgs &A,
-                                                       int vadv, long long i, double *Kp, const double *gsh, int tid, const VMixState &S) {
+// one particle of k_vmix_col: column into the thread's LDS slots, sub-steps, stores
+template <int NQ, bool TL>
+__device__ __forceinline__ void vmix_col_particle(const DevSource &s, const PView &p, const VMixDesc &D, const VMixArgs &A,
+                                                  int vadv, long long i, double *Kp, const double *gsh, int tid, const VMixState &S) {
   const int nzp = D.nzp, sfl = A.sfl;
   const double dt = A.dt;
   const double slon = S.slon, slat = S.slat, z0 = S.z0;
   int moving = S.moving;
   const float dep0 = S.dep, ssh0 = S.ssh, tv0 = S.tv;
   const int id0 = S.id;
-  VMixLazy lz;
-  lz.loaded = ~0u; lz.missed = false;
-  if (LAZY) {
-    int zs = 0;
-    const double d0 = -z0;
-#pragma unroll
-    for (int k = 0; k < 4 * NQ - 1; ++k) zs += (k < nzp - 1 && ((k & 1) ? d0 >= s.zmid[k] : d0 > s.zmid[k])) ? 1 : 0;
-    int lv0 = zs < 1 ? 1 : (zs > nzp - 2 ? nzp - 2 : zs);
-    if (nzp < 3) lv0 = 1;
-    const unsigned mine = vmix_quads_of(lv0 - 2, lv0 + 2, nzp);
-    unsigned w = 0;
-#pragma unroll
-    for (int q = 0; q < NQ; ++q) w |= __ballot((mine >> q) & 1u) ? (1u << q) : 0u;
-    lz.loaded = w;
-  }
   MixRng R0;
   R0.key = mix_key(A.seed, A.step, id0); R0.q = make_uint4(0u, 0u, 0u, 0u); R0.primed = false;
-#ifdef ODR_VMIX_LATE_RNG
-  vmix_col_fill<NQ, TL>(s, D, slon, slat, Kp, tid, lz.loaded);
-  const MixRng *pre = nullptr;
-#else
   // the stream's first block behind the first gathers of the column: its arithmetic runs while they are in flight
-  vmix_col_fill<NQ, TL>(s, D, slon, slat, Kp, tid, lz.loaded, [&]() { R0 = mix_rng_begin(A, id0); });
-  const MixRng *pre = &R0;
-#endif
+  vmix_col_fill<NQ, TL>(s, D, slon, slat, Kp, tid, [&]() { R0 = mix_rng_begin(A, id0); });
   int sf_flags = 0;
   const float Zmin = __fmul_rn(-1.f, __fadd_rn(dep0, ssh0));  // float32 (:408)
-  double z = vmix_col_walk<NQ>(s, nzp, Kp, gsh, tid, A, i, p.n, id0, z0, moving, Zmin, tv0, sf_flags, pre, LAZY ? &lz : nullptr);
-  if (LAZY && lz.missed) return true;
+  double z = vmix_col_walk<NQ>(s, nzp, Kp, gsh, tid, A, i, p.n, id0, z0, moving, Zmin, tv0, sf_flags, &R0);
   if (sf_flags & 1) {   // deactivate_elements(reason='seafloor') (basemodel/__init__.py:1774-1795)
     if (p.status[i] == 0) p.status[i] = sfl >> 8;
     p.moving[i] = 0;
@@ -2112,26 +1909,6 @@ __device__ __forceinline__ bool vmix_col_particle_pass(const DevSource &s, const
     z = zz < 0 ? zz : 0.0;
   }
   p.z[i] = z;
-  return false;
-}
-template <int NQ, bool TL>
-__device__ __forceinline__ void vmix_col_particle(const DevSource &s, const PView &p, const VMixDesc &D, const VMixArgs &A,
-                                                  int vadv, long long i, double *Kp, const double *gsh, int tid, const VMixState &S) {
-#if !defined(ODR_VMIX_LAZY_QUADS)   // the whole column for every particle (the quads on demand measured slower, profiles/r05_ab_variants.txt)
-  vmix_col_particle_pass<NQ, TL, false>(s, p, D, A, vadv, i, Kp, gsh, tid, S);
-#else
-  if constexpr (NQ == 1) vmix_col_particle_pass<NQ, TL, false>(s, p, D, A, vadv, i, Kp, gsh, tid, S);
-  else {
-    const bool again = vmix_col_particle_pass<NQ, TL, true>(s, p, D, A, vadv, i, Kp, gsh, tid, S);
-    if (__ballot(again)) {
-      // (an opaque copy of the index: addresses formed from `i` for the first pass would otherwise be kept alive -- in scratch
-      // memory, 36 B per lane -- for this one)
-      long long i2 = i;
-      asm volatile("" : "+v"(i2));
-      if (again) vmix_col_particle_pass<NQ, TL, false>(s, p, D, A, vadv, i2, Kp, gsh, tid, vmix_load_state(p, i2));
-    }
-  }
-#endif
 }
 template <int NQ, bool TL>
 __global__ __launch_bounds__(BLOCK, ODR_VMIX_WAVES) void k_vmix_col(const DevWorld *__restrict__ W, PView p, VMixDesc D,
@@ -3075,9 +2852,6 @@ __device__ __forceinline__ void leeway_body(const PView &p, long long i, double 
                                            p.aux[AUX_DW_OFFSET][i]), __fdiv_rn(dwe, 2.0f)), (float).01);
   float cw = __fmul_rn(__fadd_rn(__fadd_rn(__fmul_rn(__fadd_rn(cws, __fdiv_rn(cwe, 20.0f)), windspeed),
                                            p.aux[AUX_CW_OFFSET][i]), __fdiv_rn(cwe, 2.0f)), (float).01);
-#ifdef ODR_ABL_LW_NOTRIG
-  float sinth = xw / windspeed, costh = yw / windspeed;
-#else
   // np.sin / np.cos of the float32 winddir = float32(theta), theta = arctan2(x_wind, y_wind): sin / cos theta are x/h, y/h and
   // the float32 rounding moves the angle by delta = winddir - theta, |delta| < 2e-7:
   //   sin(theta + delta) = sin theta (1 - delta^2/2) + cos theta delta   (as azimuth_sincos_f32; delta^3/6 < 2e-21)
@@ -3099,19 +2873,13 @@ __device__ __forceinline__ void leeway_body(const PView &p, long long i, double 
       costh = (float)cos((double)winddir);
     }
   }
-#endif
   float yl = __fadd_rn(__fmul_rn(dw, costh), __fmul_rn(cw, sinth));
   float xl = __fadd_rn(__fmul_rn(-dw, sinth), __fmul_rn(cw, costh));
   if (p.aux[AUX_CAPSIZED][i] == 1.0f) { xl = __fmul_rn(xl, capsize_fraction); yl = __fmul_rn(yl, capsize_fraction); }
   MoveChain mc;
   mc.next = false;
   move_f32_chain(mc, lon, lat, -xl, yl, moving, dt);              // :472
-#ifndef ODR_ABL_LW_NOMOVE2
   move_f32_chain(mc, lon, lat, u, v, moving, dt);                 // :475-476 (start-point coefficients from the first move's)
-#endif
-#ifdef ODR_ABL_LW_NOJIBE
-  return;
-#endif
   // jibing (:478-487): rate = -log(1-p)/3600, probability per step 1-exp(-rate*|dt|), float32
   float jp = p.aux[AUX_JIBE_P][i];
   const double q1 = (double)__fsub_rn(1.0f, jp);                 // np.log of a float32: the float64 logarithm rounded to float32
@@ -3178,7 +2946,6 @@ __global__ __launch_bounds__(BLOCK, ODR_WAVES(PROJ)) void k_step_leeway(const De
     float xw = pick_slot(out, S.wind_slot), yw = pick_slot(out, S.wind_slot + 1);
     float u = pick_slot(out, S.uv_slot), v = pick_slot(out, S.uv_slot + 1);
     // environment.py:869-891: env[x] += N(0, std) (float32 array += float64 draws), first the current, then the wind
-#ifndef ODR_ABL_LW_NONOISE   // (what-if builds: tools/vbuild_many.py, profiles/r06_ab_variants.txt)
     if (S.std_current > 0) {
       const double2 g = rng_normal2(rng_block(S.seed, id, S.step, RNG_OFF_NOISE + 4ull * (unsigned)VAR_U));
       add_f32_f64(u, v, g.x * S.std_current, g.y * S.std_current);
@@ -3187,7 +2954,6 @@ __global__ __launch_bounds__(BLOCK, ODR_WAVES(PROJ)) void k_step_leeway(const De
       const double2 g = rng_normal2(rng_block(S.seed, id, S.step, RNG_OFF_NOISE + 4ull * (unsigned)VAR_XWIND));
       add_f32_f64(xw, yw, g.x * S.std_wind, g.y * S.std_wind);
     }
-#endif
 #pragma unroll
     for (int k = 0; k < MAXG; ++k) {
       if (k >= G.nv) break;

@@ -90,66 +90,10 @@ int odr_advect(odr_ctx *c, odr_particles *p, int scheme, double t, double dt, do
 // one launch (k_step_grid) when the current comes from one gridded reader; otherwise exactly the
 // four separate entry points, in that order.  Results are bit-identical either way
 // (tests/test_gpu_parity.py::test_fused_step_equals_separate_calls).
-// extras->vmix when the mixing cannot run inside the step launch: the two calls in sequence
+// extras->vmix: the mixing launch right after the step
 static int mix_after(odr_ctx *c, odr_particles *p, double t, double dt, const odr_step_extras *ex) {
   c->fuse_vadv = ex->vmix_vadv;
   return odr_vmix(c, p, t, dt, ex->vmix_dt_mix, ex->vmix_at_surface, ODR_RNG_DEVICE, nullptr, ex->vmix_step);
-}
-static bool s_is_latlong_3d(const odr_ctx *c, int sid) {
-  const DevSource &s = c->hw.src[sid];
-  return s.proj.kind == PROJ_LATLONG && s.nz > 1 && s.slot[s.level_slot[0]].var_nz[VAR_U] > 1;
-}
-
-// ---- lanes: the step kernel (gathers: bound by memory latency, VALU about half busy) and the mixing kernel (bound by
-// VALU issue) of DIFFERENT particles have nothing to wait for in each other.  The particle range is cut into `lanes`
-// contiguous windows, each on a stream of its own: step(l) -> mix(l) in order on lane l, and step(l + 1) starts when
-// step(l) has drained, so that mix(l) and step(l + 1) are resident together and fill each other's idle issue slots.
-// Results are those of the single launch (kernels are per-particle; the RNG is keyed by element ID).
-static int lane_count(odr_ctx *c, const odr_particles *p, bool want_mix, bool noise_on) {
-  if (!want_mix || noise_on || c->oil_owner == p) return 1;
-  const char *e = getenv("ODR_LANES");
-  int lanes = e ? atoi(e) : 1;
-  if (lanes > ODR_MAX_LANES) lanes = ODR_MAX_LANES;
-  const char *m = getenv("ODR_LANES_MIN_N");
-  const long long min_n = m ? atoll(m) : 2000000;
-  if (p->n < min_n || p->n / (lanes > 0 ? lanes : 1) < 4 * BLOCK) return 1;
-  return lanes;
-}
-
-static int step_in_lanes(odr_ctx *c, odr_particles *p, int lanes, const EnvGroupDesc &G, const StepDesc &S, int scheme,
-                         double t, double dt, double factor, const StageNoise &N, const odr_step_extras *ex) {
-  if (!c->lanes_ready) {
-    for (int l = 0; l < ODR_MAX_LANES; ++l) {
-      HIPCHK(hipStreamCreateWithFlags(&c->lane_stream[l], hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&c->lane_step[l], hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&c->lane_done[l], hipEventDisableTiming));
-    }
-    HIPCHK(hipEventCreateWithFlags(&c->lane_fork, hipEventDisableTiming));
-    c->lanes_ready = 1;
-  }
-  const long long n = p->n;
-  const hipStream_t main_stream = c->stream;
-  long long per = (n / lanes + BLOCK - 1) / BLOCK * BLOCK;
-  HIPCHK(hipEventRecord(c->lane_fork, main_stream));
-  int rc = 0, used = 0;
-  for (int l = 0; l < lanes && !rc; ++l) {
-    const long long first = (long long)l * per, count = l == lanes - 1 ? n - first : std::min(per, n - first);
-    if (count <= 0) break;
-    hipStream_t s = c->lane_stream[l];
-    HIPCHK(hipStreamWaitEvent(s, c->lane_fork, 0));
-    if (l > 0) HIPCHK(hipStreamWaitEvent(s, c->lane_step[l - 1], 0));
-    p->win = first; p->n = count; c->stream = s;
-    step_dispatch<false>(c, p, G, S, scheme, t, dt, factor, N);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipEventRecord(c->lane_step[l], s);
-    if (e == hipSuccess) rc = mix_after(c, p, t, dt, ex);
-    if (e == hipSuccess && !rc) e = hipEventRecord(c->lane_done[l], s);
-    p->win = 0; p->n = n; c->stream = main_stream;
-    if (e != hipSuccess) return fail(ODR_ERR_HIP, "lane launch: %s", hipGetErrorString(e));
-    used = l + 1;
-  }
-  for (int l = 0; l < used; ++l) HIPCHK(hipStreamWaitEvent(main_stream, c->lane_done[l], 0));
-  return rc;
 }
 
 int odr_env_coast_advect(odr_ctx *c, odr_particles *p, int nvars, const int32_t *var_ids, double t,
@@ -275,37 +219,6 @@ int odr_env_coast_advect(odr_ctx *c, odr_particles *p, int nvars, const int32_t 
   S.main_noise = main_noise ? 1 : 0;
   S.ssh_slot = -1;
   for (int k = 0; k < G.nv; ++k) if (G.var[k] == VAR_SSH) S.ssh_slot = k;
-  // vertical mixing inside the launch: K from the reader of the current (lon/lat, 3-D, <= 16 levels), device RNG
-  StepMix M;
-  memset(&M, 0, sizeof M);
-  bool mix_fused = false;
-  // Measured on C3 (profiles/r02_ab_variants.txt): the merged kernel needs 129 VGPRs (3 waves per SIMD instead of 4) and is
-  // SLOWER than the two launches (1.88 vs 1.75 ms per step; held at 128 VGPRs: 2.48 ms) -- both kernels are bound by
-  // instruction issue, there is no idle time for the merger to fill.  It stays behind ODR_FUSED_MIX=1 with its
-  // bit-identity test (tests/test_gpu_fused_step.py); by default extras->vmix makes the two launches back to back.
-  if (want_mix && !N.on && getenv("ODR_FUSED_MIX") && !getenv("ODR_NO_FUSED_MIX") && s_is_latlong_3d(c, G.sid) && c->oil_owner != p &&
-      build_vmix_desc(c, t, M.D) && M.D.sid == G.sid && M.D.nzp <= 16) {
-    if ((rc = ensure_env(c, p, VAR_SSH))) return rc;
-    M.A.dt = dt; M.A.dt_mix_cfg = extras->vmix_dt_mix; M.A.mix_at_surface = extras->vmix_at_surface;
-    M.A.rng_mode = ODR_RNG_DEVICE; M.A.sfl = c->seafloor; M.A.huni = nullptr; M.A.seed = c->seed;
-    M.A.step = (unsigned long long)extras->vmix_step;
-    M.vadv = extras->vmix_vadv;
-    M.w_slot = -1;
-    for (int k = 0; k < G.nv; ++k) if (G.var[k] == VAR_W) M.w_slot = k;
-    if (M.vadv >= 0 && M.w_slot < 0 && !p->env[VAR_W]) return fail(ODR_ERR_STATE, "upward_sea_water_velocity has not been sampled");
-    mix_fused = true;
-  }
-  if (mix_fused) {
-    odr_i_step_mix(c, p, G, S, scheme, t, dt, factor, M);
-    HIPCHK(hipGetLastError());
-    return coast_action ? read_counter(c, n_on_land) : 0;
-  }
-  const int lanes = lane_count(c, p, want_mix, N.on);
-  if (lanes > 1) {
-    if ((rc = ensure_env(c, p, VAR_SSH))) return rc;
-    if ((rc = step_in_lanes(c, p, lanes, G, S, scheme, t, dt, factor, N, extras))) return rc;
-    return coast_action ? read_counter(c, n_on_land) : 0;
-  }
   if (odr_i_step_tile(c, p, G, S, scheme, t, dt, factor, N)) {   // the records of the workgroup's node rectangle in LDS (odr_tile.hip.h)
     HIPCHK(hipGetLastError());
     if ((rc = coast_action ? read_counter(c, n_on_land) : 0)) return rc;
@@ -332,7 +245,7 @@ int odr_env_coast_advect(odr_ctx *c, odr_particles *p, int nvars, const int32_t 
       if ((rc = odr_i_red_records(c, p, &S.red))) return rc;
     }
   }
-  if (count_in_launch) { S.wcount = p->wcount; S.sflags = c->counter + 2; }   // (k_step_grid only: the tile / lane / merged paths left above)
+  if (count_in_launch) { S.wcount = p->wcount; S.sflags = c->counter + 2; }   // (k_step_grid only: the tile path left above)
   if (N.on && (scheme > 0 || main_noise)) {
     if (scheme > 0 && N.rng_mode == ODR_RNG_HOST && !N.stage) return fail(ODR_ERR_INVALID, "no host draws for the Runge-Kutta stage calls");
     if (N.sm == ODR_STAGE_FAST && scheme > 0) odr_i_step_fast_noise(c, p, G, S, scheme, t, dt, factor, N);

@@ -82,20 +82,18 @@ static void launch_step_grid(odr_ctx *c, odr_particles *p, const EnvGroupDesc &G
   dim3 g(nblk(p->n)), b(BLOCK);
   PView v = view(p);
   float f = (float)factor;
-  // what-if runs: ODR_OCC_LDS=<bytes> of (unused) dynamic LDS per workgroup caps the workgroups per CU (160 KiB / bytes)
-  static const size_t occ_lds = getenv("ODR_OCC_LDS") ? (size_t)atoll(getenv("ODR_OCC_LDS")) : 0;
   // the C3 group under the FAST stage arithmetic: its layout as compile-time constants (ODR_NO_LAYOUT_SPEC=1: the run-time
   // layout, for A/B runs and tests)
   if constexpr (SCHEME == 2 && !NOISE && SM == 1) {
     if (odr_proj_template(s.proj) == PROJ_LATLONG && is3d && layout_matches<LayoutC3>(G, S) && !getenv("ODR_NO_LAYOUT_SPEC")) {
-      hipLaunchKernelGGL((k_step_grid<SCHEME, PROJ_LATLONG, true, NOISE, 0, false, SM, LayoutC3>), g, b, occ_lds, c->stream, c->dw, v, G, S,
+      hipLaunchKernelGGL((k_step_grid<SCHEME, PROJ_LATLONG, true, NOISE, SM, LayoutC3>), g, b, 0, c->stream, c->dw, v, G, S,
                          dt, f, th, tf, c->counter, N);
       p->step_launches[1]++;
       return;
     }
   }
   p->step_launches[0]++;
-#define ODR_LAUNCH(PROJ, D3) hipLaunchKernelGGL((k_step_grid<SCHEME, PROJ, D3, NOISE, 0, false, SM>), g, b, occ_lds, c->stream, c->dw, v, G, S, dt, f, th, tf, c->counter, N)
+#define ODR_LAUNCH(PROJ, D3) hipLaunchKernelGGL((k_step_grid<SCHEME, PROJ, D3, NOISE, SM>), g, b, 0, c->stream, c->dw, v, G, S, dt, f, th, tf, c->counter, N)
   switch (odr_proj_template(s.proj)) {
     case PROJ_LATLONG: if (is3d) ODR_LAUNCH(PROJ_LATLONG, true); else ODR_LAUNCH(PROJ_LATLONG, false); break;
     case PROJ_STERE_POLAR: if (is3d) ODR_LAUNCH(PROJ_STERE_POLAR, true); else ODR_LAUNCH(PROJ_STERE_POLAR, false); break;
@@ -117,9 +115,6 @@ static void step_dispatch(odr_ctx *c, odr_particles *p, const EnvGroupDesc &G, c
 // odr_step_tile.hip: the fused step on the workgroup's LDS tile; false when it does not apply (the caller launches k_step_grid)
 bool odr_i_step_tile(odr_ctx *c, odr_particles *p, const EnvGroupDesc &G, StepDesc S, int scheme, double t, double dt,
                      double factor, const StageNoise &N);
-// defined in odr_step_mix.hip: the step with OceanDrift.vertical_mixing inside the launch
-void odr_i_step_mix(odr_ctx *c, odr_particles *p, const EnvGroupDesc &G, const StepDesc &S, int scheme, double t, double dt,
-                    double factor, const StepMix &M);
 // developer build (-DODR_PHASE_TIMING): per-phase cycles of the k_step_grid instantiations of ONE translation unit (g_phase is
 // a per-unit device variable), averaged per sampled wave
 #ifdef ODR_PHASE_TIMING

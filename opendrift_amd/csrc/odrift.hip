@@ -89,14 +89,6 @@ int odr_ctx_destroy(odr_ctx *c) {
   (void)hipFree(c->dilate_flags);
   if (c->tile_flags) (void)hipFree(c->tile_flags);
   for (int k = 0; k < 2; ++k) if (c->bounce[k]) (void)hipHostFree(c->bounce[k]);
-  if (c->lanes_ready) {
-    for (int l = 0; l < ODR_MAX_LANES; ++l) {
-      (void)hipStreamDestroy(c->lane_stream[l]);
-      (void)hipEventDestroy(c->lane_step[l]);
-      (void)hipEventDestroy(c->lane_done[l]);
-    }
-    (void)hipEventDestroy(c->lane_fork);
-  }
   (void)hipEventDestroy(c->ev0);
   (void)hipEventDestroy(c->ev1);
   (void)hipStreamDestroy(c->own_stream);

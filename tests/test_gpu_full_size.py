@@ -44,8 +44,7 @@ def _leeway_props(P, n, ids):
 _SIZES = [('c3', 10_000_000, 3, 499), ('c4', 6_250_000, 3, 311), ('c5', 10_000_000, 3, 499), ('c2', 1_000_000, 20, 97)]
 # EXACT under the ids the cases always had; FAST (bench.py's --stage-math default) for the Runge-Kutta workloads.  C5 has no FAST
 # case: the Leeway step is Euler, and its launch (odr_env_coast_leeway -> k_step_leeway, opendrift_amd/csrc/odrift.hip:1678-1682)
-# never reads the context's stage arithmetic -- stage_math is read by the Runge-Kutta launches only (odr_step.hip:63,
-# odr_step_mix.hip:24).
+# never reads the context's stage arithmetic -- stage_math is read by the Runge-Kutta launches only (odr_step.hip:63).
 _CASES = [c + ('exact',) for c in _SIZES] + [c + ('fast',) for c in _SIZES if c[0] != 'c5']
 
 

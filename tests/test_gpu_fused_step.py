@@ -148,27 +148,23 @@ def test_fused_with_seafloor_and_age_equals_separate(ctx):
 
 @pytest.mark.parametrize('scheme', ['euler', 'runge-kutta4'])
 @pytest.mark.parametrize('vadv', [None, False, True])
-def test_mixing_inside_the_step_launch_gives_the_same_bits_as_two_calls(monkeypatch, scheme, vadv):
-    """odr_step_extras.vmix: OceanDrift.vertical_mixing (+ vertical_advection) inside k_step_grid<..., MIXQ> -- K column
-    gathered at the sample position while the particle is in registers -- against odr_env_coast_advect followed by
-    odr_vmix (device RNG keyed by element ID and step): bit-identical lon / lat / z / status, also with the sea floor
-    in reach, a coastline and a reader time level crossed between the stages."""
+def test_mixing_inside_the_step_launch_gives_the_same_bits_as_two_calls(scheme, vadv):
+    """odr_step_extras.vmix: OceanDrift.vertical_mixing (+ vertical_advection) as part of odr_env_coast_advect against
+    odr_env_coast_advect followed by an explicit odr_vmix with the same dt_mix, step and vertical advection (device RNG keyed
+    by element ID and step): bit-identical lon / lat / z / status / moving / age and sampled environment, also with the sea
+    floor in reach, a coastline, a reader time level crossed between the stages, an element count that is not a multiple of
+    the workgroup size and a sort that drops the environment between steps."""
     g = synth.grid3d(nx=96, ny=80, nz=8, nt=3, seed=5)
     g[DEPTH][:] = np.minimum(g[DEPTH], 60.0 + 100.0 * np.linspace(0, 1, 96)[None, None, :]).astype(np.float32)
     names = [U, V, W, KZ, DEPTH, LAND]
     rng = np.random.default_rng(12)
-    n = 30000
+    n = 30011
     lon = rng.uniform(g['x'][3], g['x'][-4], n)
     lat = rng.uniform(g['y'][3], g['y'][-4], n)
     z = -rng.uniform(0, 70, n)
     z[:2000] = 0.0
     res = []
-    for fused in (True, False):
-        if fused:
-            monkeypatch.setenv('ODR_FUSED_MIX', '1')
-            monkeypatch.delenv('ODR_NO_FUSED_MIX', raising=False)
-        else:
-            monkeypatch.setenv('ODR_NO_FUSED_MIX', '1')
+    for in_call in (True, False):
         ctx = Context(seed=4)
         sid = ctx.add_grid(g['x'], g['y'], z=g['z'])
         for k in range(3):
@@ -180,49 +176,13 @@ def test_mixing_inside_the_step_launch_gives_the_same_bits_as_two_calls(monkeypa
         P.append(lon, lat, z=z, terminal_velocity=np.where(np.arange(n) % 3 == 0, -0.004, 0.001).astype(np.float32))
         P.sort_by_cell(sid)
         for k, t in enumerate((0.0, 900.0, 3300.0, 3600.0)):
-            P.env_coast_advect([U, V, W, DEPTH, SSH, LAND], t, scheme, 600.0, coastline='previous', count=False, seafloor=True,
-                               age_dt=600.0, vmix=dict(dt_mix=60.0, step=k, vertical_advection=vadv))
-        d = P.download()
-        o = np.argsort(d['ID'])
-        res.append(tuple(d[q][o] for q in ('lon', 'lat', 'z', 'status', 'moving')))
-        P.close()
-        ctx.close()
-    for a, b in zip(*res):
-        assert np.array_equal(a, b)
-    assert np.abs(res[0][2] - np.sort(z)[::1][0] * 0).max() > 1.0 and (res[0][2] <= 0).all()
-
-
-@pytest.mark.parametrize('lanes', [2, 5])
-def test_step_in_lanes_gives_the_same_bits_as_one_launch(monkeypatch, lanes):
-    """ODR_LANES: the step + mixing of contiguous particle windows on streams of their own (step_in_lanes, odr_step.hip),
-    so that the mixing kernel of one window and the step kernel of the next are resident together.  Per-particle kernels,
-    RNG keyed by element ID: bit-identical lon / lat / z / status / environment to the single launch, also with a last
-    window that is not a multiple of the workgroup size."""
-    g = synth.grid3d(nx=96, ny=80, nz=8, nt=3, seed=5)
-    g[DEPTH][:] = np.minimum(g[DEPTH], 60.0 + 100.0 * np.linspace(0, 1, 96)[None, None, :]).astype(np.float32)
-    names = [U, V, W, KZ, DEPTH, LAND]
-    rng = np.random.default_rng(13)
-    n = 30011
-    lon = rng.uniform(g['x'][3], g['x'][-4], n)
-    lat = rng.uniform(g['y'][3], g['y'][-4], n)
-    z = -rng.uniform(0, 70, n)
-    monkeypatch.setenv('ODR_LANES_MIN_N', '0')
-    res = []
-    for nl in (lanes, 1):
-        monkeypatch.setenv('ODR_LANES', str(nl))
-        ctx = Context(seed=4)
-        sid = ctx.add_grid(g['x'], g['y'], z=g['z'])
-        for k in range(3):
-            ctx.upload_block(sid, k, float(g['t'][k]), {nm: g[nm][k] for nm in names})
-        for nm in names:
-            ctx.bind(nm, [sid], {LAND: np.nan, DEPTH: 10000.0}.get(nm, 0.0))
-        ctx.bind(SSH, [], 0.0)
-        P = ctx.particles(n)
-        P.append(lon, lat, z=z, terminal_velocity=np.where(np.arange(n) % 3 == 0, -0.004, 0.001).astype(np.float32))
-        P.sort_by_cell(sid)
-        for k, t in enumerate((0.0, 900.0, 3300.0, 3600.0)):
-            P.env_coast_advect([U, V, W, DEPTH, SSH, LAND], t, 'runge-kutta4', 600.0, coastline='previous', count=False,
-                               seafloor=True, age_dt=600.0, vmix=dict(dt_mix=60.0, step=k, vertical_advection=True))
+            step = dict(coastline='previous', count=False, seafloor=True, age_dt=600.0)
+            if in_call:
+                P.env_coast_advect([U, V, W, DEPTH, SSH, LAND], t, scheme, 600.0,
+                                   vmix=dict(dt_mix=60.0, step=k, vertical_advection=vadv), **step)
+            else:
+                P.env_coast_advect([U, V, W, DEPTH, SSH, LAND], t, scheme, 600.0, **step)
+                P.vmix(t, 600.0, 60.0, step=k, fuse_vertical_advection=vadv)
             if k == 1:
                 P.sort_by_cell(sid, keep_environment=False)
         d = P.download()
@@ -233,6 +193,7 @@ def test_step_in_lanes_gives_the_same_bits_as_one_launch(monkeypatch, lanes):
         ctx.close()
     for a, b in zip(*res):
         assert np.array_equal(a, b, equal_nan=True)
+    assert np.abs(res[0][2] - np.sort(z)[::1][0] * 0).max() > 1.0 and (res[0][2] <= 0).all()
 
 
 def _leeway_props(P, n, seed):

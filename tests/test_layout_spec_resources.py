@@ -11,7 +11,7 @@ import tempfile
 import pytest
 
 READELF = '/opt/rocm/llvm/bin/llvm-readelf'
-SPEC = 'k_step_gridILi2ELi0ELb1ELb0ELi0ELb0ELi1ENS_8LayoutC3E'
+SPEC = 'k_step_gridILi2ELi0ELb1ELb0ELi1ENS_8LayoutC3E'
 
 
 def _code_objects(lib):
@@ -32,7 +32,7 @@ def _code_objects(lib):
 
 
 @pytest.mark.skipif(not os.path.exists(READELF), reason='needs the ROCm LLVM tools')
-def test_static_layout_step_kernel_does_not_spill():
+def test_static_layout_step_kernel_has_no_scratch_and_at_most_96_vgprs():
     import __graft_entry__ as g
     g.build()
     from opendrift_amd import _abi

@@ -1,7 +1,6 @@
 #!/usr/bin/env python
 """RK4 current advection on a Lambert-conformal reader (the C4 fields re-labelled as an lcc grid, WGS84): the launch of
-odr_env_coast_advect with the FAST stage arithmetic.   python tools/bench_lcc.py [particles]
-A/B: ODR_LIB=tools/_libX.so built with -DODR_NO_STAGE_ROT_CLOSED_FORM (the stage rotation from rotation_angle, rounds 3-4)."""
+odr_env_coast_advect with the FAST stage arithmetic.   python tools/bench_lcc.py [particles]"""
 import os
 import sys
 

@@ -21,7 +21,7 @@ SM = sys.argv[1] if len(sys.argv) > 1 else 'fast'
 SFX = '' if SM == 'fast' else '_' + SM
 src, dst = os.path.join(ROOT, 'gpurun_out', 'prof_' + R + SFX), os.path.join(ROOT, 'profiles')
 N = {'c3': 10_000_000, 'c4': 6_250_000, 'c5': 10_000_000}
-DOMINANT = {'c3': 'k_step_grid<2, 0, true', 'c4': 'k_step_grid<2, 2, false', 'c5': 'k_step_leeway<2>'}   # (either stage math: the template's SM argument comes last)
+DOMINANT = {'c3': 'k_step_grid<2, 0, true', 'c4': 'k_step_grid<2, 2, false', 'c5': 'k_step_leeway<2>'}   # (either stage math and slot layout: the prefix ends before the SM argument)
 SECOND = {'c3': 'k_vmix_col<3, true'}
 for w in ('c3', 'c4', 'c5', 'c3_model_api'):
     f = os.path.join(src, '%s_%s_kernel_stats.txt' % (R, w))
