@@ -517,6 +517,12 @@ int odr_particles_tile_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out4);
  *         layout is a compile-time constant (the C3 group under ODR_STAGE_FAST: csrc/odr_field.hip.h LayoutC3)}.
  * The environment variable ODR_NO_LAYOUT_SPEC=1 keeps every launch on the run-time layout. */
 int odr_particles_step_layout_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out2);
+/* The mixing launches of odr_vmix since the set was created:
+ * out3 = {launches of the K-column kernel (csrc/odr_kernels.hip.h k_vmix_col) that read its configuration at run time, launches
+ *         of its instantiation for C3's configuration as compile-time constants (VMixC3), launches of the other mixing kernels
+ *         (the five-level window, the generic and OpenOil kernels)}.
+ * The environment variable ODR_NO_VMIX_SPEC=1 keeps every column launch on the run-time configuration. */
+int odr_particles_vmix_layout_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out3);
 /* counts and min/max used for the per-step log line and early-outs (:2212-2233):
  * out16 = {n_active, lon_min, lon_max, lat_min, lat_max, z_min, z_max, D_max, stokes_sum_max,
  *          wind_speed_max, wdf_surface_max, n_surface, hs_max, tp_max, 0, 0} */

@@ -177,6 +177,7 @@ struct odr_particles {
   long long wg_cap, wg_grid, wg_n, wg_list_cap;
   unsigned long long wg_launches;            // host: launches that took the LDS-tile path
   unsigned long long step_launches[2];       // host: k_step_grid launches with the run-time slot layout [0], a static one [1]
+  unsigned long long vmix_launches[3];       // host: odr_vmix launches of k_vmix_col with the run-time configuration [0], a static one [1], of the other mixing kernels [2]
   double *z_keep;       // odr_particles_truncate_z: the elements' own z while the sampling calls see the clipped one
   long long z_keep_n;
   bool z_truncated;

@@ -472,19 +472,58 @@ struct VMixDesc {
   const unsigned long long *guard;   // nullptr, or: the launch does nothing unless *guard != 0 (odr_ctx_guard_next_vmix)
 };
 
+// The configuration of k_vmix_col -- the K source's longitude convention, projection, level count and level spacing, and the
+// call's RNG mode, surface mixing, sea-floor action, fused vertical advection and sub-step count -- as a template parameter.  Each member
+// takes the run-time value: VMixRT hands it back (any configuration), a static configuration returns its constant, and the
+// branches on it fold away.  The host launches a static configuration only when every run-time value equals the constant
+// (vmix_layout_matches, odr_mix.hip); the arithmetic and its rounding points are the same.
+struct VMixRT {
+  static constexpr bool STATIC = false;
+  __host__ __device__ static constexpr int proj_kind(int k) { return k; }
+  __host__ __device__ static constexpr int lon_mode(int m) { return m; }
+  __host__ __device__ static constexpr int mod360_x(int m) { return m; }
+  __host__ __device__ static constexpr int nzp(int n, int /*NL*/) { return n; }
+  __host__ __device__ static constexpr bool uniform_z(bool u) { return u; }
+  __host__ __device__ static constexpr int rng_mode(int m) { return m; }
+  __host__ __device__ static constexpr int mix_at_surface(int m) { return m; }
+  __host__ __device__ static constexpr int sf_action(int a) { return a; }
+  __host__ __device__ static constexpr int vadv(int v) { return v; }
+  __host__ __device__ static constexpr int ntimes(int n) { return n; }
+  __device__ static void proj_fwd(const DevProj &p, double lon, double lat, double &x, double &y) { proj_fwd_rt(p, lon, lat, x, y); }
+};
+// C3 (bench.py): K from one lat / lon reader (longitudes -180 .. 180, no x wrap) whose z levels are not uniformly spaced, every
+// level of the column (NL = 4 NQ: no padding, no level cut), device RNG, no mixing at the surface, the sea floor lifts
+// (general:seafloor_action 'lift_to_seafloor', the context's default), vertical advection fused below the surface
+// (fuse_vertical_advection=False), ten sub-steps
+struct VMixC3 {
+  static constexpr bool STATIC = true;
+  __host__ __device__ static constexpr int proj_kind(int) { return PROJ_LATLONG; }
+  __host__ __device__ static constexpr int lon_mode(int) { return 1; }
+  __host__ __device__ static constexpr int mod360_x(int) { return 0; }
+  __host__ __device__ static constexpr int nzp(int, int NL) { return NL; }
+  __host__ __device__ static constexpr bool uniform_z(bool) { return false; }
+  __host__ __device__ static constexpr int rng_mode(int) { return 0; }         // ODR_RNG_DEVICE
+  __host__ __device__ static constexpr int mix_at_surface(int) { return 0; }
+  __host__ __device__ static constexpr int sf_action(int) { return 1; }        // ODR_SEAFLOOR_LIFT
+  __host__ __device__ static constexpr int vadv(int) { return 0; }
+  __host__ __device__ static constexpr int ntimes(int) { return 10; }        // 600 s / 60 s
+  __device__ static void proj_fwd(const DevProj &, double lon, double lat, double &x, double &y) { x = lon; y = lat; }   // (proj_fwd of PROJ_LATLONG)
+};
+
 // K column of one particle at (lon, lat) -> Kp[level][tid] (LDS), time-interpolated like the ReaderBlock's profiles
 // hook: arithmetic of the caller that does not depend on the column (the first Philox block of the particle's stream), run
 // right behind the gathers of the first quad so that it overlaps their flight instead of standing in front of their issue
-template <int NQ, bool TL, class HOOK>
+template <int NQ, bool TL, class VM, class HOOK>
 __device__ __forceinline__ void vmix_col_fill(const DevSource &s, const VMixDesc &D, double lon, double lat, double *Kp,
                                               int tid, HOOK &&hook) {
   const double Kfb = (double)D.Kfb;
   double x, y;
-  if (s.lon_mode == 1) lon = np_mod(lon + 180.0, 360.0) - 180.0;
-  else if (s.lon_mode == 2) lon = np_mod(lon, 360.0);
-  proj_fwd_rt(s.proj, lon, lat, x, y);
+  const int lon_mode = VM::lon_mode(s.lon_mode);
+  if (lon_mode == 1) lon = np_mod(lon + 180.0, 360.0) - 180.0;
+  else if (lon_mode == 2) lon = np_mod(lon, 360.0);
+  VM::proj_fwd(s.proj, lon, lat, x, y);
   const bool cov = x >= s.xmin && x <= s.xmax && y >= s.ymin && y <= s.ymax;
-  if (s.mod360_x) x = np_mod(x, 360.0);
+  if (VM::mod360_x(s.mod360_x)) x = np_mod(x, 360.0);
   const DevBlock &bb = s.slot[D.geo_slot];
   const double xi = __dmul_rn(div_cr(x - bb.x0, bb.xspan, bb.ixspan), (double)(bb.nx - 1));
   const double yi = __dmul_rn(div_cr(y - bb.y0, bb.yspan, bb.iyspan), (double)(bb.ny - 1));
@@ -504,6 +543,11 @@ __device__ __forceinline__ void vmix_col_fill(const DevSource &s, const VMixDesc
   const double w00 = wy0 * wx0, w01 = wy0 * tx, w10 = ty * wx0, w11 = ty * tx;
 #pragma unroll
   for (int q = 0; q < NQ; ++q) {
+    // (a static configuration: fences in front of and behind the gathers of quads 1 .. NQ - 1.  Without them the scheduler
+    // hoists part of a quad's gathers into the previous quad's arithmetic -- the 8-level column with two time levels then spills
+    // 8-12 B at 80 registers -- or splits its gathers into two round trips.  With them every quad's gathers are one clause,
+    // issued behind the previous quad's stores, as in the run-time configuration.)
+    if (VM::STATIC && q > 0) __builtin_amdgcn_sched_barrier(0);
     // both time levels requested before anything is consumed
     const F4 b00 = ld_off<F4>(kb, o00 + 16u * q), b01 = ld_off<F4>(kb, o01 + 16u * q);
     const F4 b10 = ld_off<F4>(kb, o10 + 16u * q), b11 = ld_off<F4>(kb, o11 + 16u * q);
@@ -512,6 +556,7 @@ __device__ __forceinline__ void vmix_col_fill(const DevSource &s, const VMixDesc
       a00 = ld_off<F4>(ka, o00 + 16u * q); a01 = ld_off<F4>(ka, o01 + 16u * q);
       a10 = ld_off<F4>(ka, o10 + 16u * q); a11 = ld_off<F4>(ka, o11 + 16u * q);
     }
+    if (VM::STATIC && q > 0) __builtin_amdgcn_sched_barrier(0);
     if (q == 0) hook();
     double v[4];
     v[0] = (double)bilw(b00.x, b01.x, b10.x, b11.x, w00, w01, w10, w11);
@@ -542,33 +587,35 @@ struct VMixArgs {
 };
 struct MixRng { MixKey key; uint4 q; bool primed; };
 // the particle's stream of this step with its first block drawn (ODR_RNG_DEVICE)
+template <class VM = VMixRT>
 __device__ __forceinline__ MixRng mix_rng_begin(const VMixArgs &A, int id) {
   MixRng R;
   R.key = mix_key(A.seed, A.step, id);
   R.q = make_uint4(0u, 0u, 0u, 0u);
   R.primed = false;
-  if (A.rng_mode == 0) {
+  if (VM::rng_mode(A.rng_mode) == 0) {
     R.q = mix_block(R.key, 0u);
     R.primed = true;
   }
   return R;
 }
-template <int NQ>
+template <int NQ, class VM = VMixRT>
 __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, const double *Kp, const double *gsh, int tid,
                                                 const VMixArgs &A, long long i, long long n, int id, double z, int &moving,
                                                 float Zmin, float tv, int &sf_flags, const MixRng *pre) {
   constexpr int NL = 4 * NQ;
+  static_assert(!VM::STATIC || NL >= 3, "a static configuration has the three-level window inside the profile");
   const double dt = A.dt;
-  const int mix_at_surface = A.mix_at_surface, rng_mode = A.rng_mode, sfl = A.sfl;
+  const int mix_at_surface = VM::mix_at_surface(A.mix_at_surface), rng_mode = VM::rng_mode(A.rng_mode), sfl = A.sfl;
   // level boundaries (see k_vmix) in scalar registers; levels past the profile never match
   double zm[NL - 1];
 #pragma unroll
   for (int k = 0; k < NL - 1; ++k) zm[k] = k < nzp - 1 ? s.zmid[k] : __builtin_inf();
-  const bool uniform_z = s.vg_uniform != 0;
+  const bool uniform_z = VM::uniform_z(s.vg_uniform != 0);
   const double gd0 = s.vg_d[0], gi0 = s.vg_id[0], gd1 = s.vg_d[1], gi1 = s.vg_id[1], gd2 = s.vg_d[2], gi2 = s.vg_id[2];
   const double sgn = dt > 0 ? 1.0 : (dt < 0 ? -1.0 : 0.0);
   const double dt_mix = A.dt_mix_cfg * sgn;
-  const int ntimes = abs((int)(dt / dt_mix));
+  const int ntimes = VM::ntimes(abs((int)(dt / dt_mix)));
   const double r = 1.0 / 3, ir = 1.0 / r;
   // w*dt_mix*moving: dt_mix is a NumPy float64 scalar (np.sign, oceandrift.py:416) -> float64 product under NumPy 2
   double wstep = __dmul_rn(__dmul_rn((double)tv, dt_mix), (double)moving);
@@ -576,12 +623,14 @@ __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, con
   uint4 u4 = make_uint4(0u, 0u, 0u, 0u);
   bool primed = false;
   if (pre) { u4 = pre->q; primed = pre->primed; }
-  // -dK/dz * dt_mix and sqrt(K |dt_mix| 2 / r) of one level (oceandrift.py:501-502,527-528)
-  auto level_terms = [&](int zl, double &dk_dt, double &sg) {
+  // -dK/dz * dt_mix and sqrt(K |dt_mix| 2 / r) of one level (oceandrift.py:501-502,527-528).  edges: which ends of the profile
+  // zl can be (bit 0: level 0, bit 1: level nzp - 1) -- the window of a static configuration rules some out (below)
+  auto level_terms = [&](auto edges, int zl, double &dk_dt, double &sg) {
+    constexpr int E = decltype(edges)::value;
     const double Kz = Kp[zl * BLOCK + tid];
     double gK;  // np.gradient(Kprofiles, mixing_z, axis=0)[zl]
-    if (zl == 0) gK = div_cr(Kp[BLOCK + tid] - Kz, gd0, gi0);
-    else if (zl == nzp - 1) gK = div_cr(Kz - Kp[(nzp - 2) * BLOCK + tid], gd1, gi1);
+    if ((E & 1) && zl == 0) gK = div_cr(Kp[BLOCK + tid] - Kz, gd0, gi0);
+    else if ((E & 2) && zl == nzp - 1) gK = div_cr(Kz - Kp[(nzp - 2) * BLOCK + tid], gd1, gi1);
     else if (uniform_z) gK = div_cr(Kp[(zl + 1) * BLOCK + tid] - Kp[(zl - 1) * BLOCK + tid], gd2, gi2);
     else
       gK = __dadd_rn(__dadd_rn(__dmul_rn(gsh[zl], Kp[(zl - 1) * BLOCK + tid]), __dmul_rn(gsh[NL + zl], Kz)),
@@ -591,6 +640,7 @@ __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, con
     dk_dt = __dmul_rn(dK, dt_mix);
     sg = sqrt(div_cr(__dmul_rn(__dmul_rn(Kz, fabs(dt_mix)), 2.0), r, ir));
   };
+  using AnyLevel = std::integral_constant<int, 3>;
   // A particle rarely leaves the three levels around its starting one within a step: their terms are derived once
   // (branch-free selection in the loop); anything else is derived on demand.  With a per-iteration "derive when the
   // level changes" scheme the 64 lanes of a wave make that branch fire in practically every sub-step.
@@ -608,7 +658,11 @@ __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, con
   for (int q = 0; q < 3; ++q) {
     const int zl = lv0 - 1 + q;
     c_dk[q] = 0; c_sg[q] = 0;
-    if (zl >= 0 && zl < nzp) level_terms(zl, c_dk[q], c_sg[q]);
+    if constexpr (VM::STATIC) {   // nzp >= 3: lv0 in [1, nzp - 2], so level zl is in the profile, and only q = 0 / 2 can be an end
+      if (q == 0) level_terms(std::integral_constant<int, 1>(), zl, c_dk[q], c_sg[q]);
+      else if (q == 1) level_terms(std::integral_constant<int, 0>(), zl, c_dk[q], c_sg[q]);
+      else level_terms(std::integral_constant<int, 2>(), zl, c_dk[q], c_sg[q]);
+    } else if (zl >= 0 && zl < nzp) level_terms(AnyLevel(), zl, c_dk[q], c_sg[q]);
   }
   // The level of a sub-step is the number of boundaries below d (odd ones count when d >= zm, even ones when d > zm).
   // Inside the cached window only the window's own four boundaries decide -- lv0 - 2 ... lv0 + 1, per lane, with the
@@ -626,7 +680,8 @@ __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, con
     wb[j] = b;
   }
   // the sub-steps in groups of five = one Philox block: inside the unrolled group the word a sub-step takes from the block is
-  // known at compile time (a run-time `it % 5` costs a chain of selects and the fifth word's assembly in every sub-step)
+  // known at compile time (a run-time `it % 5` costs a chain of selects and the fifth word's assembly in every sub-step).
+  // (A static sub-step count: the groups unroll, and no sub-step tests the count.)
   for (int it0 = 0; it0 < ntimes; it0 += 5) {
   if (rng_mode == 0 && !(primed && it0 == 0)) u4 = mix_block(st, (unsigned)it0 / 5u);
 #pragma unroll
@@ -645,7 +700,7 @@ __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, con
     }
     double dKdt = q == 0 ? c_dk[0] : (q == 1 ? c_dk[1] : c_dk[2]);
     double sig = q == 0 ? c_sg[0] : (q == 1 ? c_sg[1] : c_sg[2]);
-    if (q < 0 || q > 2) level_terms(zi, dKdt, sig);
+    if (q < 0 || q > 2) level_terms(AnyLevel(), zi, dKdt, sig);
     double R;
     if (rng_mode == 1) R = __dsub_rn(__dmul_rn(2.0, A.huni[(size_t)it * n + i]), 1.0);
     else R = mix_R_of(mix_word(u4, (unsigned)k5));
@@ -656,7 +711,7 @@ __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, con
     if (!mix_at_surface && surface) z = 0.0;
     if (z > 0) z = 0.0;
     if (z < (double)Zmin) {   // "let particles stick to bottom": interact_with_seafloor() inside the loop (oceandrift.py:555-559)
-      const int act = sfl & 255;
+      const int act = VM::sf_action(sfl & 255);
       if (act == 3) sf_flags |= 2;                       // previous: lon/lat go back, z stays
       else if (act) {
         z = (double)Zmin;                                // lift_to_seafloor / deactivate
@@ -1880,10 +1935,10 @@ __device__ __forceinline__ VMixState vmix_load_state(const PView &p, long long i
   return S;
 }
 // one particle of k_vmix_col: column into the thread's LDS slots, sub-steps, stores
-template <int NQ, bool TL>
+template <int NQ, bool TL, class VM>
 __device__ __forceinline__ void vmix_col_particle(const DevSource &s, const PView &p, const VMixDesc &D, const VMixArgs &A,
                                                   int vadv, long long i, double *Kp, const double *gsh, int tid, const VMixState &S) {
-  const int nzp = D.nzp, sfl = A.sfl;
+  const int nzp = VM::nzp(D.nzp, 4 * NQ), sfl = A.sfl;
   const double dt = A.dt;
   const double slon = S.slon, slat = S.slat, z0 = S.z0;
   int moving = S.moving;
@@ -1892,15 +1947,16 @@ __device__ __forceinline__ void vmix_col_particle(const DevSource &s, const PVie
   MixRng R0;
   R0.key = mix_key(A.seed, A.step, id0); R0.q = make_uint4(0u, 0u, 0u, 0u); R0.primed = false;
   // the stream's first block behind the first gathers of the column: its arithmetic runs while they are in flight
-  vmix_col_fill<NQ, TL>(s, D, slon, slat, Kp, tid, [&]() { R0 = mix_rng_begin(A, id0); });
+  vmix_col_fill<NQ, TL, VM>(s, D, slon, slat, Kp, tid, [&]() { R0 = mix_rng_begin<VM>(A, id0); });
   int sf_flags = 0;
   const float Zmin = __fmul_rn(-1.f, __fadd_rn(dep0, ssh0));  // float32 (:408)
-  double z = vmix_col_walk<NQ>(s, nzp, Kp, gsh, tid, A, i, p.n, id0, z0, moving, Zmin, tv0, sf_flags, &R0);
+  double z = vmix_col_walk<NQ, VM>(s, nzp, Kp, gsh, tid, A, i, p.n, id0, z0, moving, Zmin, tv0, sf_flags, &R0);
   if (sf_flags & 1) {   // deactivate_elements(reason='seafloor') (basemodel/__init__.py:1774-1795)
     if (p.status[i] == 0) p.status[i] = sfl >> 8;
     p.moving[i] = 0;
   }
   if (sf_flags & 2) { p.lon[i] = p.plon[i]; p.lat[i] = p.plat[i]; }
+  vadv = VM::vadv(vadv);
   if (vadv >= 0 && (vadv ? z <= 0 : z < 0)) {  // vertical_advection (oceandrift.py:315-350)
     // (w is read here, not with the rest of the state: held through the walk it was the one value the allocator put into
     // scratch memory at 80 registers, behind a wait for every load in flight)
@@ -1910,7 +1966,8 @@ __device__ __forceinline__ void vmix_col_particle(const DevSource &s, const PVie
   }
   p.z[i] = z;
 }
-template <int NQ, bool TL>
+// VM: the mixing configuration (VMixRT / VMixC3 above)
+template <int NQ, bool TL, class VM = VMixRT>
 __global__ __launch_bounds__(BLOCK, ODR_VMIX_WAVES) void k_vmix_col(const DevWorld *__restrict__ W, PView p, VMixDesc D,
                                                     double dt, double dt_mix_cfg, int mix_at_surface,
                                                     int rng_mode, const double *__restrict__ huni,
@@ -1920,7 +1977,7 @@ __global__ __launch_bounds__(BLOCK, ODR_VMIX_WAVES) void k_vmix_col(const DevWor
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x;
   const DevSource &s = W->src[D.sid];
-  const int nzp = D.nzp;
+  const int nzp = VM::nzp(D.nzp, NL);
   double *Kp = (double *)smem;              // [NL][BLOCK]
   double *gsh = Kp + (size_t)NL * BLOCK;    // [4][NL]
   // the particle's state is requested first: its loads and the tables' are one round trip (threads past the end read element 0)
@@ -1937,7 +1994,7 @@ __global__ __launch_bounds__(BLOCK, ODR_VMIX_WAVES) void k_vmix_col(const DevWor
   VMixArgs A;
   A.dt = dt; A.dt_mix_cfg = dt_mix_cfg; A.mix_at_surface = mix_at_surface; A.rng_mode = rng_mode; A.sfl = sfl; A.pad = 0;
   A.huni = huni; A.seed = seed; A.step = step;
-  vmix_col_particle<NQ, TL>(s, p, D, A, vadv, i, Kp, gsh, tid, S);
+  vmix_col_particle<NQ, TL, VM>(s, p, D, A, vadv, i, Kp, gsh, tid, S);
 }
 
 // ---- k_vmix_win: the same mixing with the diffusivity of FIVE levels per particle instead of the whole column.

@@ -3,6 +3,19 @@
 #define ODR_TU_MIX 1
 #include "odr_host.h"
 
+// the K source and the call's settings are exactly the static mixing configuration VM (odr_kernels.hip.h VMixC3): every
+// run-time value equals its constant, the column has no padding level (nzp = 4 nq).  (ntimes as vmix_col_walk forms it)
+template <class VM>
+static bool vmix_layout_matches(const DevSource &s, const VMixDesc &D, int nq, double dt, double dt_mix, int mix_at_surface,
+                                int rng_mode, int sfl, int vadv) {
+  const bool uz = s.vg_uniform != 0;
+  const int ntimes = abs((int)(dt / (dt_mix * (dt > 0 ? 1.0 : (dt < 0 ? -1.0 : 0.0)))));
+  return VM::proj_kind(s.proj.kind) == s.proj.kind && VM::lon_mode(s.lon_mode) == s.lon_mode &&
+         VM::mod360_x(s.mod360_x) == s.mod360_x && VM::nzp(D.nzp, 4 * nq) == D.nzp && VM::uniform_z(uz) == uz &&
+         VM::rng_mode(rng_mode) == rng_mode && VM::mix_at_surface(mix_at_surface) == mix_at_surface &&
+         VM::sf_action(sfl & 255) == (sfl & 255) && VM::vadv(vadv) == vadv && VM::ntimes(ntimes) == ntimes;
+}
+
 int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, int mix_at_surface, int rng_mode,
              const double *huni, uint64_t step) {
   const bool guarded = c->guard_next_vmix != 0;     // odr_ctx_guard_next_vmix: THIS call only, however it ends
@@ -80,12 +93,18 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
     // ODR_VMIX_WINDOW=1 / 0 forces one of them (the parity tests compare the two).
     const char *wenv = getenv("ODR_VMIX_WINDOW");
     const bool win = nzp >= 3 && nzp <= BLOCK && (wenv ? atoi(wenv) != 0 : nzp > 12);
-#define VMIX_COL(NQ)                                                                                              \
+    // C3's configuration as compile-time constants (VMixC3) at both of its field sizes, 8 and 12 levels, when the source and
+    // the call are exactly that configuration; ODR_NO_VMIX_SPEC=1 forces the run-time configuration (A/B runs and tests)
+    const bool spec = !win && (nq == 2 || nq == 3) &&
+                      vmix_layout_matches<VMixC3>(c->hw.src[D.sid], D, nq, dt, dt_mix, mix_at_surface, rng_mode, c->seafloor, vadv) &&
+                      !getenv("ODR_NO_VMIX_SPEC");
+    p->vmix_launches[win ? 2 : spec ? 1 : 0]++;
+#define VMIX_COL(NQ, VM)                                                                                          \
   do {                                                                                                            \
     size_t l2 = sizeof(double) * ((size_t)(4 * NQ) * BLOCK + 4 * (size_t)(4 * NQ));                               \
-    if (tl) hipLaunchKernelGGL((k_vmix_col<NQ, true>), g, b, l2, c->stream, c->dw, v, D, dt, dt_mix,              \
+    if (tl) hipLaunchKernelGGL((k_vmix_col<NQ, true, VM>), g, b, l2, c->stream, c->dw, v, D, dt, dt_mix,          \
                                mix_at_surface, rng_mode, du, c->seed, st, vadv, c->seafloor);                                  \
-    else hipLaunchKernelGGL((k_vmix_col<NQ, false>), g, b, l2, c->stream, c->dw, v, D, dt, dt_mix,                \
+    else hipLaunchKernelGGL((k_vmix_col<NQ, false, VM>), g, b, l2, c->stream, c->dw, v, D, dt, dt_mix,            \
                             mix_at_surface, rng_mode, du, c->seed, st, vadv, c->seafloor);                                     \
   } while (0)
     if (win) {
@@ -95,15 +114,17 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
       else hipLaunchKernelGGL((k_vmix_win<false>), g, b, lw, c->stream, c->dw, v, D, dt, dt_mix, mix_at_surface, rng_mode, du,
                               c->seed, st, vadv, c->seafloor);
     }
+    else if (spec && nq == 2) VMIX_COL(2, VMixC3);
+    else if (spec) VMIX_COL(3, VMixC3);
     // the smallest instantiated quad count >= nq; over-read stays inside the 64-byte array padding
-    else if (nq <= 1) VMIX_COL(1);
-    else if (nq == 2) VMIX_COL(2);
-    else if (nq == 3) VMIX_COL(3);
-    else if (nq == 4) VMIX_COL(4);
-    else if (nq <= 6) VMIX_COL(6);
-    else if (nq <= 8) VMIX_COL(8);
-    else if (nq <= 12) VMIX_COL(12);
-    else VMIX_COL(16);
+    else if (nq <= 1) VMIX_COL(1, VMixRT);
+    else if (nq == 2) VMIX_COL(2, VMixRT);
+    else if (nq == 3) VMIX_COL(3, VMixRT);
+    else if (nq == 4) VMIX_COL(4, VMixRT);
+    else if (nq <= 6) VMIX_COL(6, VMixRT);
+    else if (nq <= 8) VMIX_COL(8, VMixRT);
+    else if (nq <= 12) VMIX_COL(12, VMixRT);
+    else VMIX_COL(16, VMixRT);
 #undef VMIX_COL
   } else if (oil) {
     if (nzp <= 16) hipLaunchKernelGGL((k_vmix<16, true>), g, b, lds, c->stream, c->dw, v, t, dt, dt_mix, mix_at_surface, rng_mode, du, c->seed, st, vadv, sfl_cut, c->oil);
@@ -112,7 +133,14 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
   } else if (nzp <= 16) hipLaunchKernelGGL(k_vmix<16>, g, b, lds, c->stream, c->dw, v, t, dt, dt_mix, mix_at_surface, rng_mode, du, c->seed, st, vadv, sfl_cut);
   else if (nzp <= 32) hipLaunchKernelGGL(k_vmix<32>, g, b, lds, c->stream, c->dw, v, t, dt, dt_mix, mix_at_surface, rng_mode, du, c->seed, st, vadv, sfl_cut);
   else hipLaunchKernelGGL(k_vmix<1>, g, b, lds, c->stream, c->dw, v, t, dt, dt_mix, mix_at_surface, rng_mode, du, c->seed, st, vadv, sfl_cut);
+  if (!fast) p->vmix_launches[2]++;
   HIPCHK(hipGetLastError());
+  return 0;
+}
+
+int odr_particles_vmix_layout_stats(odr_ctx *c, odr_particles *p, uint64_t *out3) {
+  REQUIRE(c && p && out3, "NULL argument");
+  for (int k = 0; k < 3; ++k) out3[k] = p->vmix_launches[k];
   return 0;
 }
 

@@ -909,6 +909,14 @@ class Particles:
         check(self.lib.odr_particles_step_layout_stats(self.ctx.h, self.h, out))
         return dict(runtime=int(out[0]), static=int(out[1]))
 
+    def vmix_layout_stats(self):
+        """Launches of the mixing kernels (odr_particles_vmix_layout_stats): the K-column kernel with the run-time configuration,
+        with C3's compile-time one, and the other mixing kernels."""
+        import ctypes as C
+        out = (C.c_uint64 * 3)()
+        check(self.lib.odr_particles_vmix_layout_stats(self.ctx.h, self.h, out))
+        return dict(runtime=int(out[0]), static=int(out[1]), other=int(out[2]))
+
     def reduce_global(self, combine, wind_drift_depth=0.1, relative_wind=False):
         """Sharded run: this set's raw reductions -> combine(raw16) over the ranks (counts summed, maxima maximised) ->
         installed for the movers that follow, until reduce_unpin()."""
