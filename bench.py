@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- particle-steps/s of the MI355X hot path on BASELINE.json's workloads.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5] [--particles P] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c4|c5] [--particles P] [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the per-timestep hot path over all particles of this rank with the
 inputs already resident in HBM (field blocks uploaded, particle SoA on device):
@@ -13,8 +13,11 @@ inputs already resident in HBM (field blocks uploaded, particle SoA on device):
   c4: NorKyst-800-shaped 2602x902 polar-stereographic surface block (current, wind, Stokes,
       landmask), RK4 + wind + Stokes + horizontal diffusion + stranding + compaction, 6.25 M particles.
   c5: Leeway ensemble members on the same grid (wind / current uncertainty, stranding), 10 M particles.
-One JSON line is printed by rank 0 (metric / roofline / cpu_baseline).  N>1: one process
-per GPU (torchrun), particles sharded, field blocks broadcast once from rank 0 over RCCL; weak scaling (per-GPU
+One JSON line is printed by rank 0.  A plain run sets up, warms up, times the K steps, writes
+--dump-outputs and prints the headline (metric / value / ms_per_step ...).  --full adds everything else the line can carry,
+each leg measured after the headline's steps: the kernels of the step on their own and their roofline, the other stage
+arithmetic, the model API and PCIe-inclusive legs (C3) and the CPU baseline (--no-extras / --no-cpu leave those out).
+N>1: one process per GPU (torchrun), particles sharded, field blocks broadcast once from rank 0 over RCCL; weak scaling (per-GPU
 work fixed).  --block-every N [--block-async]: a new field time level arrives from host memory every N steps
 inside the timed region (PCIe-inclusive rate).
 """
@@ -675,8 +678,11 @@ def main():
     ap.add_argument('--workload', default=os.environ.get('ODR_WORKLOAD', 'c3'), choices=['c2', 'c3', 'c4', 'c5'])
     ap.add_argument('--particles', type=int, default=0, help='particles per GPU (default: the config size)')
     ap.add_argument('--small', action='store_true', help='small field block (debug)')
-    ap.add_argument('--no-cpu', action='store_true')
-    ap.add_argument('--no-extras', action='store_true', help='skip the model_api and pcie_inclusive legs')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline: kernel timings and roofline, the other stage arithmetic, the model_api and '
+                         'pcie_inclusive legs, lds_tile and the CPU baseline (a plain run measures the headline alone)')
+    ap.add_argument('--no-cpu', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: skip the model_api and pcie_inclusive legs')
     ap.add_argument('--host-sort', action='store_true', help='experiment: seed particles already sorted by grid cell')
     ap.add_argument('--cpu-particles', type=int, default=200000)
     ap.add_argument('--cpu-all-cores-helper', action='store_true', help='(internal) the all-cores CPU leg in a process of its own')
@@ -878,93 +884,96 @@ def main():
     el_max = float(D.allreduce_scalars([el], 'max')[0])
     units = float(D.allreduce_scalars([units_rank], 'sum')[0])
 
-    # the two kernels of the step on their own, HIP events on the context stream, exactly the step's launches
-    reps = 20
-    kfused = wl.fused and a.workload in ('c3', 'c4', 'c5')
-    if a.workload != 'c2' and wl.sort_every:
-        P.sort_by_cell(wl.sid)      # the layout right after a re-sort, as in 1 of every 16 steps (the kernels drift apart by < 3 % in between)
-    if not kfused:
-        P.env_sample([U, V], wl.time_of(0))
-    # every launch between its own pair of events (one pair around all 20 launches also times the host whenever it
-    # falls behind the device: seen as 2.5 instead of 0.84 ms at --steps 200 while rocprofv3 reported 0.84 ms)
-    def launch_ms(fn):
-        fn(P, 0)
-        ctx.sync()
-        out = []
-        for k in range(reps):
-            ctx.timer_begin()
-            fn(P, k)
-            out.append(ctx.timer_end())
-        return float(np.mean(out)), float(np.median(out))
-    k_ms, k_ms_median = launch_ms(wl.dominant_kernel)
-    k2_ms = None
-    if a.workload == 'c3':
-        k2_ms, _ = launch_ms(wl.second_kernel)
-    nact = len(P)
-    kbytes = BYTES[a.workload]['fused' if kfused else 'advect']
-    ach = kbytes * nact / (k_ms * 1e-3)
-
-    # the other arithmetic of the stage evaluations on the same particles (a quarter of the steps, same bracketing): the
-    # headline is `a.stage_math`; both modes have a parity gate (tests/test_gpu_parity.py ... / tests/test_gpu_stage_math.py)
-    other_mode, other = ('exact' if a.stage_math == 'fast' else 'fast'), None
-    if a.workload != 'c5' and not a.block_every and not os.environ.get('ODR_BENCH_ONE_MODE'):
-        ctx.set_stage_math(other_mode)
-        # a measurement of its own, whatever --steps says: >= 48 steps that span two re-sorts (a whole number of re-sort
-        # intervals, so that the share of the re-sort in the mean is the steady one), after 8 untimed steps in that mode
-        # (round 4 timed 8 steps without a re-sort among them: 11 % off the 100-step figure)
-        se = wl.sort_every if (wl.sort_every and a.workload != 'c2') else 1
-        nst_o = max(48, a.steps // 4)
-        nst_o = -(-nst_o // se) * se
-        first_o = spin + a.warmup + a.steps
-        for k in range(8):
-            wl.step(P, first_o + k)
-        el_o, units_o = timed_loop(nst_o, first_o + 8)
-        el_o = float(D.allreduce_scalars([el_o], 'max')[0])
-        units_o = float(D.allreduce_scalars([units_o], 'sum')[0])
+    # --full: what the line carries besides the headline, every leg measured after the headline's steps (and after
+    # --dump-outputs), so that the timed region and the dumped state are the same with and without it
+    other, extras = None, {}
+    if a.full:
+        # the two kernels of the step on their own, HIP events on the context stream, exactly the step's launches
+        reps = 20
+        kfused = wl.fused and a.workload in ('c3', 'c4', 'c5')
         if a.workload != 'c2' and wl.sort_every:
-            P.sort_by_cell(wl.sid)
-        ko_ms, ko_med = launch_ms(wl.dominant_kernel)
-        other = dict(value=units_o / el_o, unit='particle-steps/s', ms_per_step=1e3 * el_o / nst_o, steps=nst_o, untimed_steps_before=8,
-                     re_sorts_inside=(nst_o // se if se > 1 else 0), kernel_ms=ko_ms, kernel_ms_median=ko_med)
+            P.sort_by_cell(wl.sid)      # the layout right after a re-sort, as in 1 of every 16 steps (the kernels drift apart by < 3 % in between)
+        if not kfused:
+            P.env_sample([U, V], wl.time_of(0))
+        # every launch between its own pair of events (one pair around all 20 launches also times the host whenever it
+        # falls behind the device: seen as 2.5 instead of 0.84 ms at --steps 200 while rocprofv3 reported 0.84 ms)
+        def launch_ms(fn):
+            fn(P, 0)
+            ctx.sync()
+            out = []
+            for k in range(reps):
+                ctx.timer_begin()
+                fn(P, k)
+                out.append(ctx.timer_end())
+            return float(np.mean(out)), float(np.median(out))
+        k_ms, k_ms_median = launch_ms(wl.dominant_kernel)
+        k2_ms = None
         if a.workload == 'c3':
-            other['second_kernel_ms'] = launch_ms(wl.second_kernel)[0]
-        ctx.set_stage_math(a.stage_math)
+            k2_ms, _ = launch_ms(wl.second_kernel)
+        nact = len(P)
+        kbytes = BYTES[a.workload]['fused' if kfused else 'advect']
+        ach = kbytes * nact / (k_ms * 1e-3)
 
-    # counters of the same command from the committed rocprofv3 passes (profiles/r06_<workload>_pmc[_exact].json, written by
-    # tools/gpu_profile_round.sh + tools/collect_profiles_round.py from this tree): PMC counters cannot be collected from inside
-    # this process.  Used only when they belong to this size and stage math.
-    def load_pmc(mode):
-        for r in ('r06', 'r05', 'r04'):
-            f = os.path.join('profiles', '%s_%s_pmc%s.json' % (r, a.workload, '' if mode == 'fast' else '_' + mode))
-            if os.path.exists(os.path.join(ROOT, f)):
-                pm = json.load(open(os.path.join(ROOT, f)))
-                if pm.get('particles') == n and pm.get('stage_math', mode) == mode:
-                    return pm, f
-        return None, None
-    pmc, pmc_file = load_pmc(a.stage_math)
-    pmc_other, pmc_other_file = load_pmc(other_mode)
-    extras = {}
-    if rank == 0 and world == 1 and not a.no_extras and a.workload == 'c3' and not a.small and not a.block_every:
-        # (0) the drop-in surface: OceanDrift.run() on the same inputs, in a context of its own (first of the extra legs: it
-        # came out 20 % slower when it ran after the upload leg below; the bare sequence's context and particles stay open)
-        extras['model_api'] = model_api_leg(fields, n, 48, dev)
-        extras['model_api']['vs_bare_sequence'] = extras['model_api']['ms_per_step'] / (1e3 * el_max / a.steps)
-    if rank == 0 and world == 1 and not a.no_extras and a.workload == 'c3' and not a.block_every and not a.small and \
-            not os.environ.get('ODR_BENCH_SKIP_PCIE'):
-        # (i) PCIe-inclusive: a new reader time level (hourly fields, 10-minute steps) arrives from pinned host memory
-        # every 6 steps on the upload stream inside the timed region
-        pinned = {kk: ctx.pin(np.ascontiguousarray(fields['g'][kk])) for kk in fields['names']}
-        warm_uploads(pinned)
-        nst = 120     # 20 level periods whatever --steps says (the driver's 20 steps held 4 uploads and no steady state; 48 still read 8 % high)
-        el_p, up = timed_loop(nst, a.warmup, 6, True, pinned)
-        extras['pcie_inclusive'] = dict(ms_per_step=1e3 * el_p / nst, value=up / el_p, unit='particle-steps/s', steps=nst,
-                                        what='one 210 MB time level uploaded every 6 steps (odr_block_upload_async from '
-                                             'page-locked arrays, committed one period later) inside the timed region')
-        for kk in fields['names']:
-            ctx.unpin(pinned[kk])
-        pinned = None
+        # the other arithmetic of the stage evaluations on the same particles (a quarter of the steps, same bracketing): the
+        # headline is `a.stage_math`; both modes have a parity gate (tests/test_gpu_parity.py ... / tests/test_gpu_stage_math.py)
+        other_mode, other = ('exact' if a.stage_math == 'fast' else 'fast'), None
+        if a.workload != 'c5' and not a.block_every and not os.environ.get('ODR_BENCH_ONE_MODE'):
+            ctx.set_stage_math(other_mode)
+            # a measurement of its own, whatever --steps says: >= 48 steps that span two re-sorts (a whole number of re-sort
+            # intervals, so that the share of the re-sort in the mean is the steady one), after 8 untimed steps in that mode
+            # (round 4 timed 8 steps without a re-sort among them: 11 % off the 100-step figure)
+            se = wl.sort_every if (wl.sort_every and a.workload != 'c2') else 1
+            nst_o = max(48, a.steps // 4)
+            nst_o = -(-nst_o // se) * se
+            first_o = spin + a.warmup + a.steps
+            for k in range(8):
+                wl.step(P, first_o + k)
+            el_o, units_o = timed_loop(nst_o, first_o + 8)
+            el_o = float(D.allreduce_scalars([el_o], 'max')[0])
+            units_o = float(D.allreduce_scalars([units_o], 'sum')[0])
+            if a.workload != 'c2' and wl.sort_every:
+                P.sort_by_cell(wl.sid)
+            ko_ms, ko_med = launch_ms(wl.dominant_kernel)
+            other = dict(value=units_o / el_o, unit='particle-steps/s', ms_per_step=1e3 * el_o / nst_o, steps=nst_o, untimed_steps_before=8,
+                         re_sorts_inside=(nst_o // se if se > 1 else 0), kernel_ms=ko_ms, kernel_ms_median=ko_med)
+            if a.workload == 'c3':
+                other['second_kernel_ms'] = launch_ms(wl.second_kernel)[0]
+            ctx.set_stage_math(a.stage_math)
+
+        # counters of the same command from the committed rocprofv3 passes (profiles/r06_<workload>_pmc[_exact].json, written by
+        # tools/gpu_profile_round.sh + tools/collect_profiles_round.py from this tree): PMC counters cannot be collected from inside
+        # this process.  Used only when they belong to this size and stage math.
+        def load_pmc(mode):
+            for r in ('r06', 'r05', 'r04'):
+                f = os.path.join('profiles', '%s_%s_pmc%s.json' % (r, a.workload, '' if mode == 'fast' else '_' + mode))
+                if os.path.exists(os.path.join(ROOT, f)):
+                    pm = json.load(open(os.path.join(ROOT, f)))
+                    if pm.get('particles') == n and pm.get('stage_math', mode) == mode:
+                        return pm, f
+            return None, None
+        pmc, pmc_file = load_pmc(a.stage_math)
+        pmc_other, pmc_other_file = load_pmc(other_mode)
+        extras = {}
+        if rank == 0 and world == 1 and not a.no_extras and a.workload == 'c3' and not a.small and not a.block_every:
+            # (0) the drop-in surface: OceanDrift.run() on the same inputs, in a context of its own (first of the extra legs: it
+            # came out 20 % slower when it ran after the upload leg below; the bare sequence's context and particles stay open)
+            extras['model_api'] = model_api_leg(fields, n, 48, dev)
+            extras['model_api']['vs_bare_sequence'] = extras['model_api']['ms_per_step'] / (1e3 * el_max / a.steps)
+        if rank == 0 and world == 1 and not a.no_extras and a.workload == 'c3' and not a.block_every and not a.small and \
+                not os.environ.get('ODR_BENCH_SKIP_PCIE'):
+            # (i) PCIe-inclusive: a new reader time level (hourly fields, 10-minute steps) arrives from pinned host memory
+            # every 6 steps on the upload stream inside the timed region
+            pinned = {kk: ctx.pin(np.ascontiguousarray(fields['g'][kk])) for kk in fields['names']}
+            warm_uploads(pinned)
+            nst = 120     # 20 level periods whatever --steps says (20 steps held 4 uploads and no steady state; 48 still read 8 % high)
+            el_p, up = timed_loop(nst, a.warmup, 6, True, pinned)
+            extras['pcie_inclusive'] = dict(ms_per_step=1e3 * el_p / nst, value=up / el_p, unit='particle-steps/s', steps=nst,
+                                            what='one 210 MB time level uploaded every 6 steps (odr_block_upload_async from '
+                                                 'page-locked arrays, committed one period later) inside the timed region')
+            for kk in fields['names']:
+                ctx.unpin(pinned[kk])
+            pinned = None
     if rank == 0:
-        traffic = None if pmc is None else (pmc['FETCH_SIZE_bytes_x2'] + pmc['WRITE_SIZE_bytes']) / 1e9
         out = {
             'metric': {'c3': 'particle-steps/sec (RK4, 3D interp)', 'c2': 'particle-steps/sec (RK4, analytic field)',
                        'c4': 'particle-steps/sec (RK4, 2D interp + wind + Stokes + diffusion)',
@@ -984,61 +993,62 @@ def main():
                        'block_every': a.block_every, 'inputs': 'resident in HBM' if a.block_every <= 0 else 'uploaded in the timed region',
                        'parallelism': 'particle-sharded x%d, field block broadcast once per time level' % world},
         }
-        kname = ('k_step_leeway' if wl.fused else 'k_leeway') if a.workload == 'c5' else ('k_step_grid<RK4>' if kfused else 'k_advect<RK4>')
-        # (1) SURVEY.md 8(d): algorithmic bytes (4 B per field corner touched + state once in / once out) over the launch time.
-        # Counts cache-served corners: a throughput figure in the survey's unit, NOT a physical bandwidth (it can exceed 1).
-        algorithmic = {'bound': 'hbm', 'kernel': kname, 'achieved': ach / 1e9, 'peak': HBM_PEAK / 1e9, 'unit': 'GB/s',
-                       'frac': ach / HBM_PEAK, 'algorithmic_gb_per_launch': kbytes * nact / 1e9,
-                       'algorithmic_bytes_per_particle': kbytes, 'step_bytes_per_particle': BYTES[a.workload]['step'],
-                       'step_frac': BYTES[a.workload]['step'] * (units / el_max) / world / HBM_PEAK,
-                       'note': 'SURVEY 8(d) accounting: counts corners served by L1 / L2 / Infinity Cache; not a physical bandwidth'}
-        out['roofline_algorithmic'] = algorithmic
-        if pmc is not None:
-            # (2) roofline of the dominant kernel: achieved = its HBM bytes per launch from the counters (FETCH_SIZE x 2 +
-            # WRITE_SIZE, MI355X_MICROARCH.md) over the launch time measured HERE with HIP events; peak = 8 TB/s; frac =
-            # achieved / peak -- a fraction of a physical peak, whichever unit binds.  `units` carries the other units of the
-            # launch the same way, achieved / measured peak: L1 lookups per clock per CU against the 2.03 of
-            # tools/gather_bench.hip's `nodes` shape (profiles/r03_gather_bench.txt); VALU issue cycles (every wave64
-            # instruction priced by class as measured by tools/rate_bench.hip: float64 arithmetic / conversions 4,
-            # transcendental float64 16, other 2) against 1 024 SIMDs; and, as a diagnostic only, the share of the launch the
-            # texture addresser reported busy (TA_TA_BUSY: includes the cycles it waits on the caches -- not a roofline).
-            def units_of(q, ms):
-                hb = q['FETCH_SIZE_bytes_x2'] + q['WRITE_SIZE_bytes']
-                clk_ = (q.get('GRBM_GUI_ACTIVE_8xcd') or 0) / 8.0 / (q['kernel_us_rocprof'] * 1e-6) if q.get('GRBM_GUI_ACTIVE_8xcd') else 2.4e9
-                sec = ms * 1e-3
-                return hb, clk_, {
-                    'hbm': hb / sec / HBM_PEAK,
-                    'l1_lookups': (q.get('TCP_TOTAL_CACHE_ACCESSES') or 0) / 256.0 / (clk_ * q['kernel_us_rocprof'] * 1e-6) / 2.03,
-                    'valu_issue': q['valu_cycles_per_simd_slot'] / (1024 * clk_) / sec,
-                    'ta_busy_share_diagnostic': (q.get('TA_TA_BUSY') or 0) / 256.0 / clk_ / sec}
-            hbm_bytes, clk, un = units_of(pmc, k_ms)
-            out['roofline'] = {
-                'bound': 'hbm', 'kernel': kname, 'kernel_ms': k_ms, 'kernel_ms_median': k_ms_median,
-                'achieved': hbm_bytes / (k_ms * 1e-3) / 1e9, 'peak': HBM_PEAK / 1e9, 'unit': 'GB/s', 'frac': un['hbm'],
-                'frac_of_achievable': hbm_bytes / (k_ms * 1e-3) / HBM_ACHIEVABLE, 'achievable': HBM_ACHIEVABLE / 1e9,
-                'traffic': hbm_bytes / 1e9, 'traffic_unit': 'GB of HBM traffic per launch (FETCH_SIZE x 2 + WRITE_SIZE)',
-                'algorithmic_gb_per_launch': kbytes * nact / 1e9,
-                'units': un, 'binding_unit': max((k for k in un if not k.endswith('diagnostic')), key=lambda k: un[k]),
-                'clock_ghz': clk / 1e9,
-                'source': pmc_file + ' (counters of the same command and tree; this line times the launch itself)',
-                'note': 'frac = HBM bytes of the launch (counters) / launch time / 8 TB/s; the SURVEY 8(d) figure is roofline_algorithmic'}
-            if 'second' in pmc and k2_ms is not None:
-                hb2, _, un2 = units_of(pmc['second'], k2_ms)
-                out['roofline']['second_kernel'] = {'kernel': 'k_vmix_col', 'kernel_ms': k2_ms, 'frac': un2['hbm'], 'traffic': hb2 / 1e9,
-                                                    'units': un2}
-            if pmc.get('step_hbm_bytes'):
-                # every kernel of a step (re-sort share included), real HBM bytes over the measured step time
-                sb = pmc['step_hbm_bytes']
-                out['roofline_step'] = {'bound': 'hbm', 'achieved': sb / (el_max / a.steps) / 1e9,
-                                        'peak': HBM_PEAK / 1e9, 'unit': 'GB/s', 'frac': sb / (el_max / a.steps) / HBM_PEAK,
-                                        'frac_of_achievable': sb / (el_max / a.steps) / HBM_ACHIEVABLE,
-                                        'traffic': sb / 1e9, 'kernels': pmc.get('step_hbm_kernels'),
-                                        'note': 'HBM bytes of ALL kernels of one step (counters, calls per step from the kernel trace) / ms_per_step / 8 TB/s'}
-        else:
-            out['roofline'] = dict(algorithmic, kernel_ms=k_ms, kernel_ms_median=k_ms_median, traffic=None,
-                                   note='no counter file for this size / stage math: the SURVEY 8(d) algorithmic figure only')
-            if k2_ms is not None:
-                out['roofline']['second_kernel'] = {'kernel': 'k_vmix_col', 'kernel_ms': k2_ms}
+        if a.full:
+            kname = ('k_step_leeway' if wl.fused else 'k_leeway') if a.workload == 'c5' else ('k_step_grid<RK4>' if kfused else 'k_advect<RK4>')
+            # (1) SURVEY.md 8(d): algorithmic bytes (4 B per field corner touched + state once in / once out) over the launch time.
+            # Counts cache-served corners: a throughput figure in the survey's unit, NOT a physical bandwidth (it can exceed 1).
+            algorithmic = {'bound': 'hbm', 'kernel': kname, 'achieved': ach / 1e9, 'peak': HBM_PEAK / 1e9, 'unit': 'GB/s',
+                           'frac': ach / HBM_PEAK, 'algorithmic_gb_per_launch': kbytes * nact / 1e9,
+                           'algorithmic_bytes_per_particle': kbytes, 'step_bytes_per_particle': BYTES[a.workload]['step'],
+                           'step_frac': BYTES[a.workload]['step'] * (units / el_max) / world / HBM_PEAK,
+                           'note': 'SURVEY 8(d) accounting: counts corners served by L1 / L2 / Infinity Cache; not a physical bandwidth'}
+            out['roofline_algorithmic'] = algorithmic
+            if pmc is not None:
+                # (2) roofline of the dominant kernel: achieved = its HBM bytes per launch from the counters (FETCH_SIZE x 2 +
+                # WRITE_SIZE, MI355X_MICROARCH.md) over the launch time measured HERE with HIP events; peak = 8 TB/s; frac =
+                # achieved / peak -- a fraction of a physical peak, whichever unit binds.  `units` carries the other units of the
+                # launch the same way, achieved / measured peak: L1 lookups per clock per CU against the 2.03 of
+                # tools/gather_bench.hip's `nodes` shape (profiles/r03_gather_bench.txt); VALU issue cycles (every wave64
+                # instruction priced by class as measured by tools/rate_bench.hip: float64 arithmetic / conversions 4,
+                # transcendental float64 16, other 2) against 1 024 SIMDs; and, as a diagnostic only, the share of the launch the
+                # texture addresser reported busy (TA_TA_BUSY: includes the cycles it waits on the caches -- not a roofline).
+                def units_of(q, ms):
+                    hb = q['FETCH_SIZE_bytes_x2'] + q['WRITE_SIZE_bytes']
+                    clk_ = (q.get('GRBM_GUI_ACTIVE_8xcd') or 0) / 8.0 / (q['kernel_us_rocprof'] * 1e-6) if q.get('GRBM_GUI_ACTIVE_8xcd') else 2.4e9
+                    sec = ms * 1e-3
+                    return hb, clk_, {
+                        'hbm': hb / sec / HBM_PEAK,
+                        'l1_lookups': (q.get('TCP_TOTAL_CACHE_ACCESSES') or 0) / 256.0 / (clk_ * q['kernel_us_rocprof'] * 1e-6) / 2.03,
+                        'valu_issue': q['valu_cycles_per_simd_slot'] / (1024 * clk_) / sec,
+                        'ta_busy_share_diagnostic': (q.get('TA_TA_BUSY') or 0) / 256.0 / clk_ / sec}
+                hbm_bytes, clk, un = units_of(pmc, k_ms)
+                out['roofline'] = {
+                    'bound': 'hbm', 'kernel': kname, 'kernel_ms': k_ms, 'kernel_ms_median': k_ms_median,
+                    'achieved': hbm_bytes / (k_ms * 1e-3) / 1e9, 'peak': HBM_PEAK / 1e9, 'unit': 'GB/s', 'frac': un['hbm'],
+                    'frac_of_achievable': hbm_bytes / (k_ms * 1e-3) / HBM_ACHIEVABLE, 'achievable': HBM_ACHIEVABLE / 1e9,
+                    'traffic': hbm_bytes / 1e9, 'traffic_unit': 'GB of HBM traffic per launch (FETCH_SIZE x 2 + WRITE_SIZE)',
+                    'algorithmic_gb_per_launch': kbytes * nact / 1e9,
+                    'units': un, 'binding_unit': max((k for k in un if not k.endswith('diagnostic')), key=lambda k: un[k]),
+                    'clock_ghz': clk / 1e9,
+                    'source': pmc_file + ' (counters of the same command and tree; this line times the launch itself)',
+                    'note': 'frac = HBM bytes of the launch (counters) / launch time / 8 TB/s; the SURVEY 8(d) figure is roofline_algorithmic'}
+                if 'second' in pmc and k2_ms is not None:
+                    hb2, _, un2 = units_of(pmc['second'], k2_ms)
+                    out['roofline']['second_kernel'] = {'kernel': 'k_vmix_col', 'kernel_ms': k2_ms, 'frac': un2['hbm'], 'traffic': hb2 / 1e9,
+                                                        'units': un2}
+                if pmc.get('step_hbm_bytes'):
+                    # every kernel of a step (re-sort share included), real HBM bytes over the measured step time
+                    sb = pmc['step_hbm_bytes']
+                    out['roofline_step'] = {'bound': 'hbm', 'achieved': sb / (el_max / a.steps) / 1e9,
+                                            'peak': HBM_PEAK / 1e9, 'unit': 'GB/s', 'frac': sb / (el_max / a.steps) / HBM_PEAK,
+                                            'frac_of_achievable': sb / (el_max / a.steps) / HBM_ACHIEVABLE,
+                                            'traffic': sb / 1e9, 'kernels': pmc.get('step_hbm_kernels'),
+                                            'note': 'HBM bytes of ALL kernels of one step (counters, calls per step from the kernel trace) / ms_per_step / 8 TB/s'}
+            else:
+                out['roofline'] = dict(algorithmic, kernel_ms=k_ms, kernel_ms_median=k_ms_median, traffic=None,
+                                       note='no counter file for this size / stage math: the SURVEY 8(d) algorithmic figure only')
+                if k2_ms is not None:
+                    out['roofline']['second_kernel'] = {'kernel': 'k_vmix_col', 'kernel_ms': k2_ms}
         out['comm'] = D.comm_info()     # which layer carried the collectives and how many ranks IT saw (N > 1: RCCL through the C ABI)
         out['torch_in_process'] = 'torch' in sys.modules
         if sharded_report is not None:
@@ -1046,7 +1056,7 @@ def main():
                                        '(odr_scan_status) and ONE all_gather of the step summaries; every block_every steps a reader level '
                                        'from rank 0, staged one period ahead (C-ABI collectives: odr_block_broadcast, ONE RCCL broadcast inside '
                                        'the upload pipeline; torch layer: broadcast into tensors -> odr_block_upload_device)')
-        if a.workload in ('c3', 'c4'):
+        if a.full and a.workload in ('c3', 'c4'):
             ts = P.tile_stats()     # the LDS-tile step (csrc/odr_tile.hip.h): launches on that path / elements it handed to the HBM path
             out['lds_tile'] = dict(ts, handed_over_per_launch=(ts['handed_over'] / ts['launches'] if ts['launches'] else None))
         if other is not None:
@@ -1062,7 +1072,7 @@ def main():
                                      'frac_of_achievable': hb_o / (other['kernel_ms'] * 1e-3) / HBM_ACHIEVABLE, 'source': src_f}
             out['stage_math_' + other_mode] = other
         out.update(extras)
-        if not a.no_cpu and world == 1:
+        if a.full and not a.no_cpu and world == 1:
             out['cpu_baseline'] = cpu_baseline(a.workload, fields, a.cpu_particles, np.random.default_rng(5), small=a.small)
             refs = [os.path.join(ROOT, 'profiles', '%s_cpu_reference_numpy.json' % r) for r in ('r06', 'r02')]   # newest first
             ref = next((f for f in refs if os.path.exists(f)), refs[-1])

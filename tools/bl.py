@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Compact view of a bench.py JSON line on stdin:  python bench.py ... | tail -1 | python tools/bl.py [tag]"""
+"""Compact view of a bench.py JSON line on stdin:  python bench.py --full ... | tail -1 | python tools/bl.py [tag]"""
 import json
 import sys
 

@@ -118,11 +118,11 @@ for w in ('c3', 'c4', 'c5'):
             total += byt
         out['step_hbm_bytes'] = total
         out['step_hbm_kernels'] = {k: round(v / 1e6, 1) for k, v in sorted(per_step.items(), key=lambda kv: -kv[1])[:8]}
-    out['note'] = ('rocprofv3 per-launch averages of `bench.py --workload %s --steps 6 --warmup 2 --no-cpu --no-extras` (stage math %s), '
+    out['note'] = ('rocprofv3 per-launch averages of `bench.py --workload %s --steps 6 --warmup 2 --full --no-cpu --no-extras` (stage math %s), '
                    'one --pmc pass per counter set; FETCH_SIZE doubled as MI355X_MICROARCH.md prescribes for gfx950; see '
                    'profiles/%s_%s_pmc%s.txt' % (w, SM, R, w, SFX))
     hdr = ('PMC counters of the %s bench (per dispatch, summed over dimensions; avg over the dispatches of a kernel), MI355X, stage math %s:\n'
-           'rocprofv3 --kernel-trace --pmc <set> -- python bench.py --workload %s --steps 6 --warmup 2 --no-cpu --no-extras\n'
+           'rocprofv3 --kernel-trace --pmc <set> -- python bench.py --workload %s --steps 6 --warmup 2 --full --no-cpu --no-extras\n'
            'one pass per set (tools/gpu_profile_round.sh).  FETCH_SIZE / WRITE_SIZE in KiB per dispatch; SQ cycle counters in quad-cycles\n'
            'summed over waves; GRBM_GUI_ACTIVE summed over the 8 XCDs.  FETCH_SIZE calibration on k_sort_hist (16 B per particle): %s\n'
            % (w, SM, w, ('%.3f' % calib) if calib else 'n/a'))

@@ -4,7 +4,7 @@
 #
 #   tools/gpu_ab.sh OUT [-t "pytest args"] [-w workload] [-s steps] [-b "extra bench args"] RUN [RUN ...]
 #
-# RUN = name[,VAR=VALUE...]: one `bench.py --workload W --steps S --no-cpu --no-extras` with those variables set (ODR_LIB=tools/_libX.so
+# RUN = name[,VAR=VALUE...]: one `bench.py --workload W --steps S --full --no-cpu --no-extras` with those variables set (ODR_LIB=tools/_libX.so
 # selects a variant library built by tools/vbuild.sh X <flags>); runs execute in the order given -- list a pair twice (A B A B) to see
 # the box's drift.  Every run's JSON line lands in gpurun_out/OUT/<name>.json, one summary line per run is printed.
 cd $GRAFT_REPO_ROOT
@@ -26,7 +26,7 @@ for run in "$@"; do
   name=${run%%,*}
   vars=""
   if [ "$run" != "$name" ]; then vars=$(echo "${run#*,}" | tr ',' ' '); fi
-  env ODR_BENCH_ONE_MODE=${ODR_BENCH_ONE_MODE-1} $vars timeout 900 python bench.py --workload $W --steps $S --no-cpu --no-extras $B > $OUT/${k}_$name.log 2>&1
+  env ODR_BENCH_ONE_MODE=${ODR_BENCH_ONE_MODE-1} $vars timeout 900 python bench.py --workload $W --steps $S --full --no-cpu --no-extras $B > $OUT/${k}_$name.log 2>&1
   grep "^{" $OUT/${k}_$name.log | tail -1 > $OUT/${k}_$name.json
   python - "$OUT/${k}_$name.json" "$name" <<'PY'
 import json, sys

@@ -6,6 +6,7 @@
 #   Every rocprofv3 pass runs under `timeout`: a counter set rocprofv3 chokes on must not eat the round's GPU minutes.
 R=${R:-r06}
 SFX=""; [ "${ODR_STAGE_MATH:-fast}" = exact ] && SFX=_exact
+BENCH=$(cd "$(dirname "$0")/.." && pwd)/bench.py   # (resolved before the cd below)
 P=$GRAFT_REPO_ROOT/gpurun_out/prof_$R$SFX
 mkdir -p $P
 cd /tmp && export TMPDIR=/tmp
@@ -19,14 +20,14 @@ SETS=(
  "GRBM_GUI_ACTIVE TA_TA_BUSY_sum TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCC_HIT_sum TCC_MISS_sum SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES"
 )
 for w in ${@:-c3 c4 c5}; do
-  timeout 300 rocprofv3 --kernel-trace --stats -d $P/stats_$w -o st -- python $GRAFT_REPO_ROOT/bench.py --workload $w --steps 32 --warmup 3 --no-cpu --no-extras > $P/bench_$w.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats -d $P/stats_$w -o st -- python $BENCH --workload $w --steps 32 --warmup 3 --full --no-cpu --no-extras > $P/bench_$w.log 2>&1
   python $GRAFT_REPO_ROOT/tools/rocpd_summary.py $P/stats_$w $P/${R}_${w}_kernel_stats.txt > /dev/null
   rm -rf $P/stats_$w
   rm -f $P/${R}_${w}_pmc_raw.txt
   k=0
   for set in "${SETS[@]}"; do
     k=$((k+1))
-    timeout 200 rocprofv3 --kernel-trace --pmc $set -d $P/pmc_${w}_$k -o pmc -- python $GRAFT_REPO_ROOT/bench.py --workload $w --steps 6 --warmup 2 --no-cpu --no-extras > /dev/null 2>&1
+    timeout 200 rocprofv3 --kernel-trace --pmc $set -d $P/pmc_${w}_$k -o pmc -- python $BENCH --workload $w --steps 6 --warmup 2 --full --no-cpu --no-extras > /dev/null 2>&1
     python $GRAFT_REPO_ROOT/tools/rocpd_summary.py $P/pmc_${w}_$k | grep -E "n=" | grep -E "k_step_grid|k_step_tile|k_step_list|k_vmix_col|k_step_leeway|k_leeway|k_env_grid|k_gather_perm|k_sort_hist|k_sort_perm|k_reduce|k_movers|k_cmp_|k_wg_|k_scan_|k_red_init" >> $P/${R}_${w}_pmc_raw.txt
     rm -rf $P/pmc_${w}_$k
   done
