@@ -513,10 +513,14 @@ int odr_sort_particles_ex(odr_ctx *ctx, odr_particles *p, int32_t source_id, int
  * Synchronises the context's stream. */
 int odr_particles_tile_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out4);
 /* The fused step launch of odr_env_coast_advect (csrc/odr_kernels.hip.h k_step_grid) since the set was created:
- * out2 = {launches that read the group's slot layout from its descriptors at run time, launches of an instantiation whose
- *         layout is a compile-time constant (the C3 group under ODR_STAGE_FAST: csrc/odr_field.hip.h LayoutC3)}.
+ * out2 = {launches other than those of the C3 group's two-level static layout (the run-time layout, and the on-level
+ *         static layout counted by odr_particles_step_onlevel_stats), launches of the instantiation whose layout is the
+ *         C3 group between two time levels as compile-time constants (under ODR_STAGE_FAST: csrc/odr_field.hip.h LayoutC3)}.
  * The environment variable ODR_NO_LAYOUT_SPEC=1 keeps every launch on the run-time layout. */
 int odr_particles_step_layout_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out2);
+/* The launches of the same kernel with the C3 group's static layout on a step whose time sits on a reader level
+ * (csrc/odr_field.hip.h LayoutC3L1) since the set was created: out1 = {launches}.  They are part of out2[0] above. */
+int odr_particles_step_onlevel_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out1);
 /* The mixing launches of odr_vmix since the set was created:
  * out3 = {launches of the K-column kernel (csrc/odr_kernels.hip.h k_vmix_col) that read its configuration at run time, launches
  *         of its instantiation for C3's configuration as compile-time constants (VMixC3), launches of the other mixing kernels

@@ -1740,8 +1740,9 @@ enum { ENV_S2 = 0, ENV_S3 = 1, ENV_S3I = 2, ENV_P2 = 3, ENV_P3 = 4, ENV_LAND = 5
 // index maps, the gather modes, the Kelvin and rotation flags and the static-slot bits fold away (select chains over MAXG,
 // mode branches, scalar loads of the descriptors).  The host launches a static layout only when the group it built is
 // exactly that layout (layout_matches), otherwise LayoutRT; the arithmetic and its rounding points are the same.
+// ONE_LEVEL: the sample sits on a time level (see LayoutC3L1); false for the layouts that read G.ba.
 struct LayoutRT {
-  static constexpr bool STATIC = false;
+  static constexpr bool STATIC = false, ONE_LEVEL = false;
   __host__ __device__ static int nv_of(const EnvGroupDesc &G) { return G.nv; }
   __host__ __device__ static int offA_of(const EnvGroupDesc &G) { return G.ps_off[0]; }
 };
@@ -1750,9 +1751,22 @@ struct LayoutRT {
 // the same at both time levels (content ids); no Kelvin conversion; a lat / lon reader (no rotation); ssh is not in the
 // group (p.env[ssh])
 struct LayoutC3 {
-  static constexpr bool STATIC = true;
+  static constexpr bool STATIC = true, ONE_LEVEL = false;
   static constexpr int nv = 5, kA = 0, kB = 4, kC = 3, kD = -1, kL = 2;
   static constexpr int mA = ENV_P3, mB = ENV_S3, mC = ENV_S2, offA = 0, ps_static = 4 | 16;
+  static constexpr int land_slot = 2, depth_slot = 3, ssh_slot = -1;
+  __host__ __device__ static constexpr int nv_of(const EnvGroupDesc &) { return nv; }
+  __host__ __device__ static constexpr int offA_of(const EnvGroupDesc &) { return offA; }
+};
+// The same group on a step whose time sits on a reader level (G.ba == nullptr: one C3 step in six).  The sample has one
+// level: slots B, C and L are gathered once, and no time interpolation is compiled in (ps_static is 0 on a level, and does
+// not matter).  Slot A is gathered at both levels of the half-step stages' bracket (th.b = the sample's level, th.a = the
+// level after, handed in by the step launch): the sample reads th.b's records, the stage samples keep both combined over the
+// vertical bracket, as on the steps between two levels -- instead of fetching the footprint again in stage 1.
+struct LayoutC3L1 {
+  static constexpr bool STATIC = true, ONE_LEVEL = true;
+  static constexpr int nv = 5, kA = 0, kB = 4, kC = 3, kD = -1, kL = 2;
+  static constexpr int mA = ENV_P3, mB = ENV_S3, mC = ENV_S2, offA = 0, ps_static = 0;
   static constexpr int land_slot = 2, depth_slot = 3, ssh_slot = -1;
   __host__ __device__ static constexpr int nv_of(const EnvGroupDesc &) { return nv; }
   __host__ __device__ static constexpr int offA_of(const EnvGroupDesc &) { return offA; }
@@ -1861,6 +1875,9 @@ template <int PROJ, class LY, class LD>
 __device__ __forceinline__ void env_burst(const DevSource &s, const EnvGroupDesc &G, const LD &L, const Foot &ft, const ZBracket &zb,
                                           unsigned near_off, bool tl, double x, double y, float *out /*[MAXG]*/, EnvExport *X ODR_PT_PARAM) {
   constexpr bool ST = LY::STATIC;
+  // L1: the sample sits on a level (LayoutC3L1; tl is false): slots B, C, D and L are gathered at time 0 only.  L's time 1
+  // is then the level after the stages' bracket, which only slot A's gathers read (the stage samples' kept records).
+  constexpr bool L1 = LY::ONE_LEVEL;
   const unsigned o[4] = {ft.o00, ft.o01, ft.o10, ft.o11};
   const unsigned iz0 = (unsigned)zb.iz0;
   int kA, kB, kC, kD, kL, mA, mB, mC, temp_mask, ps_static, offA;
@@ -1910,13 +1927,16 @@ __device__ __forceinline__ void env_burst(const DevSource &s, const EnvGroupDesc
     // condition that also guards its arithmetic lets the compiler merge the two blocks -- gathers, wait, arithmetic, slot by
     // slot -- 1.26 -> 1.45 ms per step; a zero-length buffer descriptor for empty slots 1.26 -> 1.31)
 #pragma unroll
-    for (int c = 0; c < 4; ++c) { Bb[c] = L.template ld<F2>(0, o[c] + dB); Ba[c] = L.template ld<F2>(1, o[c] + dB); }
+    for (int c = 0; c < 4; ++c) {
+      Bb[c] = L.template ld<F2>(0, o[c] + dB);
+      if constexpr (L1) Ba[c] = Bb[c]; else Ba[c] = L.template ld<F2>(1, o[c] + dB);
+    }
     // (a slot whose variable holds the same values at both time levels -- ps_static, from the blocks' content ids -- is
     // gathered once: four 32-cycle gathers less; the copies sit behind the slot's own last load, where the arithmetic
     // waits anyway)
 #pragma unroll
     for (int c = 0; c < 4; ++c) Cb[c] = L.template ld<F2>(0, o[c] + dC);
-    if (ps_static & 4) {
+    if (L1 || (ps_static & 4)) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) Ca[c] = Cb[c];
     } else {
@@ -1925,7 +1945,7 @@ __device__ __forceinline__ void env_burst(const DevSource &s, const EnvGroupDesc
     }
 #pragma unroll
     for (int c = 0; c < 4; ++c) Db[c] = L.template ld<float>(0, o[c] + dD);
-    if (ps_static & 8) {
+    if (L1 || (ps_static & 8)) {
 #pragma unroll
       for (int c = 0; c < 4; ++c) Da[c] = Db[c];
     } else {
@@ -1979,7 +1999,7 @@ __device__ __forceinline__ void env_burst(const DevSource &s, const EnvGroupDesc
     }
     const float Lb = L.template ld<float>(0, dL);
     float La;
-    if (ps_static & 16) La = Lb; else La = L.template ld<float>(1, dL);   // same values at both levels: one gather less
+    if (L1 || (ps_static & 16)) La = Lb; else La = L.template ld<float>(1, dL);   // same values at both levels: one gather less
     if (kA >= 0) {
       double v0, v1;
       burst_math<4>(mA, [&](int t, int c, int q) { const F4 &r = t ? Aa[c] : Ab[c]; return q == 0 ? r.x : q == 1 ? r.y : q == 2 ? r.z : r.w; },
@@ -2067,7 +2087,7 @@ __device__ __forceinline__ bool env_group_sample(const DevWorld &W, const EnvGro
                         (fr.f32idx & 1) ? nearest_index_f32(x, geo.xmin, geo.xrange, geo.nx) : nearest_index(x, geo.xmin, geo.xrange, geo.ixrange, geo.nx),
                         geo.nx, rec_bytes, ok_near);
     if (!(ok && ok_near)) return false;
-    const bool tl = G.ba != nullptr && !G.all_static;
+    const bool tl = !LY::ONE_LEVEL && G.ba != nullptr && !G.all_static;
     ODR_PT_USE(ft.o00); ODR_PT_USE(ft.o11); ODR_PT_USE(near_off); ODR_PT(14);
     if (burst) env_burst<PROJ, LY>(s, G, L, ft, zb, near_off, tl, x, y, out, X ODR_PT_ARG);
     else if constexpr (!BURST_ONLY) {
@@ -2142,14 +2162,18 @@ __device__ __forceinline__ LdGlobal env_global(const EnvGroupDesc &G) {
   return g;
 }
 // front door + sample from the blocks in HBM
+// ua (LY::ONE_LEVEL): slot A's (u, v) array at the level after the half-step stages' bracket (th.a), which slot A's time-1
+// gathers read; its record base is ua - LY::offA
 template <int PROJ, bool BURST_ONLY, bool ZT, class LY = LayoutRT>
 __device__ __forceinline__ void env_group_fast(const DevWorld &W, const EnvGroupDesc &G, double lon,
                                                double lat, double z, float *out /*[MAXG]*/, const double *zt,
                                                ZBracket &zb_out, EnvExport *X = nullptr ODR_PT_PARAM, int f32idx = 0,
-                                               const ProjStart ps = ProjStart()) {
+                                               const ProjStart ps = ProjStart(), const float *ua = nullptr) {
   const DevSource &s = W.src[G.sid];
   const EnvFront fr = env_front<PROJ>(s, s.slot[G.geo_slot], lon, lat, z, f32idx, ps);
-  env_group_sample<PROJ, BURST_ONLY, ZT, LY>(W, G, env_global(G), fr, z, out, zt, zb_out, X ODR_PT_ARG);
+  LdGlobal L = env_global(G);
+  if constexpr (LY::ONE_LEVEL) L.a = (const float *)((const char *)ua - LY::offA);
+  env_group_sample<PROJ, BURST_ONLY, ZT, LY>(W, G, L, fr, z, out, zt, zb_out, X ODR_PT_ARG);
 }
 // The records the main-loop sample fetched for slot A, as the kept footprint of the stage samples -- valid when slot A holds
 // the current (an interleaved pair of the stage samples' dimensionality) and the sample's time bracket is that of the
@@ -2182,12 +2206,13 @@ __device__ __forceinline__ UVKeep<IS3D> uv_keep_from_sm(const EnvGroupDesc &G, c
     const bool tl = G.ba != nullptr && !G.all_static;
     const int offA = LY::offA_of(G);
     const float *mb = (const float *)((const char *)G.bb + offA);
-    const float *ma = tl ? (const float *)((const char *)G.ba + offA) : nullptr;
+    // (LY::ONE_LEVEL: the burst gathered slot A's time 1 at th.a itself, env_group_fast)
+    const float *ma = LY::ONE_LEVEL ? th.a : tl ? (const float *)((const char *)G.ba + offA) : nullptr;
     const bool fits = (LY::STATIC || (G.bs[0] == 0 && G.var[0] == VAR_U && G.ps_mode[0] == ENV_P3)) && mb == th.b && ma == th.a;
     K.valid = fits && X.valid && z_unchanged;
     K.n00 = X.n00; K.n11 = X.n11; K.kb = (unsigned)X.iz0 * 8u;
     // X.combine: the burst already combined the corners over the bracket (time level `a` = `b` when the sample is on a level:
-    // the loader reads the same records for both)
+    // the loader reads the same records for both -- except under LY::ONE_LEVEL, whose time 1 is th.a)
 #pragma unroll
     for (int c = 0; c < 4; ++c) { K.q.b[c].x = X.b[4 * c]; K.q.b[c].y = X.b[4 * c + 1]; K.q.b[c].z = X.b[4 * c + 2]; K.q.b[c].w = X.b[4 * c + 3]; }
     return K;

@@ -176,7 +176,7 @@ struct odr_particles {
   unsigned long long *wg_total, *wg_stats;   // device: wg_total[0] table length, [1] length of wg_list; wg_stats = wg_total + 2: [0] sum of the list lengths, [1] rectangles cut
   long long wg_cap, wg_grid, wg_n, wg_list_cap;
   unsigned long long wg_launches;            // host: launches that took the LDS-tile path
-  unsigned long long step_launches[2];       // host: k_step_grid launches with the run-time slot layout [0], a static one [1]
+  unsigned long long step_launches[3];       // host: k_step_grid launches other than LayoutC3 [0], of LayoutC3 [1], of LayoutC3L1 [2] (also in [0])
   unsigned long long vmix_launches[3];       // host: odr_vmix launches of k_vmix_col with the run-time configuration [0], a static one [1], of the other mixing kernels [2]
   double *z_keep;       // odr_particles_truncate_z: the elements' own z while the sampling calls see the clipped one
   long long z_keep_n;

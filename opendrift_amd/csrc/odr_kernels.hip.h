@@ -1024,7 +1024,7 @@ struct StepDesc {
 #endif
 #define ODR_PARK_WAVES_OF(PROJ, IS3D, SM) (((PROJ) == PROJ_LATLONG && (IS3D) && (SM) == 1) ? ODR_PARK_WAVES_FAST3D : ODR_PARK_WAVES)
 #define ODR_STEP_PARKS(SCHEME, PROJ) ((SCHEME) > 0 && ((PROJ) == PROJ_LATLONG || (PROJ) == PROJ_CURVILINEAR))
-// LY: the slot layout of the group and of the bookkeeping below (odr_field.hip.h LayoutRT / LayoutC3)
+// LY: the slot layout of the group and of the bookkeeping below (odr_field.hip.h LayoutRT / LayoutC3 / LayoutC3L1)
 template <int SCHEME, int PROJ, bool IS3D, bool NOISE, int SM = 0, class LY = LayoutRT>
 __global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ) ? ODR_PARK_WAVES_OF(PROJ, IS3D, SM) : ODR_STEP_WAVES(PROJ)) void k_step_grid(const DevWorld *__restrict__ W, PView p, EnvGroupDesc G,
                                                      StepDesc S, double dt, float factor, UVTime th, UVTime tf,
@@ -1084,7 +1084,7 @@ __global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ) ? ODR_PARK_WAVE
       else if (s0.lon_mode == 2) lw = np_mod(lw, 360.0);
       ps0 = proj_start(s0.proj, lw, lat);
     }
-    env_group_fast<PROJ, true, IS3D, LY>(*W, G, lon, lat, z, out, zt, zb_env, &X ODR_PT_ARG, 0, ps0);
+    env_group_fast<PROJ, true, IS3D, LY>(*W, G, lon, lat, z, out, zt, zb_env, &X ODR_PT_ARG, 0, ps0, th.a);
     UVKeep<IS3D> K = uv_keep_from_sm<IS3D, SM, LY>(G, X, th, zb_env, W->src[G.sid].nz, true);   // (FAST, 3-D: combined over the bracket's levels)
     if constexpr (STATE_LATE) load_state();
     ODR_PT_USE(out[0]); ODR_PT_USE(out[1]); ODR_PT_USE(out[2]); ODR_PT_USE(out[3]); ODR_PT_USE(out[4]); ODR_PT(2);

@@ -269,3 +269,9 @@ int odr_particles_step_layout_stats(odr_ctx *c, odr_particles *p, uint64_t *out2
   out2[0] = p->step_launches[0]; out2[1] = p->step_launches[1];
   return 0;
 }
+
+int odr_particles_step_onlevel_stats(odr_ctx *c, odr_particles *p, uint64_t *out1) {
+  REQUIRE(c && p && out1, "NULL argument");
+  out1[0] = p->step_launches[2];
+  return 0;
+}

@@ -66,6 +66,20 @@ static bool layout_matches(const EnvGroupDesc &G, const StepDesc &S) {
          G.ps_mode[2] == LY::mC && G.ps_off[0] == LY::offA && G.ps_static == LY::ps_static && G.temp_mask == 0 &&
          S.land_slot == LY::land_slot && S.depth_slot == LY::depth_slot && S.ssh_slot == LY::ssh_slot;
 }
+// LayoutC3L1: the C3 group on a step whose time sits on a reader level, and half-step stages between that level (th.b) and
+// the next (th.a), whose records slot A's time-1 gathers read (env_group_fast).  The step is forward in time: a backward
+// step's stages lie before the level, th.b is another level than the sample's.
+static bool layout_matches_onlevel(const DevSource &s, const EnvGroupDesc &G, const StepDesc &S, double t, double dt,
+                                   const UVTime &th) {
+  typedef LayoutC3L1 LY;
+  if (!(layout_matches<LY>(G, S) && G.ba == nullptr && !G.all_static && th.a != nullptr &&
+        th.b == (const float *)((const char *)G.bb + LY::offA)))
+    return false;
+  int ib, ia;
+  host_bracket(s, t + dt / 2, ib, ia);    // the level th.a is (uv_time)
+  return ia >= 0 && th.a == (const float *)((const char *)s.slot[ia].base + LY::offA) && s.slot[ia].small &&
+         s.slot[ia].rec == s.slot[ib].rec;
+}
 
 // get_environment -> interact_with_coastline -> update_previous_state -> advect_ocean_current in
 // one launch (k_step_grid) when the current comes from one gridded reader; otherwise exactly the
@@ -82,14 +96,23 @@ static void launch_step_grid(odr_ctx *c, odr_particles *p, const EnvGroupDesc &G
   dim3 g(nblk(p->n)), b(BLOCK);
   PView v = view(p);
   float f = (float)factor;
-  // the C3 group under the FAST stage arithmetic: its layout as compile-time constants (ODR_NO_LAYOUT_SPEC=1: the run-time
-  // layout, for A/B runs and tests)
+  // the C3 group under the FAST stage arithmetic: its layout as compile-time constants, between two levels (LayoutC3) and on a
+  // level (LayoutC3L1) (ODR_NO_LAYOUT_SPEC=1: the run-time layout, for A/B runs and tests)
   if constexpr (SCHEME == 2 && !NOISE && SM == 1) {
-    if (odr_proj_template(s.proj) == PROJ_LATLONG && is3d && layout_matches<LayoutC3>(G, S) && !getenv("ODR_NO_LAYOUT_SPEC")) {
-      hipLaunchKernelGGL((k_step_grid<SCHEME, PROJ_LATLONG, true, NOISE, SM, LayoutC3>), g, b, 0, c->stream, c->dw, v, G, S,
-                         dt, f, th, tf, c->counter, N);
-      p->step_launches[1]++;
-      return;
+    if (odr_proj_template(s.proj) == PROJ_LATLONG && is3d && !getenv("ODR_NO_LAYOUT_SPEC")) {
+      if (layout_matches<LayoutC3>(G, S)) {
+        hipLaunchKernelGGL((k_step_grid<SCHEME, PROJ_LATLONG, true, NOISE, SM, LayoutC3>), g, b, 0, c->stream, c->dw, v, G, S,
+                           dt, f, th, tf, c->counter, N);
+        p->step_launches[1]++;
+        return;
+      }
+      if (layout_matches_onlevel(s, G, S, t, dt, th)) {
+        hipLaunchKernelGGL((k_step_grid<SCHEME, PROJ_LATLONG, true, NOISE, SM, LayoutC3L1>), g, b, 0, c->stream, c->dw, v, G, S,
+                           dt, f, th, tf, c->counter, N);
+        p->step_launches[0]++;   // (counted with the run-time layout: odr_particles_step_layout_stats)
+        p->step_launches[2]++;
+        return;
+      }
     }
   }
   p->step_launches[0]++;

@@ -902,12 +902,21 @@ class Particles:
         return dict(launches=int(out[0]), handed_over=int(out[1]), rectangles_cut=int(out[2]), ranges=int(out[3]))
 
     def step_layout_stats(self):
-        """Launches of the fused step kernel (odr_particles_step_layout_stats): with the run-time slot layout, with a
-        compile-time one."""
+        """Launches of the fused step kernel (odr_particles_step_layout_stats): `static` with the C3 group's compile-time
+        layout between two time levels, `runtime` all others (the run-time slot layout, and the on-level static layout
+        that step_onlevel_stats counts on its own)."""
         import ctypes as C
         out = (C.c_uint64 * 2)()
         check(self.lib.odr_particles_step_layout_stats(self.ctx.h, self.h, out))
         return dict(runtime=int(out[0]), static=int(out[1]))
+
+    def step_onlevel_stats(self):
+        """Launches of the fused step kernel with the C3 group's compile-time layout on a step whose time sits on a reader
+        level (odr_particles_step_onlevel_stats)."""
+        import ctypes as C
+        out = (C.c_uint64 * 1)()
+        check(self.lib.odr_particles_step_onlevel_stats(self.ctx.h, self.h, out))
+        return int(out[0])
 
     def vmix_layout_stats(self):
         """Launches of the mixing kernels (odr_particles_vmix_layout_stats): the K-column kernel with the run-time configuration,
