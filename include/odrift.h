@@ -419,6 +419,13 @@ int odr_oil_mixing_stats(odr_ctx *ctx, double *mean_zb, double *dv50);
 int odr_oil_local_sums(odr_ctx *ctx, odr_particles *p, double interfacial_tension, double sea_water_density,
                        int droplet_distribution, int hs_mode, double *sum_dv50, double *sum_zb);
 int odr_oil_set_mixing_stats(odr_ctx *ctx, double mean_zb, double dv50);
+/* PelagicEggDrift.update_terminal_velocity (models/pelagicegg.py:100-179; Sundby 1983): elements.terminal_velocity of every
+ * active element from the sampled float32 sea_water_temperature / sea_water_salinity and two float32 property slots (egg
+ * diameter [m], salinity of neutral buoyancy) -- Stokes' law, Dallavalle's empirical form where Re > 0.5, in the reference's
+ * float32 operation order (csrc/odr_egg.hip.h).  ODR_ERR_STATE when temperature or salinity have not been sampled or a slot has
+ * not been set.  Enqueued on the context's stream; no host synchronisation. */
+enum { ODR_EGG_DIAMETER = 0, ODR_EGG_NEUTRAL_BUOYANCY_SALINITY = 1, ODR_EGG_DENSITY = 2, ODR_EGG_HATCHED = 3 };
+int odr_egg_terminal_velocity(odr_ctx *ctx, odr_particles *p, int diameter_slot, int salinity_slot);
 /* performance hint: apply vertical_advection (oceandrift.py:315-350) inside the next odr_vmix
  * kernel (OceanDrift.update() calls them back to back, oceandrift.py:201-208) */
 int odr_vmix_fuse_vertical_advection(odr_ctx *ctx, int at_surface);

@@ -17,6 +17,7 @@
 //
 // Included by odr_kernels.hip.h (needs PView, speed_f32, rng_init).
 #pragma once
+#include "odr_seawater.hip.h"
 
 namespace odr {
 
@@ -43,34 +44,9 @@ struct OilArgs {
   const double *stat;      // OIL_STAT_*
 };
 
-// ---- float32 chains (Python float constants are cast to float32, no contraction)
+// ---- float32 chains (Python float constants are cast to float32, no contraction); oil_sea_water_density_f32 and
+// oil_water_viscosity_f32 live in odr_seawater.hip.h (shared with the pelagic egg model, odr_egg.hip.h)
 #define OF(x) ((float)(x))
-__device__ __forceinline__ float oil_sea_water_density_f32(float T, float S) {
-  float R1 = __fsub_rn(__fmul_rn(OF(6.536332E-09), T), OF(1.120083E-06));
-  R1 = __fadd_rn(__fmul_rn(R1, T), OF(1.001685E-04));
-  R1 = __fsub_rn(__fmul_rn(R1, T), OF(9.095290E-03));
-  R1 = __fadd_rn(__fmul_rn(R1, T), OF(6.793952E-02));
-  R1 = __fsub_rn(__fmul_rn(R1, T), OF(28.263737));
-  float R2 = __fsub_rn(__fmul_rn(OF(5.3875E-09), T), OF(8.2467E-07));
-  R2 = __fadd_rn(__fmul_rn(R2, T), OF(7.6438E-05));
-  R2 = __fsub_rn(__fmul_rn(R2, T), OF(4.0899E-03));
-  R2 = __fadd_rn(__fmul_rn(R2, T), OF(8.24493E-01));
-  float R3 = __fadd_rn(__fmul_rn(OF(-1.6546E-06), T), OF(1.0227E-04));
-  R3 = __fsub_rn(__fmul_rn(R3, T), OF(5.72466E-03));
-  const float in = __fadd_rn(__fadd_rn(__fmul_rn(OF(4.8314E-04), S), __fmul_rn(R3, sqrtf(S))), R2);
-  const float SIG = __fadd_rn(R1, __fmul_rn(in, S));
-  return __fadd_rn(__fadd_rn(SIG, OF(28.106331)), 1000.f);
-}
-
-__device__ __forceinline__ float oil_water_viscosity_f32(float T, float S) {
-  const float t1 = __fadd_rn(T, OF(64.993));
-  const float mu_w = __fadd_rn(OF(4.2844e-5), __fdiv_rn(1.0f, __fsub_rn(__fmul_rn(OF(0.157), __fmul_rn(t1, t1)), OF(91.296))));
-  const float T2 = __fmul_rn(T, T);
-  const float A = __fsub_rn(__fadd_rn(OF(1.541), __fmul_rn(OF(1.998e-2), T)), __fmul_rn(OF(9.52e-5), T2));
-  const float B = __fadd_rn(__fsub_rn(OF(7.974), __fmul_rn(OF(7.561e-2), T)), __fmul_rn(OF(4.724e-4), T2));
-  const float s = __fdiv_rn(S, 1000.f);
-  return __fmul_rn(mu_w, __fadd_rn(__fadd_rn(1.f, __fmul_rn(A, s)), __fmul_rn(B, __fmul_rn(s, s))));
-}
 
 // significant_wave_height() (physics_methods.py:893-907), float32
 __device__ __forceinline__ float oil_hs(const PView &p, long long i, int hs_mode, float ws) {

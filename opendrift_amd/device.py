@@ -785,6 +785,11 @@ class Particles:
         else:
             self.vmix_analytic(model, background_diffusivity, dt, dt_mix, mix_at_surface=mix_at_surface, step=step, uniforms=mix)
 
+    def egg_terminal_velocity(self, diameter_slot=0, salinity_slot=1):
+        """PelagicEggDrift.update_terminal_velocity (pelagicegg.py:100-179): terminal_velocity of every element from the sampled
+        sea_water_temperature / sea_water_salinity and the two property slots (egg diameter, salinity of neutral buoyancy)."""
+        check(self.lib.odr_egg_terminal_velocity(self.ctx.h, self.h, int(diameter_slot), int(salinity_slot)))
+
     def vertical_advection(self, dt, at_surface=False):
         check(self.lib.odr_vertical_advection(self.ctx.h, self.h, float(dt), int(at_surface)))
 
@@ -996,7 +1001,7 @@ for _name in ('append', 'upload', 'env_sample', 'env_upload', 'env_add_noise', '
               'update_positions', 'advect_wind', 'stokes_drift', 'advect_sea_ice', 'set_property', 'leeway_capsize', 'leeway', 'hdiffusion', 'movers',
               'vmix', 'vmix_analytic', 'vmix_oil', 'vertical_advection', 'vertical_buoyancy', 'coastline', 'coastline_crossing',
               'increase_age', 'deactivate_missing', 'remap_status', 'seafloor', 'deactivate', 'deactivate_outside', 'compact',
-              'compact_apply', 'sort_by_cell', 'store_previous', 'oil_prepare_mixing', 'env_coast_leeway'):
+              'compact_apply', 'sort_by_cell', 'store_previous', 'oil_prepare_mixing', 'env_coast_leeway', 'egg_terminal_velocity'):
     setattr(Particles, _name, _touching(getattr(Particles, _name)))
 
 
