@@ -196,6 +196,13 @@ int odr_block_set_content_ids(odr_ctx *ctx, int32_t source_id, int32_t slot, int
 int odr_host_register(odr_ctx *ctx, void *ptr, uint64_t bytes);   /* hipHostRegister: reader arrays that are uploaded repeatedly */
 int odr_host_unregister(odr_ctx *ctx, void *ptr);
 int odr_block_drop(odr_ctx *ctx, int32_t source_id, int32_t slot);
+/* Debugging / tests: the K plane of a resident level -- ocean_vertical_diffusivity a second time, as *krec = 4 * ((nz + 3) / 4)
+ * floats per node (z innermost, node order iy * nx + ix, padding floats 0), written by the level's preparation next to the node
+ * records when the block can serve the K-column mixing kernels (csrc/odr_field.hip.h DevBlock::kplane).  *krec = 0: the level
+ * has none.  plane_out / records_out (both or neither; cap_floats >= ny * nx * *krec each): the plane, and the K part of the
+ * node records in the plane's layout, which the plane equals bit for bit; synchronous. */
+int odr_block_kplane_read(odr_ctx *ctx, int32_t source_id, int32_t slot, int32_t *krec, float *plane_out, float *records_out,
+                          uint64_t cap_floats);
 /* drift:truncate_ocean_model_below_m (models/basemodel/environment.py:554-566): every get_environment call samples the readers
  * at max(z, -truncate_depth) while the elements keep their depth.  odr_particles_truncate_z puts the clipped depths in place for
  * the sampling calls that follow (odr_env_sample, odr_advect / odr_env_coast_advect: the Runge-Kutta stage calls are
@@ -534,6 +541,11 @@ int odr_particles_step_onlevel_stats(odr_ctx *ctx, odr_particles *p, uint64_t *o
  *         (the five-level window, the generic and OpenOil kernels)}.
  * The environment variable ODR_NO_VMIX_SPEC=1 keeps every column launch on the run-time configuration. */
 int odr_particles_vmix_layout_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out3);
+/* Where the K-column and five-level-window launches of odr_vmix gathered the diffusivity from since the set was created:
+ * out2 = {launches that read the levels' K planes (every resident level of the K source has one, see odr_block_kplane_read),
+ *         launches that read the node records}.
+ * The environment variable ODR_NO_KPLANE=1 keeps every launch on the node records (the planes are still written). */
+int odr_particles_vmix_kplane_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out2);
 /* counts and min/max used for the per-step log line and early-outs (:2212-2233):
  * out16 = {n_active, lon_min, lon_max, lat_min, lat_max, z_min, z_max, D_max, stokes_sum_max,
  *          wind_speed_max, wdf_surface_max, n_surface, hs_max, tp_max, 0, 0} */

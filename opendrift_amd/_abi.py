@@ -93,6 +93,7 @@ _SIGNATURES = {
     'odr_host_register': [_vp, _vp, C.c_uint64],
     'odr_host_unregister': [_vp, _vp],
     'odr_block_drop': [_vp, C.c_int32, C.c_int32],
+    'odr_block_kplane_read': [_vp, C.c_int32, C.c_int32, _ip, _fp, _fp, C.c_uint64],
     'odr_env_bind': [_vp, C.c_int32, C.c_int, _ip, C.c_float],
     'odr_env_sample': [_vp, _vp, C.c_int, _ip, C.c_double, _P(_fp)],
     'odr_env_download': [_vp, _vp, C.c_int32, _fp],
@@ -176,6 +177,7 @@ _SIGNATURES = {
     'odr_particles_step_layout_stats': [_vp, _vp, _P(C.c_uint64)],
     'odr_particles_step_onlevel_stats': [_vp, _vp, _P(C.c_uint64)],
     'odr_particles_vmix_layout_stats': [_vp, _vp, _P(C.c_uint64)],
+    'odr_particles_vmix_kplane_stats': [_vp, _vp, _P(C.c_uint64)],
     'odr_reduce_scalars': [_vp, _vp, C.c_double, _dp],
     'odr_ctx_set_step_reduce': [_vp, C.c_int, C.c_double, C.c_int],
     'odr_reduce_local': [_vp, _vp, C.c_double, C.c_int, _dp],

@@ -93,6 +93,13 @@ struct DevBlock {
   const float *data[NVAR];
   int var_nz[NVAR];
   int es[NVAR];
+  // The K plane: ocean_vertical_diffusivity a second time, as `krec` = 4 * ((nz + 3) / 4) floats per node (z innermost, node
+  // order of the records, padding floats 0, 64 spare bytes behind the last node) -- the same bits as the record's K part.
+  // Written by the record writer (k_blk_records) for a block that qualifies for the fast mixing path (build_vmix_desc: one
+  // member, es == 1, every level of the source, `small`); nullptr otherwise.  It lives in the block's allocation, behind the
+  // records: allocated, recycled and freed with them.
+  const float *kplane;
+  int krec, pad_k;
 };
 
 struct DevSource {

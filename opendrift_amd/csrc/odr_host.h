@@ -178,6 +178,7 @@ struct odr_particles {
   unsigned long long wg_launches;            // host: launches that took the LDS-tile path
   unsigned long long step_launches[3];       // host: k_step_grid launches other than LayoutC3 [0], of LayoutC3 [1], of LayoutC3L1 [2] (also in [0])
   unsigned long long vmix_launches[3];       // host: odr_vmix launches of k_vmix_col with the run-time configuration [0], a static one [1], of the other mixing kernels [2]
+  unsigned long long vmix_kplane[2];         // host: odr_vmix launches of k_vmix_col / k_vmix_win that gathered K from the levels' K planes [0], from the node records [1]
   double *z_keep;       // odr_particles_truncate_z: the elements' own z while the sampling calls see the clipped one
   long long z_keep_n;
   bool z_truncated;
@@ -259,7 +260,9 @@ static inline UVTime uv_time(const DevSource &s, double t) {
 
 // The fast column path of vertical mixing (k_vmix_col, and the mixing fused into k_step_grid): K from one gridded
 // reader with a plain z-innermost array on every resident level of the same geometry.  Fills D for time t.
-static inline bool build_vmix_desc(const odr_ctx *c, double t, VMixDesc &D) {
+// kplanes, in: the levels' K planes (DevBlock::kplane) may be used (false: ODR_NO_KPLANE=1); out: D gathers K from them -- when
+// EVERY resident level has one of the same record length, one rule for both time levels -- and not from the node records.
+static inline bool build_vmix_desc(const odr_ctx *c, double t, VMixDesc &D, bool &kplanes) {
   memset(&D, 0, sizeof D);
   int ksid = -1, nzp = 1;
   for (int k = 0; k < c->hw.nlist[VAR_KZ]; ++k)
@@ -274,12 +277,20 @@ static inline bool build_vmix_desc(const odr_ctx *c, double t, VMixDesc &D) {
     if (s.members[VAR_KZ] > 1 || !bk.small || !bk.data[VAR_KZ] || bk.es[VAR_KZ] != 1 || bk.var_nz[VAR_KZ] != nzp || bk.rec != g0.rec || bk.ny != g0.ny || bk.nx != g0.nx ||
         bk.x0 != g0.x0 || bk.xspan != g0.xspan || bk.y0 != g0.y0 || bk.yspan != g0.yspan)
       return false;
+    if (!bk.kplane || bk.krec != g0.krec) kplanes = false;
   }
   int ib, ia;
   host_bracket(s, t, ib, ia);
   D.sid = ksid; D.nzp = nzp; D.geo_slot = ib;
-  D.kb = s.slot[ib].data[VAR_KZ];
-  D.ka = ia >= 0 ? s.slot[ia].data[VAR_KZ] : nullptr;
+  if (kplanes) {
+    D.kb = s.slot[ib].kplane;
+    D.ka = ia >= 0 ? s.slot[ia].kplane : nullptr;
+    D.kstride = 4u * (unsigned)g0.krec;
+  } else {
+    D.kb = s.slot[ib].data[VAR_KZ];
+    D.ka = ia >= 0 ? s.slot[ia].data[VAR_KZ] : nullptr;
+    D.kstride = 4u * (unsigned)g0.rec;
+  }
   D.wgt = ia >= 0 ? (t - s.slot[ib].t) / (s.slot[ia].t - s.slot[ib].t) : 0.0;
   D.Kfb = c->hw.fallback[VAR_KZ];
   return true;

@@ -465,8 +465,10 @@ __device__ __forceinline__ double mix_R_of(unsigned x) {
 // boundaries live in scalar registers and the np.gradient divisors are host constants.
 constexpr int AUX_KMEMBER = 8;   // property slot that parks the member of an ensemble diffusivity (k_kmember)
 struct VMixDesc {
-  int sid, nzp, geo_slot, pad;
-  const float *kb, *ka;  // K arrays of the bracketing time levels (ka == nullptr: on a time level)
+  int sid, nzp, geo_slot;
+  unsigned kstride;      // bytes from one node's K column to the next in kb / ka: 4 * krec (K planes) or 4 * rec (node records)
+  const float *kb, *ka;  // K of the bracketing time levels (ka == nullptr: on a time level): the levels' K planes when every
+                         // resident level has one (DevBlock::kplane), else the K part of their node records
   double wgt;            // weight_after (structured.py:353-354)
   float Kfb, pad2;
   const unsigned long long *guard;   // nullptr, or: the launch does nothing unless *guard != 0 (odr_ctx_guard_next_vmix)
@@ -489,12 +491,13 @@ struct VMixRT {
   __host__ __device__ static constexpr int sf_action(int a) { return a; }
   __host__ __device__ static constexpr int vadv(int v) { return v; }
   __host__ __device__ static constexpr int ntimes(int n) { return n; }
+  __host__ __device__ static constexpr unsigned kstride(unsigned b, int /*NQ*/) { return b; }
   __device__ static void proj_fwd(const DevProj &p, double lon, double lat, double &x, double &y) { proj_fwd_rt(p, lon, lat, x, y); }
 };
 // C3 (bench.py): K from one lat / lon reader (longitudes -180 .. 180, no x wrap) whose z levels are not uniformly spaced, every
 // level of the column (NL = 4 NQ: no padding, no level cut), device RNG, no mixing at the surface, the sea floor lifts
 // (general:seafloor_action 'lift_to_seafloor', the context's default), vertical advection fused below the surface
-// (fuse_vertical_advection=False), ten sub-steps
+// (fuse_vertical_advection=False), ten sub-steps, K gathered from the levels' K planes (16 NQ bytes per node)
 struct VMixC3 {
   static constexpr bool STATIC = true;
   __host__ __device__ static constexpr int proj_kind(int) { return PROJ_LATLONG; }
@@ -507,7 +510,14 @@ struct VMixC3 {
   __host__ __device__ static constexpr int sf_action(int) { return 1; }        // ODR_SEAFLOOR_LIFT
   __host__ __device__ static constexpr int vadv(int) { return 0; }
   __host__ __device__ static constexpr int ntimes(int) { return 10; }        // 600 s / 60 s
+  __host__ __device__ static constexpr unsigned kstride(unsigned, int NQ) { return 16u * (unsigned)NQ; }
   __device__ static void proj_fwd(const DevProj &, double lon, double lat, double &x, double &y) { x = lon; y = lat; }   // (proj_fwd of PROJ_LATLONG)
+};
+
+// the same configuration with K gathered from the node records (a level without a K plane, ODR_NO_KPLANE=1): the stride is
+// the run-time value, everything else stays static
+struct VMixC3Rec : VMixC3 {
+  __host__ __device__ static constexpr unsigned kstride(unsigned b, int /*NQ*/) { return b; }
 };
 
 // K column of one particle at (lon, lat) -> Kp[level][tid] (LDS), time-interpolated like the ReaderBlock's profiles
@@ -531,8 +541,9 @@ __device__ __forceinline__ void vmix_col_fill(const DevSource &s, const VMixDesc
   const Axis ay = axis_fp(yi, ny), ax = axis_fp(xi, nx);
   const double ty = ay.t, tx = ax.t, wy0 = 1 - ty, wx0 = 1 - tx, wgt = D.wgt;
   // uncovered particles gather node (0,0) and discard it: keeps the loads unconditional
-  // byte offsets of the four node records (blocks of the fast path are `small`: < 2^24 nodes, < 4 GiB; 24-bit multiplies)
-  const unsigned recb = (unsigned)bb.rec * 4u;
+  // byte offsets of the four nodes' K columns (blocks of the fast path are `small`: < 2^24 nodes, < 4 GiB; 24-bit multiplies;
+  // the stride of a K plane is never longer than the record's)
+  const unsigned recb = VM::kstride(D.kstride, NQ);
   const unsigned r0 = __umul24((unsigned)ay.i0, (unsigned)nx), r1 = __umul24((unsigned)ay.i1, (unsigned)nx);
   const unsigned o00 = cov ? __umul24(r0 + (unsigned)ax.i0, recb) : 0u, o01 = cov ? __umul24(r0 + (unsigned)ax.i1, recb) : 0u;
   const unsigned o10 = cov ? __umul24(r1 + (unsigned)ax.i0, recb) : 0u, o11 = cov ? __umul24(r1 + (unsigned)ax.i1, recb) : 0u;
@@ -2097,8 +2108,8 @@ __global__ __launch_bounds__(BLOCK, ODR_VWIN_WAVES) void k_vmix_win(const DevWor
   double c_dk[3], c_sg[3], wb[4];
   auto load_window = [&](int lv0, unsigned o00, unsigned o01, unsigned o10, unsigned o11, double w00, double w01, double w10,
                          double w11, bool cov, bool first) {
-    // level offsets inside the node record; the wide gather reaches level lv0 + 2 <= nzp: at most one float past the K
-    // array, inside the record or the 64 spare bytes a block ends with
+    // level offsets inside the node's K column; the wide gather reaches level lv0 + 2 <= nzp: at most one float past the K
+    // array, inside the record (the next node's column in a K plane) or the 64 spare bytes a block and its plane end with
     const unsigned lq = (unsigned)(lv0 - 1) * 4u, l1 = (unsigned)(lv0 >= 2 ? lv0 - 2 : 0) * 4u;
     const F4 b00 = ld_off<F4>(kb, o00 + lq), b01 = ld_off<F4>(kb, o01 + lq), b10 = ld_off<F4>(kb, o10 + lq), b11 = ld_off<F4>(kb, o11 + lq);
     const float c00 = ld_off<float>(kb, o00 + l1), c01 = ld_off<float>(kb, o01 + l1), c10 = ld_off<float>(kb, o10 + l1), c11 = ld_off<float>(kb, o11 + l1);
@@ -2180,7 +2191,7 @@ __global__ __launch_bounds__(BLOCK, ODR_VWIN_WAVES) void k_vmix_win(const DevWor
     const Axis ay = axis_fp(yi, ny), ax = axis_fp(xi, nx);
     const double ty = ay.t, tx = ax.t, wy0 = 1 - ty, wx0 = 1 - tx;
     // uncovered particles gather node (0,0) and discard it: keeps the loads unconditional
-    const unsigned recb = (unsigned)bb.rec * 4u;
+    const unsigned recb = D.kstride;
     const unsigned r0 = __umul24((unsigned)ay.i0, (unsigned)nx), r1 = __umul24((unsigned)ay.i1, (unsigned)nx);
     const unsigned o00 = cov ? __umul24(r0 + (unsigned)ax.i0, recb) : 0u, o01 = cov ? __umul24(r0 + (unsigned)ax.i1, recb) : 0u;
     const unsigned o10 = cov ? __umul24(r1 + (unsigned)ax.i0, recb) : 0u, o11 = cov ? __umul24(r1 + (unsigned)ax.i1, recb) : 0u;
@@ -3321,6 +3332,8 @@ struct BlkPrep {   // the variables of one time level, staged side by side ([nz]
   int nz[NVAR], cum[NVAR + 1];             // layers; layers of the variables before it (flag rows, flat layer index)
   int off[NVAR], es[NVAR], eo[NVAR];       // record layout (DevBlock)
   unsigned char fill[NVAR], dil[NVAR];     // fill towards the sea floor; dilate (everything but the land mask)
+  float *kplane;                           // K plane of the block (DevBlock::kplane), or nullptr
+  int koff, knz, krec, pad2;               // K's offset in the record, its levels, floats per node of the plane
 };
 __global__ __launch_bounds__(BLOCK) void k_blk_mask_fill(BlkPrep Q, int *__restrict__ tile_flags) {
   const int x = blockIdx.x * BLOCK + threadIdx.x, y = blockIdx.y, kv = blockIdx.z;
@@ -3593,7 +3606,8 @@ __global__ __launch_bounds__(BLOCK) void k_blk_to_record(const float *__restrict
 // The record writer of the three-pass preparation: 64 nodes per workgroup, the COMPLETE records of those nodes assembled
 // in LDS (every layer of every variable read along the nodes: 256-byte coalesced reads; NaN cells take the dilated value)
 // and written as one contiguous run of 64 x rec floats -- instead of one strided pass over the block per variable.
-// Records longer than REC_CH floats go in chunks.  Padding floats are written as 0.
+// Records longer than REC_CH floats go in chunks.  Padding floats are written as 0.  The K part of the records goes out a
+// second time from the same LDS image, as one contiguous run of 64 x krec floats of the block's K plane (Q.kplane).
 constexpr int REC_CH = 128;
 __global__ __launch_bounds__(BLOCK) void k_blk_records(BlkPrep Q, float *__restrict__ dst, size_t plane) {
   extern __shared__ float t[];   // [64][cs], cs = min(rec, REC_CH) | 1: lane-strided writes and row reads without bank conflicts
@@ -3644,6 +3658,15 @@ __global__ __launch_bounds__(BLOCK) void k_blk_records(BlkPrep Q, float *__restr
     for (int node = w; node < 64; node += NW)
       if (n0 + node < plane)
         for (int pp = lane; pp < cw; pp += 64) dst[(n0 + node) * rec + r0 + pp] = t[node * cs + pp];
+    if (Q.kplane) {
+      const int krec = Q.krec, kr = Q.koff - r0;   // K's first float in this chunk's LDS image
+      for (int q = threadIdx.x; q < 64 * krec; q += BLOCK) {
+        const int node = q / krec, j = q - node * krec, pp = kr + j;
+        if (n0 + node >= plane) break;
+        if (j >= Q.knz) { if (r0 == 0) Q.kplane[n0 * krec + q] = 0.f; }          // the plane's padding floats, once
+        else if (pp >= 0 && pp < cw) Q.kplane[n0 * krec + q] = t[node * cs + pp];
+      }
+    }
   }
 }
 

@@ -13,7 +13,8 @@ static bool vmix_layout_matches(const DevSource &s, const VMixDesc &D, int nq, d
   return VM::proj_kind(s.proj.kind) == s.proj.kind && VM::lon_mode(s.lon_mode) == s.lon_mode &&
          VM::mod360_x(s.mod360_x) == s.mod360_x && VM::nzp(D.nzp, 4 * nq) == D.nzp && VM::uniform_z(uz) == uz &&
          VM::rng_mode(rng_mode) == rng_mode && VM::mix_at_surface(mix_at_surface) == mix_at_surface &&
-         VM::sf_action(sfl & 255) == (sfl & 255) && VM::vadv(vadv) == vadv && VM::ntimes(ntimes) == ntimes;
+         VM::sf_action(sfl & 255) == (sfl & 255) && VM::vadv(vadv) == vadv && VM::ntimes(ntimes) == ntimes &&
+         VM::kstride(D.kstride, nq) == D.kstride;
 }
 
 int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, int mix_at_surface, int rng_mode,
@@ -29,7 +30,9 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
   const bool f32prof = p->profiles_f32;
   const int cut = c->vmix_levels;
   VMixDesc D;
-  const bool fast = !oil && !f32prof && cut <= 0 && !getenv("ODR_NO_FAST_PATH") && build_vmix_desc(c, t, D);
+  // (ODR_NO_KPLANE=1: K from the node records although the levels have K planes, for A/B runs and tests)
+  bool kplanes = !getenv("ODR_NO_KPLANE");
+  const bool fast = !oil && !f32prof && cut <= 0 && !getenv("ODR_NO_FAST_PATH") && build_vmix_desc(c, t, D, kplanes);
   // a guarded call that cannot honour the guard (host-drawn numbers, another kernel family) launches nothing and consumes
   // nothing -- the one-shot settings stay armed, DevWorld::f32pos is not touched --: the caller calls again, unguarded
   if (guarded && (rng_mode == ODR_RNG_HOST || !fast)) return 1;
@@ -94,11 +97,15 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
     const char *wenv = getenv("ODR_VMIX_WINDOW");
     const bool win = nzp >= 3 && nzp <= BLOCK && (wenv ? atoi(wenv) != 0 : nzp > 12);
     // C3's configuration as compile-time constants (VMixC3) at both of its field sizes, 8 and 12 levels, when the source and
-    // the call are exactly that configuration; ODR_NO_VMIX_SPEC=1 forces the run-time configuration (A/B runs and tests)
+    // the call are exactly that configuration; ODR_NO_VMIX_SPEC=1 forces the run-time configuration (A/B runs and tests).
+    // VMixC3 gathers K from the K planes (the stride a constant); a C3 launch that gathers from the records keeps the static
+    // configuration with the run-time stride (VMixC3Rec).
     const bool spec = !win && (nq == 2 || nq == 3) &&
-                      vmix_layout_matches<VMixC3>(c->hw.src[D.sid], D, nq, dt, dt_mix, mix_at_surface, rng_mode, c->seafloor, vadv) &&
+                      vmix_layout_matches<VMixC3Rec>(c->hw.src[D.sid], D, nq, dt, dt_mix, mix_at_surface, rng_mode, c->seafloor, vadv) &&
                       !getenv("ODR_NO_VMIX_SPEC");
+    const bool specp = spec && vmix_layout_matches<VMixC3>(c->hw.src[D.sid], D, nq, dt, dt_mix, mix_at_surface, rng_mode, c->seafloor, vadv);
     p->vmix_launches[win ? 2 : spec ? 1 : 0]++;
+    p->vmix_kplane[kplanes ? 0 : 1]++;
 #define VMIX_COL(NQ, VM)                                                                                          \
   do {                                                                                                            \
     size_t l2 = sizeof(double) * ((size_t)(4 * NQ) * BLOCK + 4 * (size_t)(4 * NQ));                               \
@@ -114,8 +121,10 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
       else hipLaunchKernelGGL((k_vmix_win<false>), g, b, lw, c->stream, c->dw, v, D, dt, dt_mix, mix_at_surface, rng_mode, du,
                               c->seed, st, vadv, c->seafloor);
     }
-    else if (spec && nq == 2) VMIX_COL(2, VMixC3);
-    else if (spec) VMIX_COL(3, VMixC3);
+    else if (specp && nq == 2) VMIX_COL(2, VMixC3);
+    else if (specp) VMIX_COL(3, VMixC3);
+    else if (spec && nq == 2) VMIX_COL(2, VMixC3Rec);
+    else if (spec) VMIX_COL(3, VMixC3Rec);
     // the smallest instantiated quad count >= nq; over-read stays inside the 64-byte array padding
     else if (nq <= 1) VMIX_COL(1, VMixRT);
     else if (nq == 2) VMIX_COL(2, VMixRT);
@@ -141,6 +150,12 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
 int odr_particles_vmix_layout_stats(odr_ctx *c, odr_particles *p, uint64_t *out3) {
   REQUIRE(c && p && out3, "NULL argument");
   for (int k = 0; k < 3; ++k) out3[k] = p->vmix_launches[k];
+  return 0;
+}
+
+int odr_particles_vmix_kplane_stats(odr_ctx *c, odr_particles *p, uint64_t *out2) {
+  REQUIRE(c && p && out2, "NULL argument");
+  out2[0] = p->vmix_kplane[0]; out2[1] = p->vmix_kplane[1];
   return 0;
 }
 

@@ -710,7 +710,18 @@ static int stage_block(odr_ctx *c, int32_t sid, int32_t slot, double t_epoch, in
       rec += nzv;
     }
   rec = (rec + 3) & ~3;
-  const size_t base_bytes = sizeof(float) * plane * (size_t)rec + 64;
+  const size_t rec_bytes = sizeof(float) * plane * (size_t)rec + 64;
+  const bool prep_all = !getenv("ODR_PLAIN_DILATE") && !getenv("ODR_ROW_DILATE") && ny < 65536 && nlayers < 65536 && nvars <= NVAR;
+  const bool small = plane < (1u << 24) && (double)plane * rec * 4.0 < 4294967296.0 && rec * 4 < (1 << 24);
+  // The K plane (DevBlock::kplane) of a block that can serve the fast mixing path -- the conditions of build_vmix_desc that are
+  // properties of one block -- behind the records in the same allocation, 256-byte aligned, with 64 spare bytes of its own.
+  // Written by k_blk_records only: the per-variable preparation (ODR_PLAIN_DILATE / ODR_ROW_DILATE) leaves a block without one.
+  int kvar = -1;
+  for (int k = 0; k < nvars; ++k) if (var_ids[k] == VAR_KZ) kvar = k;
+  const bool with_kplane = prep_all && small && kvar >= 0 && s.members[VAR_KZ] <= 1 && es[(size_t)kvar] == 1 && s.nz > 1 && var_nz[kvar] == s.nz;
+  const int krec = with_kplane ? 4 * ((s.nz + 3) / 4) : 0;
+  const size_t kplane_at = (rec_bytes + 255) & ~(size_t)255;
+  const size_t base_bytes = with_kplane ? kplane_at + sizeof(float) * plane * (size_t)krec + 64 : rec_bytes;
   float *base = nullptr;
   reap(c, base_bytes, &base);   // recycle a retired block of the same size if the compute stream is done with it
   if (!base) { SlowSpan sp("stage_block: hipMalloc of the block"); HIPCHK(hipMalloc((void **)&base, base_bytes)); }
@@ -741,7 +752,6 @@ static int stage_block(odr_ctx *c, int32_t sid, int32_t slot, double t_epoch, in
   // staged side by side in the scratch pool, mask + sea-floor fill with a NaN flag per (layer, tile), the ten dilation
   // sweeps on flagged tiles only, one record writer that assembles complete node records.  ODR_ROW_DILATE /
   // ODR_PLAIN_DILATE: the per-variable whole-array sweeps of rounds 1-2 (the cross-check of tests/test_gpu_async_upload.py).
-  const bool prep_all = !getenv("ODR_PLAIN_DILATE") && !getenv("ODR_ROW_DILATE") && ny < 65536 && nlayers < 65536 && nvars <= NVAR;
   if (bcast_root >= 0 && !prep_all) return fail(ODR_ERR_INVALID, "odr_block_broadcast: the level does not fit the one-pass preparation");
   if (prep_all) {
     BlkPrep Q;
@@ -758,7 +768,13 @@ static int stage_block(odr_ctx *c, int32_t sid, int32_t slot, double t_epoch, in
       c->tile_flags_n = nflags;
     }
     HIPCHK(hipMemsetAsync(c->tile_flags, 0, sizeof(int) * nflags, st));
-    HIPCHK(hipMemsetAsync((char *)base + base_bytes - 64, 0, 64, st));   // the spare bytes wide slot loads may touch
+    HIPCHK(hipMemsetAsync((char *)base + rec_bytes - 64, 0, 64, st));   // the spare bytes wide slot loads may touch
+    if (with_kplane) {
+      Q.kplane = (float *)((char *)base + kplane_at);
+      Q.koff = off[(size_t)kvar]; Q.knz = s.nz; Q.krec = krec;
+      HIPCHK(hipMemsetAsync((char *)base + base_bytes - 64, 0, 64, st));
+      b.kplane = Q.kplane; b.krec = krec;
+    }
     size_t at_f = 0;
     int cum = 0, ndil = 0;
     for (int k = 0; k < nvars; ++k) {
@@ -853,7 +869,7 @@ static int stage_block(odr_ctx *c, int32_t sid, int32_t slot, double t_epoch, in
   HIPCHK(hipGetLastError());
   b.base = base;
   b.rec = rec;
-  b.small = plane < (1u << 24) && (double)plane * rec * 4.0 < 4294967296.0 && rec * 4 < (1 << 24);
+  b.small = small;
   S.base = base;
   S.bytes = base_bytes;
   HIPCHK(hipEventRecord(c->up_done, st));
@@ -974,6 +990,36 @@ int odr_block_drop(odr_ctx *c, int32_t sid, int32_t slot) {
   memset(c->block_cid[sid][slot], 0, sizeof c->block_cid[sid][slot]);
   sort_levels(c->hw.src[sid]);
   c->dirty = true;
+  return 0;
+}
+
+// the K part of the node records in the layout of the K plane (odr_block_kplane_read)
+__global__ __launch_bounds__(BLOCK) void k_blk_record_k(const float *__restrict__ kdata, int rec, int nz, int krec, size_t n, float *__restrict__ out) {
+  const size_t q = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (q >= n) return;
+  const size_t node = q / (size_t)krec;
+  const int j = (int)(q - node * (size_t)krec);
+  out[q] = j < nz ? kdata[node * (size_t)rec + j] : 0.f;
+}
+int odr_block_kplane_read(odr_ctx *c, int32_t sid, int32_t slot, int32_t *krec, float *plane_out, float *records_out, uint64_t cap_floats) {
+  REQUIRE(sid >= 0 && sid < c->nsrc && slot >= 0 && slot < MAXLEVELS && krec, "bad source/slot");
+  REQUIRE((plane_out != nullptr) == (records_out != nullptr), "both output arrays or neither");
+  const DevBlock &b = c->hw.src[sid].slot[slot];
+  REQUIRE(b.valid, "no resident block for source %d slot %d", sid, slot);
+  *krec = b.kplane ? b.krec : 0;
+  if (!b.kplane || !plane_out) return 0;
+  const size_t n = (size_t)b.ny * b.nx * (size_t)b.krec;
+  REQUIRE(cap_floats >= n, "the K plane holds %zu floats", n);
+  HIPCHK(hipSetDevice(c->device));
+  float *tmp = nullptr;
+  HIPCHK(hipMalloc((void **)&tmp, sizeof(float) * n));
+  struct Free { float *p; ~Free() { (void)hipFree(p); } } free_tmp{tmp};   // on every way out
+  hipLaunchKernelGGL(k_blk_record_k, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, b.data[VAR_KZ], b.rec, b.var_nz[VAR_KZ],
+                     b.krec, n, tmp);
+  HIPCHK(hipGetLastError());
+  D2H(records_out, tmp, sizeof(float) * n);
+  D2H(plane_out, b.kplane, sizeof(float) * n);
+  HIPCHK(hipStreamSynchronize(c->stream));
   return 0;
 }
 

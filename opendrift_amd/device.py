@@ -358,6 +358,20 @@ class Context:
     def drop_block(self, sid, slot):
         check(self.lib.odr_block_drop(self.h, sid, slot))
 
+    def kplane_read(self, sid, slot):
+        """Debugging / tests (odr_block_kplane_read): (K plane of a resident level, K part of its node records in the same
+        layout) as float32 [ny, nx, krec] arrays, or None when the level has no K plane."""
+        g = self._grids[sid]
+        krec = C.c_int32(0)
+        check(self.lib.odr_block_kplane_read(self.h, sid, slot, C.byref(krec), None, None, 0))
+        if krec.value == 0:
+            return None
+        plane = np.empty((g['ny'], g['nx'], krec.value), dtype=np.float32)
+        recs = np.empty_like(plane)
+        check(self.lib.odr_block_kplane_read(self.h, sid, slot, C.byref(krec), plane.ctypes.data_as(_fp), recs.ctypes.data_as(_fp),
+                                             plane.size))
+        return plane, recs
+
     def release_source(self, sid):
         """The source is no longer used: its blocks are dropped, its id is free for the next add_* (odr_source_release)."""
         check(self.lib.odr_source_release(self.h, int(sid)))
@@ -930,6 +944,14 @@ class Particles:
         out = (C.c_uint64 * 3)()
         check(self.lib.odr_particles_vmix_layout_stats(self.ctx.h, self.h, out))
         return dict(runtime=int(out[0]), static=int(out[1]), other=int(out[2]))
+
+    def vmix_kplane_stats(self):
+        """Where the K-column / window mixing launches gathered the diffusivity from (odr_particles_vmix_kplane_stats): the
+        levels' K planes, or the node records."""
+        import ctypes as C
+        out = (C.c_uint64 * 2)()
+        check(self.lib.odr_particles_vmix_kplane_stats(self.ctx.h, self.h, out))
+        return dict(planes=int(out[0]), records=int(out[1]))
 
     def reduce_global(self, combine, wind_drift_depth=0.1, relative_wind=False):
         """Sharded run: this set's raw reductions -> combine(raw16) over the ranks (counts summed, maxima maximised) ->
