@@ -464,12 +464,23 @@ int odr_increase_age(odr_ctx *ctx, odr_particles *p, double dt, double max_age_s
 int odr_seafloor(odr_ctx *ctx, odr_particles *p, int64_t *n_below);   /* 'lift_to_seafloor' */
 /* the other general:seafloor_action values (:768-783): DEACTIVATE flags the element with status_code ('seafloor') and
  * puts it on the sea floor, PREVIOUS moves it back to the lon/lat of odr_store_previous (z unchanged) */
-enum { ODR_SEAFLOOR_LIFT = 1, ODR_SEAFLOOR_DEACTIVATE = 2, ODR_SEAFLOOR_PREVIOUS = 3 };
+enum { ODR_SEAFLOOR_LIFT = 1, ODR_SEAFLOOR_DEACTIVATE = 2, ODR_SEAFLOOR_PREVIOUS = 3,
+       /* SedimentDrift.bottom_interaction (models/sedimentdrift.py:108-116), the hook the reference calls behind
+        * interact_with_seafloor() inside update() (oceandrift.py:364-368, :556-561): the element is put on the sea floor
+        * and SETTLES -- moving = 0, status unchanged, it stays active and no mover moves it until odr_resuspend.
+        * Accepted by odr_set_seafloor_action only (the main-loop interact_with_seafloor() never settles). */
+       ODR_SEAFLOOR_SETTLE = 4 };
 int odr_seafloor_action(odr_ctx *ctx, odr_particles *p, int action, int32_t status_code, int64_t *n_below);
 /* The reference calls interact_with_seafloor() again INSIDE update(): from vertical_buoyancy (oceandrift.py:362-368)
  * and from every sub-step of vertical_mixing (:555-559).  This sets what odr_vertical_buoyancy / odr_vmix* do with an
- * element below the sea floor there (default ODR_SEAFLOOR_LIFT; 0 = 'none'). */
+ * element below the sea floor there (default ODR_SEAFLOOR_LIFT; 0 = 'none'; ODR_SEAFLOOR_SETTLE). */
 int odr_set_seafloor_action(odr_ctx *ctx, int action, int32_t status_code);
+/* SedimentDrift.resuspension (models/sedimentdrift.py:118-126): every element of the active set with moving == 0 whose
+ * current speed -- np.sqrt(u**2 + v**2) of the sampled float32 x_sea_water_velocity / y_sea_water_velocity
+ * (current_speed(), physics_methods.py:889-891) -- exceeds `threshold` (the configuration value as float32) gets
+ * moving = 1 and z + 0.01 (float64).  *n_resuspended: how many (NULL: not counted, no host synchronisation).
+ * ODR_ERR_STATE when the two current components have not been sampled (csrc/odr_sediment.hip.h). */
+int odr_resuspend(odr_ctx *ctx, odr_particles *p, float threshold, int64_t *n_resuspended);
 /* number of active-set elements currently flagged with status_code (not yet removed by odr_compact) */
 int odr_particles_count_status(odr_ctx *ctx, odr_particles *p, int32_t status_code, int64_t *n);
 /* status_categories grow in the order in which reasons FIRST OCCUR (deactivate_elements, :1778-1781): a caller hands

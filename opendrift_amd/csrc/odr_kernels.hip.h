@@ -589,7 +589,8 @@ __device__ __forceinline__ void vmix_col_fill(const DevSource &s, const VMixDesc
 }
 
 // The ntimes_mix random-walk sub-steps of one particle on its K column in LDS (oceandrift.py:505-565).  Returns the
-// new z; sf_flags: 1 deactivated on the sea floor, 2 moved back horizontally (general:seafloor_action).
+// new z; sf_flags: 1 deactivated on the sea floor, 2 moved back horizontally (general:seafloor_action), 4 settled
+// (ODR_SEAFLOOR_SETTLE: moving = 0, the element stays active).
 struct VMixArgs {
   double dt, dt_mix_cfg;
   int mix_at_surface, rng_mode, sfl, pad;
@@ -725,8 +726,9 @@ __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, con
       const int act = VM::sf_action(sfl & 255);
       if (act == 3) sf_flags |= 2;                       // previous: lon/lat go back, z stays
       else if (act) {
-        z = (double)Zmin;                                // lift_to_seafloor / deactivate
+        z = (double)Zmin;                                // lift_to_seafloor / deactivate / settle
         if (act == 2) { sf_flags |= 1; moving = 0; wstep = 0.0; }
+        else if (act == 4) { sf_flags |= 4; moving = 0; wstep = 0.0; }   // SedimentDrift.bottom_interaction (sedimentdrift.py:108-116)
       }
     }
   }
@@ -1910,8 +1912,9 @@ __global__ __launch_bounds__(BLOCK) void k_vmix(const DevWorld *__restrict__ W, 
       const int act = sfl & 255;
       if (act == 3) sf_flags |= 2;                       // previous: lon/lat go back, z stays
       else if (act) {
-        z = (double)Zmin;                                // lift_to_seafloor / deactivate
+        z = (double)Zmin;                                // lift_to_seafloor / deactivate / settle
         if (act == 2) { sf_flags |= 1; moving = 0; wstep = 0.0; }
+        else if (act == 4) { sf_flags |= 4; moving = 0; wstep = 0.0; }   // SedimentDrift.bottom_interaction (sedimentdrift.py:108-116)
       }
     }
   }
@@ -1919,6 +1922,7 @@ __global__ __launch_bounds__(BLOCK) void k_vmix(const DevWorld *__restrict__ W, 
     if (p.status[i] == 0) p.status[i] = sfl >> 8;
     p.moving[i] = 0;
   }
+  if (sf_flags & 4) p.moving[i] = 0;   // settled: the element stays active (status unchanged)
   if (sf_flags & 2) { p.lon[i] = p.plon[i]; p.lat[i] = p.plat[i]; }
   if (vadv >= 0 && (vadv ? z <= 0 : z < 0)) {  // vertical_advection (oceandrift.py:315-350)
     double zz = __dadd_rn(z, __dmul_rn(__dmul_rn((double)moving, (double)p.env[VAR_W][i]), dt));
@@ -1966,6 +1970,7 @@ __device__ __forceinline__ void vmix_col_particle(const DevSource &s, const PVie
     if (p.status[i] == 0) p.status[i] = sfl >> 8;
     p.moving[i] = 0;
   }
+  if (sf_flags & 4) p.moving[i] = 0;   // settled: the element stays active (status unchanged)
   if (sf_flags & 2) { p.lon[i] = p.plon[i]; p.lat[i] = p.plat[i]; }
   vadv = VM::vadv(vadv);
   if (vadv >= 0 && (vadv ? z <= 0 : z < 0)) {  // vertical_advection (oceandrift.py:315-350)
@@ -2169,8 +2174,9 @@ __global__ __launch_bounds__(BLOCK, ODR_VWIN_WAVES) void k_vmix_win(const DevWor
       const int act = sfl & 255;
       if (act == 3) sf_flags |= 2;                       // previous: lon/lat go back, z stays
       else if (act) {
-        z = (double)Zmin;                                // lift_to_seafloor / deactivate
+        z = (double)Zmin;                                // lift_to_seafloor / deactivate / settle
         if (act == 2) { sf_flags |= 1; moving = 0; wstep = 0.0; }
+        else if (act == 4) { sf_flags |= 4; moving = 0; wstep = 0.0; }   // SedimentDrift.bottom_interaction (sedimentdrift.py:108-116)
       }
     }
     return true;
@@ -2229,6 +2235,7 @@ __global__ __launch_bounds__(BLOCK, ODR_VWIN_WAVES) void k_vmix_win(const DevWor
     if (p.status[i] == 0) p.status[i] = sfl >> 8;
     p.moving[i] = 0;
   }
+  if (sf_flags & 4) p.moving[i] = 0;   // settled: the element stays active (status unchanged)
   if (sf_flags & 2) { p.lon[i] = p.plon[i]; p.lat[i] = p.plat[i]; }
   if (vadv >= 0 && (vadv ? z <= 0 : z < 0)) {  // vertical_advection (oceandrift.py:315-350)
     double zz = __dadd_rn(z, __dmul_rn(__dmul_rn((double)moving, (double)w0), dt));
@@ -2329,8 +2336,9 @@ __global__ __launch_bounds__(BLOCK) void k_vmix_wind(PView p, const double *__re
       const int act = sfl & 255;
       if (act == 3) sf_flags |= 2;                       // previous: lon/lat go back, z stays
       else if (act) {
-        z = (double)Zmin;                                // lift_to_seafloor / deactivate
+        z = (double)Zmin;                                // lift_to_seafloor / deactivate / settle
         if (act == 2) { sf_flags |= 1; moving = 0; wstep = 0.0; }
+        else if (act == 4) { sf_flags |= 4; moving = 0; wstep = 0.0; }   // SedimentDrift.bottom_interaction (sedimentdrift.py:108-116)
       }
     }
   }
@@ -2338,6 +2346,7 @@ __global__ __launch_bounds__(BLOCK) void k_vmix_wind(PView p, const double *__re
     if (p.status[i] == 0) p.status[i] = sfl >> 8;
     p.moving[i] = 0;
   }
+  if (sf_flags & 4) p.moving[i] = 0;   // settled: the element stays active (status unchanged)
   if (sf_flags & 2) { p.lon[i] = p.plon[i]; p.lat[i] = p.plat[i]; }
   if (vadv >= 0 && (vadv ? z <= 0 : z < 0)) {  // vertical_advection (oceandrift.py:315-350)
     double zz = __dadd_rn(z, __dmul_rn(__dmul_rn((double)moving, (double)p.env[VAR_W][i]), dt));
@@ -2364,7 +2373,7 @@ __global__ __launch_bounds__(BLOCK) void k_vadvect(PView p, double dt, int at_su
 }
 
 // vertical_buoyancy (oceandrift.py:352-368); elements below the sea floor "interact_with_seafloor" again, here
-// inside update(): sfl = action | status_code << 8 (0 none, 1 lift_to_seafloor, 2 deactivate, 3 previous)
+// inside update(): sfl = action | status_code << 8 (0 none, 1 lift_to_seafloor, 2 deactivate, 3 previous, 4 settle)
 __global__ __launch_bounds__(BLOCK) void k_vbuoy(PView p, double dt, int sfl) {
   long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
   if (i >= p.n) return;
@@ -2382,7 +2391,7 @@ __global__ __launch_bounds__(BLOCK) void k_vbuoy(PView p, double dt, int sfl) {
       if (act == 2) {
         if (p.status[i] == 0) p.status[i] = sfl >> 8;
         p.moving[i] = 0;
-      }
+      } else if (act == 4) p.moving[i] = 0;   // settle (sedimentdrift.py:108-116): the element stays active
     }
   }
   p.z[i] = z;

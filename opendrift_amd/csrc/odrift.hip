@@ -2101,7 +2101,7 @@ int odr_seafloor_action(odr_ctx *c, odr_particles *p, int action, int32_t code, 
 }
 
 int odr_set_seafloor_action(odr_ctx *c, int action, int32_t code) {
-  REQUIRE(action >= 0 && action <= ODR_SEAFLOOR_PREVIOUS, "unknown seafloor action %d", action);
+  REQUIRE(action >= 0 && action <= ODR_SEAFLOOR_SETTLE, "unknown seafloor action %d", action);
   c->seafloor = action | ((int)code << 8);
   return 0;
 }

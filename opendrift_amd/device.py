@@ -349,7 +349,7 @@ class Context:
 
     def set_seafloor_action(self, action, status_code=0):
         """general:seafloor_action for the sea floor checks inside update() (vertical_buoyancy, vertical_mixing)."""
-        a = {'none': 0, 'lift_to_seafloor': 1, 'deactivate': 2, 'previous': 3}[action]
+        a = _abi.SEAFLOOR[action]      # ('settle': SedimentDrift.bottom_interaction, sedimentdrift.py:108-116)
         check(self.lib.odr_set_seafloor_action(self.h, a, int(status_code)))
 
     def set_time_coverage(self, sid, t_start, t_end, always_valid=False):
@@ -804,6 +804,14 @@ class Particles:
         sea_water_temperature / sea_water_salinity and the two property slots (egg diameter, salinity of neutral buoyancy)."""
         check(self.lib.odr_egg_terminal_velocity(self.ctx.h, self.h, int(diameter_slot), int(salinity_slot)))
 
+    def resuspend(self, threshold, count=True):
+        """SedimentDrift.resuspension (sedimentdrift.py:118-126): settled elements (moving == 0) whose sampled current speed
+        exceeds `threshold` (compared as float32, like NumPy 2) move again, 1 cm up.  Returns how many (count=False: None,
+        and the host does not wait)."""
+        n = C.c_int64()
+        check(self.lib.odr_resuspend(self.ctx.h, self.h, C.c_float(np.float32(threshold)), C.byref(n) if count else None))
+        return n.value if count else None
+
     def vertical_advection(self, dt, at_surface=False):
         check(self.lib.odr_vertical_advection(self.ctx.h, self.h, float(dt), int(at_surface)))
 
@@ -1023,7 +1031,8 @@ for _name in ('append', 'upload', 'env_sample', 'env_upload', 'env_add_noise', '
               'update_positions', 'advect_wind', 'stokes_drift', 'advect_sea_ice', 'set_property', 'leeway_capsize', 'leeway', 'hdiffusion', 'movers',
               'vmix', 'vmix_analytic', 'vmix_oil', 'vertical_advection', 'vertical_buoyancy', 'coastline', 'coastline_crossing',
               'increase_age', 'deactivate_missing', 'remap_status', 'seafloor', 'deactivate', 'deactivate_outside', 'compact',
-              'compact_apply', 'sort_by_cell', 'store_previous', 'oil_prepare_mixing', 'env_coast_leeway', 'egg_terminal_velocity'):
+              'compact_apply', 'sort_by_cell', 'store_previous', 'oil_prepare_mixing', 'env_coast_leeway', 'egg_terminal_velocity',
+              'resuspend'):
     setattr(Particles, _name, _touching(getattr(Particles, _name)))
 
 

@@ -778,9 +778,17 @@ class OpenDriftSimulation(Configurable):
         action = self.get_config('general:seafloor_action', 'lift_to_seafloor')
         if 'sea_floor_depth_below_sea_level' not in self.priority_list:
             action = 'none'     # interact_with_seafloor returns before doing anything (:753-754)
+        action = self._seafloor_action_in_update(action)
         self.ctx.set_seafloor_action(action, self._status_code('seafloor') if action == 'deactivate' else 0)
         call()
         self._resolve_status()
+
+    def _seafloor_action_in_update(self, action):
+        """What the device does with an element below the sea floor inside update() for the configured `action`: a model
+        whose bottom_interaction() hook (oceandrift.py:376-378, called behind interact_with_seafloor() at :368 and :561) does
+        something names the device action that includes it (device.Context.set_seafloor_action).  OceanDrift's hook is empty:
+        no change."""
+        return action
 
     def update_positions(self, x_vel, y_vel):   # :4631-4669
         self._require('Run')
@@ -1285,7 +1293,7 @@ class OpenDriftSimulation(Configurable):
             fused_lane and not os.environ.get('ODR_NO_SPECULATION') and self.rng == 'device' and isinstance(self, OD) and
             all(getattr(cls, m) is getattr(OD, m) for m in ('vertical_mixing', 'vertical_advection', 'update_terminal_velocity',
                                                            '_advect_wind_then_stokes_drift', 'advect_wind', 'stokes_drift',
-                                                           '_with_seafloor_action')) and
+                                                           '_with_seafloor_action', '_seafloor_action_in_update')) and
             self.get_config('drift:vertical_mixing') is True and
             self.get_config('vertical_mixing:diffusivitymodel') == 'environment' and
             ('x_wind' not in self.required_variables or self._calm_everywhere()) and
@@ -1297,7 +1305,8 @@ class OpenDriftSimulation(Configurable):
         stock_update = isinstance(self, OD) and all(
             getattr(cls, m) is getattr(OD, m) for m in ('update', 'vertical_mixing', 'vertical_advection', 'update_terminal_velocity',
                                                         '_advect_wind_then_stokes_drift', 'advect_wind', 'stokes_drift',
-                                                        '_with_seafloor_action', 'vertical_buoyancy'))
+                                                        '_with_seafloor_action', '_seafloor_action_in_update',
+                                                        'vertical_buoyancy'))
         self._vmix_speculated = False
         self.ctx.sync()
         t_loop = [time.perf_counter(), None]      # main-loop wall time (the reference keeps 'main loop' timers, basemodel :2174)

@@ -1,0 +1,134 @@
+"""CPU: the host side of SedimentDrift (opendrift_amd/sedimentdrift.py) -- what can be checked without a device: the class, its
+configuration, its element properties, what it refuses, and the C ABI entries of its device code."""
+import os
+import re
+from datetime import datetime
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+T0 = datetime(2020, 1, 1)
+TM02 = 'sea_surface_wave_mean_period_from_variance_spectral_density_second_frequency_moment'
+REQUIRED = {   # opendrift/models/sedimentdrift.py:45-61
+    'x_sea_water_velocity': 0, 'y_sea_water_velocity': 0, 'sea_surface_height': 0, 'upward_sea_water_velocity': 0,
+    'x_wind': 0, 'y_wind': 0, 'sea_surface_wave_stokes_drift_x_velocity': 0, 'sea_surface_wave_stokes_drift_y_velocity': 0,
+    'sea_surface_wave_period_at_variance_spectral_density_maximum': 0, TM02: 0, 'land_binary_mask': None,
+    'ocean_vertical_diffusivity': 0.02, 'ocean_mixed_layer_thickness': 50, 'sea_floor_depth_below_sea_level': 10000}
+
+
+def model(**kw):
+    from opendrift_amd.sedimentdrift import SedimentDrift
+    return SedimentDrift(loglevel=50, **kw)
+
+
+def test_class_and_config_defaults():
+    from opendrift_amd.oceandrift import OceanDrift
+    o = model()
+    assert isinstance(o, OceanDrift)
+    assert o.get_config('general:coastline_action') == 'previous'
+    assert o.get_config('drift:vertical_mixing') is True
+    assert o.get_config('vertical_mixing:resuspension_threshold') == 0.2
+    assert OceanDrift(loglevel=50).get_config('drift:vertical_mixing') is False      # (the base class keeps its own)
+
+
+def test_resuspension_threshold_key():
+    from opendrift_amd.config import CONFIG_LEVEL_ESSENTIAL
+    o = model()
+    spec = o.get_configspec('vertical_mixing:resuspension_threshold')['vertical_mixing:resuspension_threshold']
+    assert spec['type'] == 'float' and spec['default'] == 0.2 and spec['min'] == 0 and spec['max'] == 3
+    assert spec['units'] == 'm/s' and spec['level'] == CONFIG_LEVEL_ESSENTIAL
+    o.set_config('vertical_mixing:resuspension_threshold', 3)
+    o.set_config('vertical_mixing:resuspension_threshold', 0)
+    for bad in (-0.01, 3.01):
+        with pytest.raises(ValueError):
+            o.set_config('vertical_mixing:resuspension_threshold', bad)
+
+
+def test_required_variables_and_their_fallbacks():
+    from opendrift_amd import _abi
+    from opendrift_amd.sedimentdrift import SedimentDrift
+    assert {k: v['fallback'] for k, v in SedimentDrift.required_variables.items()} == REQUIRED and len(REQUIRED) == 14
+    assert SedimentDrift.required_variables['ocean_vertical_diffusivity'].get('profiles') is True
+    o = model()
+    for v, fb in REQUIRED.items():
+        assert o.get_config('environment:fallback:%s' % v) == fb
+        assert o.get_config('environment:constant:%s' % v) is None
+    # the one without a device id: its keys exist, with the value 0 it is not sampled
+    assert set(REQUIRED) - set(_abi.VARIABLES) == {TM02}
+    assert set(o.required_variables) == set(REQUIRED) - {TM02}
+    o.set_config('environment:constant:%s' % TM02, 0)
+    o.set_config('environment:fallback:%s' % TM02, 0)
+
+
+def test_a_sampled_tm02_is_refused_by_name():
+    from opendrift_amd import readers
+    o = model()
+    with pytest.raises(NotImplementedError, match=TM02):
+        o.add_reader(readers.ConstantReader({TM02: 6.0, 'x_wind': 5.0}))
+    assert not o.priority_list
+    with pytest.raises(NotImplementedError, match=TM02):
+        o.set_config('environment:constant:%s' % TM02, 6.0)
+    assert o.get_config('environment:constant:%s' % TM02) is None
+    o.add_reader(readers.ConstantReader({'x_wind': 5.0}))                       # (a reader without it is accepted,
+    o.add_reader(readers.ConstantReader({TM02: 6.0, 'y_wind': 5.0}), variables=['y_wind'])    # and one asked for other variables only)
+    assert set(o.priority_list) == {'x_wind', 'y_wind'}
+
+
+def test_element_properties_and_their_defaults():
+    o = model()
+    assert o.get_config('seed:terminal_velocity') == -0.001
+    assert o.aux_properties == ['settled'] and o.get_config('seed:settled') == 0
+    o.seed_elements(lon=4.0, lat=60.0, number=5, time=T0)
+    assert o._sched['terminal_velocity'].dtype == np.float32 and (o._sched['terminal_velocity'] == np.float32(-0.001)).all()
+    assert o._sched['settled'].dtype == np.float32 and o._sched['settled'].shape == (5,) and (o._sched['settled'] == 0).all()
+    tv = np.linspace(-0.02, -0.0005, 3)
+    o.seed_elements(lon=[4.0, 4.1, 4.2], lat=[60.0, 60.0, 60.0], time=T0, terminal_velocity=tv)
+    assert np.array_equal(o._sched['terminal_velocity'][5:], tv.astype(np.float32)) and len(o._sched['settled']) == 8
+    from opendrift_amd.oceandrift import OceanDrift
+    assert OceanDrift(loglevel=50).get_config('seed:terminal_velocity') == 0       # (the base class keeps its own)
+
+
+@pytest.mark.parametrize('action', ['none', 'previous'])
+def test_seafloor_actions_that_would_settle_below_the_floor_are_refused_by_name(action):
+    from opendrift_amd.sedimentdrift import REFUSED_SEAFLOOR_ACTIONS
+    assert set(REFUSED_SEAFLOOR_ACTIONS) == {'none', 'previous'}
+    o = model()
+    o.set_config('general:seafloor_action', action)
+    o.seed_elements(lon=4.0, lat=60.0, number=3, time=T0)
+    with pytest.raises(NotImplementedError, match="'%s'" % action):      # when run() starts: nothing has touched a device yet
+        o.run(time_step=600, steps=1)
+    assert o._ctx is None and o.mode == 'Ready'
+
+
+def test_the_settle_action_is_handed_to_the_device_for_lift_only():
+    from opendrift_amd.oceandrift import OceanDrift
+    o = model()
+    assert [o._seafloor_action_in_update(a) for a in ('lift_to_seafloor', 'deactivate', 'none')] == ['settle', 'deactivate', 'none']
+    b = OceanDrift(loglevel=50)
+    assert [b._seafloor_action_in_update(a) for a in ('lift_to_seafloor', 'deactivate', 'none', 'previous')] == \
+        ['lift_to_seafloor', 'deactivate', 'none', 'previous']
+    assert o.bottom_interaction() is None and o.bottom_interaction(Zmin=np.zeros(3)) is None
+
+
+def test_run_takes_the_call_by_call_lane():
+    """run() chooses its lane by the methods a class overrides (oceandrift.py, run()): update() is the model's own, so neither
+    the fused OceanDrift launch nor the speculated mixing launch (which needs the fused lane and the stock sea-floor hook) is
+    taken; vertical_advection is the model's own, so the mixing launch does not take the vertical advection in."""
+    from opendrift_amd.oceandrift import OceanDrift
+    from opendrift_amd.sedimentdrift import SedimentDrift
+    assert SedimentDrift.update is not OceanDrift.update
+    assert SedimentDrift.vertical_advection is not OceanDrift.vertical_advection
+    assert SedimentDrift._seafloor_action_in_update is not OceanDrift._seafloor_action_in_update
+    assert SedimentDrift.vertical_mixing is OceanDrift.vertical_mixing and SedimentDrift.interact_with_seafloor is OceanDrift.interact_with_seafloor
+    assert getattr(SedimentDrift, 'leeway_lane_update', None) is None
+
+
+def test_abi_entries_are_declared_and_bound():
+    from opendrift_amd import _abi, device
+    src = open(os.path.join(ROOT, 'include', 'odrift.h')).read()
+    assert re.search(r'\bint odr_resuspend\(odr_ctx \*ctx, odr_particles \*p, float threshold, int64_t \*n_resuspended\);', src)
+    assert re.search(r'\bODR_SEAFLOOR_SETTLE = 4\b', src)
+    assert 'odr_resuspend' in _abi._SIGNATURES and 'odr_resuspend' in _abi.EXPORTS and len(_abi._SIGNATURES['odr_resuspend']) == 4
+    assert _abi.SEAFLOOR['settle'] == 4 and _abi.SEAFLOOR['lift_to_seafloor'] == 1
+    assert callable(device.Particles.resuspend)
