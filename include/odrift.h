@@ -433,6 +433,25 @@ int odr_oil_set_mixing_stats(odr_ctx *ctx, double mean_zb, double dv50);
  * not been set.  Enqueued on the context's stream; no host synchronisation. */
 enum { ODR_EGG_DIAMETER = 0, ODR_EGG_NEUTRAL_BUOYANCY_SALINITY = 1, ODR_EGG_DENSITY = 2, ODR_EGG_HATCHED = 3 };
 int odr_egg_terminal_velocity(odr_ctx *ctx, odr_particles *p, int diameter_slot, int salinity_slot);
+/* LarvalFish (models/larvalfish.py; Kvile et al. 2018).  The element properties of LarvalFishElement (:31-52) in the property
+ * slots of odr_particles_set_property, float32 all seven: `hatched` (uint8 in the reference) holds 0 (egg) or 1 (larva).  The
+ * terminal velocity of the model (:105-183) is odr_egg_terminal_velocity with these slot numbers. */
+enum { ODR_LARVA_DIAMETER = 0, ODR_LARVA_NEUTRAL_BUOYANCY_SALINITY = 1, ODR_LARVA_STAGE_FRACTION = 2, ODR_LARVA_HATCHED = 3,
+       ODR_LARVA_LENGTH = 4, ODR_LARVA_WEIGHT = 5, ODR_LARVA_SURVIVAL = 6 };
+/* LarvalFish.update_fish_larvae with fish_growth (models/larvalfish.py:200-231, :185-198) over the active set: an egg
+ * (hatched == 0) adds days_in_timestep / exp(3.65 - 0.145 T) to stage_fraction and hatches when the float32 sum is >= 1; every
+ * larva, one hatched in this call included, grows `weight` (Folkvord 2005) and gets `length` from the new weight.  T: the sampled
+ * float32 sea_water_temperature [deg C].  Eggs keep weight and length untouched.  The reference's float32 operation order
+ * (csrc/odr_larval.hip.h).  ODR_ERR_STATE when the temperature has not been sampled or a slot has not been set.  Enqueued on the
+ * context's stream; no host synchronisation. */
+int odr_larval_update(odr_ctx *ctx, odr_particles *p, int stage_fraction_slot, int hatched_slot, int weight_slot, int length_slot,
+                      double dt_seconds);
+/* LarvalFish.larvae_vertical_migration (models/larvalfish.py:233-253): z of a larva becomes min(0, z + direction *
+ * fraction_swimming * swim_speed(length) * dt_seconds) (Peck et al. 2006; float32 displacement, float64 sum); eggs are untouched.
+ * direction: -1 (down: the reference's `self.time.hour < 12`) or +1, decided by the caller once per step.  ODR_ERR_STATE when a
+ * slot has not been set.  No host synchronisation. */
+int odr_larval_migrate(odr_ctx *ctx, odr_particles *p, int hatched_slot, int length_slot, double fraction_swimming,
+                       double dt_seconds, int direction);
 /* performance hint: apply vertical_advection (oceandrift.py:315-350) inside the next odr_vmix
  * kernel (OceanDrift.update() calls them back to back, oceandrift.py:201-208) */
 int odr_vmix_fuse_vertical_advection(odr_ctx *ctx, int at_surface);

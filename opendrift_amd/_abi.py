@@ -133,6 +133,8 @@ _SIGNATURES = {
     'odr_oil_set_mixing_stats': [_vp, C.c_double, C.c_double],
     'odr_egg_terminal_velocity': [_vp, _vp, C.c_int, C.c_int],
     'odr_resuspend': [_vp, _vp, C.c_float, _i64p],
+    'odr_larval_update': [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double],
+    'odr_larval_migrate': [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int],
     'odr_vertical_advection': [_vp, _vp, C.c_double, C.c_int],
     'odr_vertical_buoyancy': [_vp, _vp, C.c_double],
     'odr_store_previous': [_vp, _vp],
@@ -232,6 +234,7 @@ DROPLETS = {'Johansen et al. (2015)': 1, 'Li et al. (2017)': 2}
 OIL_PROPERTIES = ['diameter', 'density', 'viscosity', 'oil_film_thickness', 'diameter_if_entrained']
 SEAFLOOR = {'none': 0, 'lift_to_seafloor': 1, 'deactivate': 2, 'previous': 3, 'settle': 4}     # include/odrift.h ODR_SEAFLOOR_*
 EGG_PROPERTIES = ['diameter', 'neutral_buoyancy_salinity', 'density', 'hatched']     # include/odrift.h ODR_EGG_*
+LARVA_PROPERTIES = ['diameter', 'neutral_buoyancy_salinity', 'stage_fraction', 'hatched', 'length', 'weight', 'survival']     # ODR_LARVA_*
 
 
 def check(rc):

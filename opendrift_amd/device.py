@@ -804,6 +804,19 @@ class Particles:
         sea_water_temperature / sea_water_salinity and the two property slots (egg diameter, salinity of neutral buoyancy)."""
         check(self.lib.odr_egg_terminal_velocity(self.ctx.h, self.h, int(diameter_slot), int(salinity_slot)))
 
+    def larval_update(self, dt, stage_fraction_slot=2, hatched_slot=3, weight_slot=5, length_slot=4):
+        """LarvalFish.update_fish_larvae (larvalfish.py:200-231, with fish_growth :185-198) over the active set: eggs add to
+        stage_fraction and hatch at >= 1, larvae grow in weight and get their length from it.  `hatched` is uint8 in the
+        reference; here it is a float32 property slot holding 0 (egg) or 1 (larva), like PelagicEggDrift's."""
+        check(self.lib.odr_larval_update(self.ctx.h, self.h, int(stage_fraction_slot), int(hatched_slot), int(weight_slot),
+                                         int(length_slot), float(dt)))
+
+    def larval_migrate(self, dt, fraction_swimming, direction, hatched_slot=3, length_slot=4):
+        """LarvalFish.larvae_vertical_migration (larvalfish.py:233-253): every larva (hatched slot == 1) swims for
+        `fraction_swimming` of the time step, down (direction -1) or up (+1), not above z = 0."""
+        check(self.lib.odr_larval_migrate(self.ctx.h, self.h, int(hatched_slot), int(length_slot), float(fraction_swimming),
+                                          float(dt), int(direction)))
+
     def resuspend(self, threshold, count=True):
         """SedimentDrift.resuspension (sedimentdrift.py:118-126): settled elements (moving == 0) whose sampled current speed
         exceeds `threshold` (compared as float32, like NumPy 2) move again, 1 cm up.  Returns how many (count=False: None,
@@ -1032,7 +1045,7 @@ for _name in ('append', 'upload', 'env_sample', 'env_upload', 'env_add_noise', '
               'vmix', 'vmix_analytic', 'vmix_oil', 'vertical_advection', 'vertical_buoyancy', 'coastline', 'coastline_crossing',
               'increase_age', 'deactivate_missing', 'remap_status', 'seafloor', 'deactivate', 'deactivate_outside', 'compact',
               'compact_apply', 'sort_by_cell', 'store_previous', 'oil_prepare_mixing', 'env_coast_leeway', 'egg_terminal_velocity',
-              'resuspend'):
+              'resuspend', 'larval_update', 'larval_migrate'):
     setattr(Particles, _name, _touching(getattr(Particles, _name)))
 
 

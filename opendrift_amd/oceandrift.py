@@ -1066,10 +1066,35 @@ class OpenDriftSimulation(Configurable):
         r = self._reduce_scalars(self.get_config('drift:wind_drift_depth', 0.1))
         if r['stokes_sum_max'] == 0:
             return None
-        # provenance of Hs / Tp (physics_methods.py:893-943, :809-814)
-        hs_mode = 0 if r['hs_max'] > 0 else (1 if r['wind_speed_max'] > 0 else 2)
-        tp_mode = 1 if r['wind_speed_max'] >= 0 else 2   # Tp is not an OceanDrift variable: from wind (omega=5 when calm)
+        hs_mode, tp_mode = self._stokes_wave_provenance(r)
         return dict(profile=profile, hs_mode=hs_mode, tp_mode=tp_mode, factor=factor)
+
+    def _wind_speed_max_all(self):
+        """The largest wind speed over EVERY active element, of all ranks in a sharded run (the reduction's own wind maximum is
+        advect_wind's: over the elements within wind_drift_depth of the surface).  One more reduction -- and, sharded, one more
+        collective, entered by every rank: the caller decides on all-rank values -- with the step's installed reduction put back."""
+        if self._world == 1:
+            return self.P.reduce_scalars(1e30)['wind_speed_max']      # z >= -1e30: every element
+        self._timing_collectives += 1
+        g = self._combine()(self.P.reduce_local(1e30, False))
+        if getattr(self, '_step_red', None) is not None:
+            self.P.reduce_install(self._step_red)
+        else:      # (the reduction _reduce_scalars installed for the mover that follows)
+            self._timing_collectives += 2
+            self.P.reduce_global(self._combine(), self.get_config('drift:wind_drift_depth', 0.1), False)
+        return self.P.reduction_dict(g)['wind_speed_max']
+
+    def _stokes_wave_provenance(self, r):
+        """(hs_mode, tp_mode) of the Stokes profile from the all-rank reduction `r` (physics_methods.py:893-943, :809-814): wave
+        height from the environment (0) where some element has one, else from the wind (1), else 1 m (2); Tp is not an
+        OceanDrift variable: from the wind (1; omega = 5 when calm) where the wind is sampled, else 8 s (2).  The reference looks
+        at the wind of EVERY element; `r['wind_speed_max']` covers the elements within wind_drift_depth of the surface and is -inf
+        when there is none (a submerged population): the maximum over all elements is then asked for where the decision needs it."""
+        wind_max = r['wind_speed_max']
+        if wind_max < 0 and r['n_surface'] == 0 and 'x_wind' in self.required_variables and 'y_wind' in self.required_variables:
+            wind_max = 0.0 if r['hs_max'] > 0 else self._wind_speed_max_all()      # (given Hs: only the wind's being sampled matters)
+        hs_mode = 0 if r['hs_max'] > 0 else (1 if wind_max > 0 else 2)
+        return hs_mode, (1 if wind_max >= 0 else 2)
 
     def stokes_drift(self, factor=1):
         try:
