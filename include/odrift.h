@@ -452,6 +452,36 @@ int odr_larval_update(odr_ctx *ctx, odr_particles *p, int stage_fraction_slot, i
  * slot has not been set.  No host synchronisation. */
 int odr_larval_migrate(odr_ctx *ctx, odr_particles *p, int hatched_slot, int length_slot, double fraction_swimming,
                        double dt_seconds, int direction);
+/* OpenBerg (models/openberg.py; Keghouche et al. 2010).  The element properties of IcebergObj (:45-100) that differ between
+ * elements in the property slots of odr_particles_set_property, float32 all six; the six coefficients (weight_coef, the four drag
+ * coefficients, wave_drag_coef) are scalars of a call. */
+enum { ODR_BERG_SAIL = 0, ODR_BERG_DRAFT = 1, ODR_BERG_LENGTH = 2, ODR_BERG_WIDTH = 3, ODR_BERG_X_VELOCITY = 4, ODR_BERG_Y_VELOCITY = 5 };
+/* OpenBerg.roll_over (models/openberg.py:587-614; Wagner et al. 2017) over the active set: length >= width, the berg rolls where
+ * width / (sail + draft) < sqrt(6 a (1 - a)), a = 900 / 1027, and thickness is split again into draft = H a and sail = H - draft --
+ * for EVERY element, as in the reference (csrc/odr_berg.hip.h).  ODR_ERR_STATE when a slot has not been set.  Enqueued on the
+ * context's stream; no host synchronisation. */
+int odr_berg_roll_over(odr_ctx *ctx, odr_particles *p, int sail_slot, int draft_slot, int length_slot, int width_slot);
+/* OpenBerg.advect_iceberg with surface currents (models/openberg.py:427-552; the forces :104-218) over the active set.  From the
+ * sampled float32 environment (current, wind; where sampled: Stokes drift, sea-floor depth, sea-surface height, wave height, sea-ice
+ * fraction and velocity -- otherwise the reference's fallbacks 10000 m and 0) and the four dimensions: grounding and degrounding
+ * of `moving`, V0 from the no-acceleration formula, then the momentum balance (ocean and wind drag, wave radiation, Coriolis, sea
+ * ice) integrated over dt_seconds with SciPy's solve_ivp (RK45, rtol 1e-3, atol 1e-6, scipy/integrate/_ivp/rk.py) over the velocity
+ * vector of ALL elements in float64: one error norm, summed in a fixed order, is read back per attempt.  Grounded elements get
+ * velocity 0; positions move along the geodesic as in odr_update_positions; the velocities go to the two velocity slots (float32).
+ * sea_surface_wave_from_direction [deg] and sea_ice_thickness [m] are scalars (they have no variable id); wave_rad, stokes_drift,
+ * coriolis, grounding: the configuration flags of the same names.  lat_is_float32: the reference's elements.lat is still a float32
+ * array (until the first update_positions of a run) and the Coriolis parameter a float32 value.  n_attempts / n_rejected (NULL: not reported): Dormand-Prince
+ * attempts made and rejected.  velocity_f64 (NULL: not reported): 2 n doubles on the host, the float64 velocities of the n active
+ * elements in device order (x of all, then y of all) as the positions were moved with them.  ODR_ERR_INVALID for a slot outside
+ * 0..8 or a NaN scalar.  ODR_ERR_STATE for slot 8 on a set whose ensemble diffusivity parks its member there, and when current or wind (or, with stokes_drift, the Stokes drift) have not been sampled,
+ * a dimension slot has not been set, or the solve fails (error norm not finite, step size below 10 ulp of t, more than 10000
+ * attempts).  After a failed solve the call is partly applied: `moving` holds the grounding and degrounding of this call, the
+ * positions and the two velocity slots are untouched.  Synchronises with the host once per attempt. */
+int odr_berg_advect(odr_ctx *ctx, odr_particles *p, int sail_slot, int draft_slot, int length_slot, int width_slot, int x_velocity_slot,
+                    int y_velocity_slot, double weight_coef, double water_form_drag_coef, double water_skin_drag_coef,
+                    double wind_form_drag_coef, double wind_skin_drag_coef, double wave_drag_coef, double wave_from_direction,
+                    double sea_ice_thickness, int wave_rad, int stokes_drift, int coriolis, int grounding, int lat_is_float32,
+                    double dt_seconds, int32_t *n_attempts, int32_t *n_rejected, double *velocity_f64);
 /* performance hint: apply vertical_advection (oceandrift.py:315-350) inside the next odr_vmix
  * kernel (OceanDrift.update() calls them back to back, oceandrift.py:201-208) */
 int odr_vmix_fuse_vertical_advection(odr_ctx *ctx, int at_surface);

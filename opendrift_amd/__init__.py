@@ -6,3 +6,10 @@ __version__ = '0.2.0'
 # Multi-process GPU work on this platform (RCCL, device memory shared between the ranks of a node) needs the dmabuf IPC mode;
 # the launch environment normally exports it already.
 _os.environ.setdefault('HSA_ENABLE_IPC_MODE_LEGACY', '0')
+
+
+def __getattr__(name):      # the model classes import the device binding: resolved on first use
+    if name == 'OpenBerg':
+        from .openberg import OpenBerg
+        return OpenBerg
+    raise AttributeError('module %r has no attribute %r' % (__name__, name))

@@ -135,6 +135,8 @@ _SIGNATURES = {
     'odr_resuspend': [_vp, _vp, C.c_float, _i64p],
     'odr_larval_update': [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double],
     'odr_larval_migrate': [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int],
+    'odr_berg_roll_over': [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int],
+    'odr_berg_advect': [_vp, _vp] + [C.c_int] * 6 + [C.c_double] * 8 + [C.c_int] * 5 + [C.c_double, _ip, _ip, _vp],
     'odr_vertical_advection': [_vp, _vp, C.c_double, C.c_int],
     'odr_vertical_buoyancy': [_vp, _vp, C.c_double],
     'odr_store_previous': [_vp, _vp],
@@ -234,6 +236,7 @@ DROPLETS = {'Johansen et al. (2015)': 1, 'Li et al. (2017)': 2}
 OIL_PROPERTIES = ['diameter', 'density', 'viscosity', 'oil_film_thickness', 'diameter_if_entrained']
 SEAFLOOR = {'none': 0, 'lift_to_seafloor': 1, 'deactivate': 2, 'previous': 3, 'settle': 4}     # include/odrift.h ODR_SEAFLOOR_*
 EGG_PROPERTIES = ['diameter', 'neutral_buoyancy_salinity', 'density', 'hatched']     # include/odrift.h ODR_EGG_*
+BERG_PROPERTIES = ['sail', 'draft', 'length', 'width', 'iceb_x_velocity', 'iceb_y_velocity']     # ODR_BERG_*
 LARVA_PROPERTIES = ['diameter', 'neutral_buoyancy_salinity', 'stage_fraction', 'hatched', 'length', 'weight', 'survival']     # ODR_LARVA_*
 
 

@@ -817,6 +817,35 @@ class Particles:
         check(self.lib.odr_larval_migrate(self.ctx.h, self.h, int(hatched_slot), int(length_slot), float(fraction_swimming),
                                           float(dt), int(direction)))
 
+    def berg_roll_over(self, sail_slot=0, draft_slot=1, length_slot=2, width_slot=3):
+        """OpenBerg.roll_over (openberg.py:587-614) over the active set: length >= width, bergs that fail the stability criterion of
+        Wagner et al. roll, and every berg's thickness is split again into draft and sail."""
+        check(self.lib.odr_berg_roll_over(self.ctx.h, self.h, int(sail_slot), int(draft_slot), int(length_slot), int(width_slot)))
+
+    def berg_advect(self, dt, weight_coef=1.0, water_form_drag_coef=0.25, water_skin_drag_coef=0.0055, wind_form_drag_coef=0.8,
+                    wind_skin_drag_coef=0.0022, wave_drag_coef=0.3, wave_from_direction=0.0, sea_ice_thickness=0.0, wave_rad=True,
+                    stokes_drift=False, coriolis=True, grounding=True, lat_is_float32=False, sail_slot=0, draft_slot=1, length_slot=2, width_slot=3,
+                    x_velocity_slot=4, y_velocity_slot=5, velocity_f64=False):
+        """OpenBerg.advect_iceberg with surface currents (openberg.py:427-552): grounding, the momentum balance of every berg
+        integrated over `dt` with SciPy's RK45 over the whole active set, positions and the two velocity slots.  Returns
+        (attempts, rejected attempts) of the solve; with velocity_f64 also the float64 velocities (x, y) of the active elements in
+        device order, as the positions were moved with them."""
+        na, nr = C.c_int32(), C.c_int32()
+        vel = np.empty((2, len(self)), np.float64) if velocity_f64 else None
+        # IcebergObj declares the coefficients float32: the reference's float64 arrays hold float32 values (0.8 is 0.800000011920929)
+        (weight_coef, water_form_drag_coef, water_skin_drag_coef, wind_form_drag_coef, wind_skin_drag_coef, wave_drag_coef) = (
+            float(np.float32(v)) for v in (weight_coef, water_form_drag_coef, water_skin_drag_coef, wind_form_drag_coef, wind_skin_drag_coef,
+                                           wave_drag_coef))
+        check(self.lib.odr_berg_advect(self.ctx.h, self.h, int(sail_slot), int(draft_slot), int(length_slot), int(width_slot),
+                                       int(x_velocity_slot), int(y_velocity_slot), float(weight_coef), float(water_form_drag_coef),
+                                       float(water_skin_drag_coef), float(wind_form_drag_coef), float(wind_skin_drag_coef),
+                                       float(wave_drag_coef), float(wave_from_direction), float(sea_ice_thickness), int(bool(wave_rad)),
+                                       int(bool(stokes_drift)), int(bool(coriolis)), int(bool(grounding)), int(bool(lat_is_float32)), float(dt), C.byref(na),
+                                       C.byref(nr), vel.ctypes.data_as(C.c_void_p) if velocity_f64 else None))
+        if velocity_f64:
+            return na.value, nr.value, vel[0], vel[1]
+        return na.value, nr.value
+
     def resuspend(self, threshold, count=True):
         """SedimentDrift.resuspension (sedimentdrift.py:118-126): settled elements (moving == 0) whose sampled current speed
         exceeds `threshold` (compared as float32, like NumPy 2) move again, 1 cm up.  Returns how many (count=False: None,
@@ -1045,7 +1074,7 @@ for _name in ('append', 'upload', 'env_sample', 'env_upload', 'env_add_noise', '
               'vmix', 'vmix_analytic', 'vmix_oil', 'vertical_advection', 'vertical_buoyancy', 'coastline', 'coastline_crossing',
               'increase_age', 'deactivate_missing', 'remap_status', 'seafloor', 'deactivate', 'deactivate_outside', 'compact',
               'compact_apply', 'sort_by_cell', 'store_previous', 'oil_prepare_mixing', 'env_coast_leeway', 'egg_terminal_velocity',
-              'resuspend', 'larval_update', 'larval_migrate'):
+              'resuspend', 'larval_update', 'larval_migrate', 'berg_roll_over', 'berg_advect'):
     setattr(Particles, _name, _touching(getattr(Particles, _name)))
 
 
