@@ -482,6 +482,43 @@ int odr_berg_advect(odr_ctx *ctx, odr_particles *p, int sail_slot, int draft_slo
                     double wind_form_drag_coef, double wind_skin_drag_coef, double wave_drag_coef, double wave_from_direction,
                     double sea_ice_thickness, int wave_rad, int stokes_drift, int coriolis, int grounding, int lat_is_float32,
                     double dt_seconds, int32_t *n_attempts, int32_t *n_rejected, double *velocity_f64);
+/* ShipDrift (models/shipdrift.py; Soergaard & Vada 1998).  The element properties of ShipObject (:32-77) in the property slots of
+ * odr_particles_set_property, float32 all eight: length, height, draft, beam [m], wind_drag_coeff (Cf), water_drag_coeff (Cd),
+ * orientation (uint8 there: 0 left, 1 right of the downwind direction, held as 0.f / 1.f) and the index of the element's class in
+ * the class table (a small integer held exactly). */
+enum { ODR_SHIP_LENGTH = 0, ODR_SHIP_HEIGHT = 1, ODR_SHIP_DRAFT = 2, ODR_SHIP_BEAM = 3, ODR_SHIP_WIND_DRAG = 4, ODR_SHIP_WATER_DRAG = 5,
+       ODR_SHIP_ORIENTATION = 6, ODR_SHIP_CLASS = 7 };
+/* The class tables of ShipDrift on the device, kept with their count.  A class is a unique pair of the clipped float32 ratios
+ * (beam / length, draft / length) of :220-227; its table holds what the reference's two LinearNDInterpolator objects (:137-145)
+ * return for it at the 49 spectrum points omega = 2.25 + i (12 - 2.25) / 99 < 7 (:262-277): table[n_classes][49][2] doubles, F
+ * then D.  The caller evaluates the interpolators (the coefficient table wforce.dat is data of the reference).  ODR_ERR_INVALID
+ * for a NaN.  odr_ship_table_destroy waits for the context's stream. */
+typedef struct odr_ship_table odr_ship_table;
+int odr_ship_table_create(odr_ctx *ctx, const double *table, int n_classes, odr_ship_table **out);
+int odr_ship_table_classes(const odr_ship_table *table, int32_t *n_classes);
+int odr_ship_table_destroy(odr_ctx *ctx, odr_ship_table *table);
+/* ShipDrift.update (models/shipdrift.py:216-343) over the active set, ONE launch (csrc/odr_ship.hip.h): update_positions with the
+ * sampled float32 current (:230); wind force, 0 where the wind is calm (:234-245); the 100-point wave spectrum from period and
+ * height (:256-265) and the trapezoid integrals of force and damping over it, with the class table below omega = 7 and f = 0.5,
+ * d = 2 omega above (:267-287); the factors for long (Tm > 8.55) and medium (5.7 <= Tm <= 8.55) periods (:290-296); form drag,
+ * wave direction = wind direction (wave_dir_from_stokes 0) or Stokes drift direction (1) -+ 20 degrees by orientation
+ * (:299-317) -- the reference decides between the two for the whole call (both Stokes components have a maximum of exactly 0),
+ * the caller does; four damping iterations (:321-334); update_positions with the float64 drift velocity (:337-339); elements
+ * whose sampled land_binary_mask is 1 get status stranded_code (where it was 0) and moving = 0 (:342).  hs_mode: 0 wave height as
+ * sampled, 1 from the wind; tp_mode: 0 the wave period in the slot of ODR_VAR 13 as sampled, 3 from the wind as stored to the
+ * float32 environment -- the conventions of odr_stokes_drift / odr_oil_prepare_mixing.  A period of exactly 0 on an element (a
+ * reader that does not cover it) gives that element no waves (F_wave = beta2 = 0); the reference's replacement by the mean of
+ * the other elements' periods (physics_methods.py:936-939) is not built.  table: odr_ship_table_create's; the caller guarantees
+ * that every class index is below its class count (the kernel clamps, it does not report).  stranded_code: positive.
+ * ODR_ERR_INVALID for a slot outside 0..8 or given twice, a NaN dt_seconds, no table, a stranded_code <= 0, other modes.  ODR_ERR_STATE when a slot has
+ * not been set, for slot 8 on a set whose ensemble diffusivity parks its member there, and when current, wind or land mask -- or
+ * what the modes and wave_dir_from_stokes name -- have not been sampled.  intermediates_f64 (NULL: not reported): 10 n doubles on
+ * the host, for the n active elements in device order: F_wave and beta2 before the period factors, F_wave, beta2, the wave
+ * direction, F_total, uw_tot, uw_dir and the two components of the drift velocity (all n of one, then the next).  Enqueued on the
+ * context's stream; no host synchronisation unless intermediates_f64 is given. */
+int odr_ship_drift(odr_ctx *ctx, odr_particles *p, int length_slot, int height_slot, int draft_slot, int beam_slot, int wind_drag_slot,
+                   int water_drag_slot, int orientation_slot, int class_slot, const odr_ship_table *table, int hs_mode,
+                   int tp_mode, int wave_dir_from_stokes, int stranded_code, double dt_seconds, double *intermediates_f64);
 /* performance hint: apply vertical_advection (oceandrift.py:315-350) inside the next odr_vmix
  * kernel (OceanDrift.update() calls them back to back, oceandrift.py:201-208) */
 int odr_vmix_fuse_vertical_advection(odr_ctx *ctx, int at_surface);

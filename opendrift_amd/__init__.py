@@ -12,4 +12,7 @@ def __getattr__(name):      # the model classes import the device binding: resol
     if name == 'OpenBerg':
         from .openberg import OpenBerg
         return OpenBerg
+    if name == 'ShipDrift':
+        from .shipdrift import ShipDrift
+        return ShipDrift
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

@@ -137,6 +137,10 @@ _SIGNATURES = {
     'odr_larval_migrate': [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int],
     'odr_berg_roll_over': [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int],
     'odr_berg_advect': [_vp, _vp] + [C.c_int] * 6 + [C.c_double] * 8 + [C.c_int] * 5 + [C.c_double, _ip, _ip, _vp],
+    'odr_ship_table_create': [_vp, _dp, C.c_int, _P(_vp)],
+    'odr_ship_table_classes': [_vp, _ip],
+    'odr_ship_table_destroy': [_vp, _vp],
+    'odr_ship_drift': [_vp, _vp] + [C.c_int] * 8 + [_vp] + [C.c_int] * 4 + [C.c_double, _vp],
     'odr_vertical_advection': [_vp, _vp, C.c_double, C.c_int],
     'odr_vertical_buoyancy': [_vp, _vp, C.c_double],
     'odr_store_previous': [_vp, _vp],
@@ -237,6 +241,8 @@ OIL_PROPERTIES = ['diameter', 'density', 'viscosity', 'oil_film_thickness', 'dia
 SEAFLOOR = {'none': 0, 'lift_to_seafloor': 1, 'deactivate': 2, 'previous': 3, 'settle': 4}     # include/odrift.h ODR_SEAFLOOR_*
 EGG_PROPERTIES = ['diameter', 'neutral_buoyancy_salinity', 'density', 'hatched']     # include/odrift.h ODR_EGG_*
 BERG_PROPERTIES = ['sail', 'draft', 'length', 'width', 'iceb_x_velocity', 'iceb_y_velocity']     # ODR_BERG_*
+SHIP_PROPERTIES = ['length', 'height', 'draft', 'beam', 'wind_drag_coeff', 'water_drag_coeff', 'orientation', 'ship_class']     # ODR_SHIP_*
+SHIP_TABLE_ROWS = 49     # spectrum points below omega = 7 (odr_ship_table_create)
 LARVA_PROPERTIES = ['diameter', 'neutral_buoyancy_salinity', 'stage_fraction', 'hatched', 'length', 'weight', 'survival']     # ODR_LARVA_*
 
 

@@ -15,8 +15,15 @@ from ._abi import VARIABLES, check
 _dp, _fp, _ip = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int32)
 
 
-def _vid(v):
-    return v if isinstance(v, (int, np.integer)) else VARIABLES[v]
+def _vid(v, aliases=None):
+    """Device id of a variable name (ids pass through).  aliases: Context.slot_aliases."""
+    if isinstance(v, (int, np.integer)):
+        return v
+    if v in VARIABLES:
+        return VARIABLES[v]
+    if aliases and v in aliases:
+        return aliases[v]
+    raise KeyError(v)
 
 
 def _d(a, n=None):
@@ -108,9 +115,25 @@ class Context:
         check(self.lib.odr_ctx_create(device, seed, C.byref(self.h)))
         self.device = device
         self._grids = {}
+        # A variable without a device id of its own that rides the slot of another one ON THIS CONTEXT: {name: id}.  Empty unless
+        # a model opts in (ShipDrift: the Tm02 wave period in the peak period's slot); every other model's
+        # context keeps failing on such a name with a KeyError that names it.
+        self.slot_aliases = {}
         self.stage_math = 'exact'
         if os.environ.get('ODR_STAGE_MATH'):     # what-if runs of whole test / bench sessions: 'exact' | 'fast'
             self.set_stage_math(os.environ['ODR_STAGE_MATH'])
+
+    def _vid(self, v):
+        return _vid(v, self.slot_aliases)
+
+    def _block_ids(self, names):
+        """The ids of the variables of one block; two names that resolve to the same id (an alias and the variable whose slot
+        it rides) in one block raise: the later one would silently replace the earlier."""
+        ids = [self._vid(k) for k in names]
+        if len(set(ids)) != len(ids):
+            twice = [k for k, i in zip(names, ids) if ids.count(i) > 1]
+            raise ValueError('variables %s of one block resolve to the same device id' % twice)
+        return ids
 
     def close(self):
         if self.h:
@@ -131,7 +154,7 @@ class Context:
 
     # ---- sources ----
     def add_constant(self, values):
-        ids, pi = _i([_vid(k) for k in values])
+        ids, pi = _i([self._vid(k) for k in values])
         vals, pv = _d([float(v) for v in values.values()])
         sid = C.c_int32()
         check(self.lib.odr_source_constant(self.h, len(ids), pi, pv, C.byref(sid)))
@@ -153,7 +176,7 @@ class Context:
         return sid.value
 
     def add_oscillating(self, variable, amplitude, period_s, t0):
-        prm, pp = _d([_vid(variable), amplitude, period_s, t0])
+        prm, pp = _d([self._vid(variable), amplitude, period_s, t0])
         sid = C.c_int32()
         check(self.lib.odr_source_analytic(self.h, _abi.ANALYTIC_OSCILLATING, pp, 4, C.byref(sid)))
         return sid.value
@@ -217,7 +240,7 @@ class Context:
                 m = np.stack([np.ma.filled(a, np.nan) if isinstance(a, np.ma.MaskedArray) else np.asarray(a) for a in v]).astype(np.float32)
                 known = self._grids[sid].setdefault('members', {})
                 if known.get(k) != len(v):
-                    check(self.lib.odr_source_set_members(self.h, sid, _vid(k), len(v)))
+                    check(self.lib.odr_source_set_members(self.h, sid, self._vid(k), len(v)))
                     known[k] = len(v)
                 v = np.ascontiguousarray(m.reshape((-1,) + m.shape[-2:]))
             out[k] = v
@@ -228,7 +251,7 @@ class Context:
         _ensemble_arrays does for a list of member arrays; a sharded run receives the stack itself)."""
         known = self._grids[sid].setdefault('members', {})
         if known.get(variable) != members:
-            check(self.lib.odr_source_set_members(self.h, sid, _vid(variable), int(members)))
+            check(self.lib.odr_source_set_members(self.h, sid, self._vid(variable), int(members)))
             known[variable] = members
 
     def _content_ids(self, sid, slot, given):
@@ -238,7 +261,7 @@ class Context:
         than the gathers it saves)."""
         given = {k: v for k, v in (given or {}).items() if v}
         if given:
-            (va, pv), ia = _i([_vid(k) for k in given]), np.asarray(list(given.values()), dtype=np.uint64)
+            (va, pv), ia = _i([self._vid(k) for k in given]), np.asarray(list(given.values()), dtype=np.uint64)
             check(self.lib.odr_block_set_content_ids(self.h, sid, slot, len(given), pv, ia.ctypes.data_as(C.POINTER(C.c_uint64))))
 
     def upload_block(self, sid, slot, t_epoch, arrays, content_ids=None):
@@ -247,7 +270,7 @@ class Context:
         g = self._grids[sid]
         arrays = self._ensemble_arrays(sid, arrays)
         names = list(arrays)
-        ids, pi = _i([_vid(k) for k in names])
+        ids, pi = _i(self._block_ids(names))
         keep = [np.ascontiguousarray(np.ma.filled(arrays[k], np.nan) if isinstance(arrays[k], np.ma.MaskedArray)
                                      else arrays[k], dtype=np.float32) for k in names]
         for a in keep:
@@ -266,7 +289,7 @@ class Context:
         g = self._grids[sid]
         dev_ptrs = self._ensemble_arrays(sid, dev_ptrs)
         names = list(dev_ptrs)
-        ids, pi = _i([_vid(k) for k in names])
+        ids, pi = _i(self._block_ids(names))
         keep = {k: np.ascontiguousarray(np.ma.filled(v, np.nan) if isinstance(v, np.ma.MaskedArray) else v, dtype=np.float32)
                 for k, v in dev_ptrs.items() if not isinstance(v, (int, np.integer))}
         nzs, pn = _i([(keep[k].shape[0] if keep[k].ndim == 3 else 1) if k in keep else var_nz[k] for k in names])
@@ -283,7 +306,7 @@ class Context:
         g = self._grids[sid]
         arrays = self._ensemble_arrays(sid, arrays)
         names = list(arrays)
-        ids, pi = _i([_vid(k) for k in names])
+        ids, pi = _i(self._block_ids(names))
         keep = {k: np.ascontiguousarray(np.ma.filled(v, np.nan) if isinstance(v, np.ma.MaskedArray) else v, dtype=np.float32)
                 for k, v in arrays.items() if not isinstance(v, (int, np.integer))}
         nzs, pn = _i([(keep[k].shape[0] if keep[k].ndim == 3 else 1) if k in keep else var_nz[k] for k in names])
@@ -300,7 +323,7 @@ class Context:
         elsewhere; shapes: {variable: shape} on every rank (the order of its keys is the order of the level's variables)."""
         g = self._grids[sid]
         names = list(shapes)
-        ids, pi = _i([_vid(k) for k in names])
+        ids, pi = _i(self._block_ids(names))
         nzs, pn = _i([(int(shapes[k][0]) if len(shapes[k]) == 3 else 1) for k in names])
         xy8, px = _d(g['xy8'])
         keep, ptrs = None, None
@@ -379,7 +402,7 @@ class Context:
 
     def bind(self, variable, source_ids, fallback=np.nan):
         ids, pi = _i(list(source_ids)) if len(source_ids) else (None, None)
-        check(self.lib.odr_env_bind(self.h, _vid(variable), len(source_ids), pi,
+        check(self.lib.odr_env_bind(self.h, self._vid(variable), len(source_ids), pi,
                                     np.nan if fallback is None else float(fallback)))
 
     def history(self, n_trajectories, n_times, variables, id_base=0):
@@ -487,7 +510,7 @@ class Particles:
 
     # ---- hot-path stages ----
     def env_sample(self, variables, t_epoch, download=False):
-        ids, pi = _i([_vid(v) for v in variables])
+        ids, pi = _i([self.ctx._vid(v) for v in variables])
         if download:
             n = len(self)
             outs = [np.empty(n, np.float32) for _ in variables]
@@ -498,12 +521,12 @@ class Particles:
 
     def env_download(self, variable):
         out = np.empty(len(self), np.float32)
-        check(self.lib.odr_env_download(self.ctx.h, self.h, _vid(variable), out.ctypes.data_as(_fp)))
+        check(self.lib.odr_env_download(self.ctx.h, self.h, self.ctx._vid(variable), out.ctypes.data_as(_fp)))
         return out
 
     def env_upload(self, variable, values):
         a, p = _f(values, len(self))
-        check(self.lib.odr_env_upload(self.ctx.h, self.h, _vid(variable), p))
+        check(self.lib.odr_env_upload(self.ctx.h, self.h, self.ctx._vid(variable), p))
 
     def env_add_noise(self, var_x, var_y, std, step=0, normals=None, uniform=False):
         """drift:current_uncertainty / wind_uncertainty (normal) or drift:current_uncertainty_uniform (uniform=True) on
@@ -512,10 +535,10 @@ class Particles:
         dist = _abi.NOISE_UNIFORM if uniform else _abi.NOISE_NORMAL
         if normals is not None:
             (ax, px), (ay, py) = _d(self._host_order(normals[0]), n), _d(self._host_order(normals[1]), n)
-            check(self.lib.odr_env_add_noise(self.ctx.h, self.h, _vid(var_x), _vid(var_y), float(std), dist,
+            check(self.lib.odr_env_add_noise(self.ctx.h, self.h, self.ctx._vid(var_x), self.ctx._vid(var_y), float(std), dist,
                                              _abi.RNG_HOST, px, py, step))
         else:
-            check(self.lib.odr_env_add_noise(self.ctx.h, self.h, _vid(var_x), _vid(var_y), float(std), dist,
+            check(self.lib.odr_env_add_noise(self.ctx.h, self.h, self.ctx._vid(var_x), self.ctx._vid(var_y), float(std), dist,
                                              _abi.RNG_DEVICE, None, None, step))
 
     def set_advect_noise(self, std_normal=0.0, std_uniform=0.0, step=0, stage_draws=None, main_draws=None):
@@ -553,7 +576,7 @@ class Particles:
         if s < 0:
             raise ValueError('Drift scheme not recognised: ' + str(scheme))
         a = coastline if isinstance(coastline, int) else _abi.COAST[coastline]
-        ids, pi = _i([_vid(v) for v in variables])
+        ids, pi = _i([self.ctx._vid(v) for v in variables])
         n = C.c_int64()
         ex = None
         if seafloor or age_dt or missing_code or main_noise or vmix:
@@ -667,7 +690,7 @@ class Particles:
         env_coast_leeway() + compact() is the same sequence either way.  Returns the number of elements on land.
         split='return': in that case nothing more is done here and (elements on land, True) comes back -- the caller compacts
         (after whatever it does between coastline and update) and calls leeway() itself; (elements on land, False) otherwise."""
-        ids, pi = _i([_vid(v) for v in variables])
+        ids, pi = _i([self.ctx._vid(v) for v in variables])
         nhit = C.c_int64()
         if missing_code:     # report_missing_variables inside the call (status of an element without data)
             check(self.lib.odr_leeway_set_missing_code(self.ctx.h, int(missing_code)))
@@ -846,6 +869,33 @@ class Particles:
             return na.value, nr.value, vel[0], vel[1]
         return na.value, nr.value
 
+    SHIP_INTERMEDIATES = ('F_wave_b', 'beta2_b', 'F_wave', 'beta2', 'wave_dir', 'F_total', 'uw_tot', 'uw_dir', 'velocity_u', 'velocity_v')
+
+    def ship_table(self, table):
+        """The class tables of ShipDrift on the device (odr_ship_table_create): table[n_classes][49][2] float64, F and D of the
+        reference's interpolators at the 49 spectrum points below omega = 7.  Returns a ShipTable (free it with close())."""
+        return ShipTable(self.ctx, table)
+
+    def ship_drift(self, dt, table, hs_mode=1, tp_mode=3, wave_dir_from_stokes=False, stranded_code=1, length_slot=0, height_slot=1,
+                   draft_slot=2, beam_slot=3, wind_drag_slot=4, water_drag_slot=5, orientation_slot=6, class_slot=7, check_classes=True,
+                   intermediates=False):
+        """ShipDrift.update (shipdrift.py:216-343) over the active set in one launch: the move with the current, wind force, wave
+        force and damping from the spectrum and the class tables, the four damping iterations, the move with the drift velocity,
+        stranding.  table: a ShipTable.  check_classes: every element's class index is read back and checked against the table
+        (one download); a caller that built the indices with the table passes False.  intermediates: returns the float64
+        intermediates of the active elements in device order, {name: array} (the host waits for the launch)."""
+        if check_classes and len(self):
+            k = self.get_property(class_slot)
+            if not (np.all(k == np.floor(k)) and k.min() >= 0 and k.max() < table.n_classes):
+                raise ValueError('ship_drift: class indices %s..%s, the table has %d classes' % (k.min(), k.max(), table.n_classes))
+        rep = np.empty((len(self.SHIP_INTERMEDIATES), len(self)), np.float64) if intermediates else None
+        check(self.lib.odr_ship_drift(self.ctx.h, self.h, int(length_slot), int(height_slot), int(draft_slot), int(beam_slot),
+                                      int(wind_drag_slot), int(water_drag_slot), int(orientation_slot), int(class_slot), table.ptr,
+                                      int(hs_mode), int(tp_mode), int(bool(wave_dir_from_stokes)), int(stranded_code),
+                                      float(dt), rep.ctypes.data_as(C.c_void_p) if intermediates else None))
+        if intermediates:
+            return dict(zip(self.SHIP_INTERMEDIATES, rep))
+
     def resuspend(self, threshold, count=True):
         """SedimentDrift.resuspension (sedimentdrift.py:118-126): settled elements (moving == 0) whose sampled current speed
         exceeds `threshold` (compared as float32, like NumPy 2) move again, 1 cm up.  Returns how many (count=False: None,
@@ -882,7 +932,7 @@ class Particles:
 
     def deactivate_missing(self, variables, status_code):
         """report_missing_variables (basemodel/__init__.py:2501-2515) on the last environment sample."""
-        ids, pi = _i([_vid(v) for v in variables])
+        ids, pi = _i([self.ctx._vid(v) for v in variables])
         n = C.c_int64()
         check(self.lib.odr_deactivate_missing(self.ctx.h, self.h, len(ids), pi, int(status_code), C.byref(n)))
         return n.value
@@ -1074,7 +1124,7 @@ for _name in ('append', 'upload', 'env_sample', 'env_upload', 'env_add_noise', '
               'vmix', 'vmix_analytic', 'vmix_oil', 'vertical_advection', 'vertical_buoyancy', 'coastline', 'coastline_crossing',
               'increase_age', 'deactivate_missing', 'remap_status', 'seafloor', 'deactivate', 'deactivate_outside', 'compact',
               'compact_apply', 'sort_by_cell', 'store_previous', 'oil_prepare_mixing', 'env_coast_leeway', 'egg_terminal_velocity',
-              'resuspend', 'larval_update', 'larval_migrate', 'berg_roll_over', 'berg_advect'):
+              'resuspend', 'larval_update', 'larval_migrate', 'berg_roll_over', 'berg_advect', 'ship_drift'):
     setattr(Particles, _name, _touching(getattr(Particles, _name)))
 
 
@@ -1099,6 +1149,31 @@ for _name in ('download', 'download_f32', 'env_download', 'get_property', 'reduc
     setattr(Particles, _name, _reading(getattr(Particles, _name)))
 
 
+class ShipTable:
+    """Device copy of ShipDrift's class tables (odr_ship_table_create / _destroy)."""
+
+    def __init__(self, ctx, table):
+        t = np.ascontiguousarray(table, dtype=np.float64)
+        if t.ndim != 3 or t.shape[1:] != (_abi.SHIP_TABLE_ROWS, 2) or t.shape[0] < 1:
+            raise ValueError('ship class table of shape %s, expected (n_classes, %d, 2)' % (t.shape, _abi.SHIP_TABLE_ROWS))
+        self.ctx, self.ptr = ctx, C.c_void_p()
+        check(ctx.lib.odr_ship_table_create(ctx.h, t.ctypes.data_as(_dp), t.shape[0], C.byref(self.ptr)))
+        n = C.c_int32()
+        check(ctx.lib.odr_ship_table_classes(self.ptr, C.byref(n)))
+        self.n_classes = n.value      # (the library keeps the count with the table)
+
+    def close(self):
+        if self.ptr and self.ctx.h:
+            self.ctx.lib.odr_ship_table_destroy(self.ctx.h, self.ptr)
+        self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class History:
     """Device-resident float32 result buffer (state_to_buffer, basemodel/__init__.py:2084-2105,2384-2499):
     `variables` = element property names ('lon', 'lat', 'z', 'status', ...), environment variable names, or
@@ -1117,7 +1192,7 @@ class History:
             elif v in _abi.HIST:
                 codes.append(_abi.HIST[v])
             else:
-                codes.append(_vid(v))
+                codes.append(ctx._vid(v))
         a, pa = _i(codes)
         self.h = C.c_void_p()
         check(self.lib.odr_history_create(ctx.h, self.n_trajectories, self.n_times, len(codes), pa, C.byref(self.h)))
