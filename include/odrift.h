@@ -555,7 +555,15 @@ enum { ODR_SEAFLOOR_LIFT = 1, ODR_SEAFLOOR_DEACTIVATE = 2, ODR_SEAFLOOR_PREVIOUS
         * interact_with_seafloor() inside update() (oceandrift.py:364-368, :556-561): the element is put on the sea floor
         * and SETTLES -- moving = 0, status unchanged, it stays active and no mover moves it until odr_resuspend.
         * Accepted by odr_set_seafloor_action only (the main-loop interact_with_seafloor() never settles). */
-       ODR_SEAFLOOR_SETTLE = 4 };
+       ODR_SEAFLOOR_SETTLE = 4,
+       /* RadionuclideDrift.bottom_interaction (models/radionuclides.py:912-942) behind the same hook: an element below the
+        * sea floor is lifted onto it, and SETTLES (as above) only if its species -- the small integer held in a float32
+        * property slot -- is in a set, given as a bit mask over the species numbers 0 .. 6; any other element is only lifted
+        * and keeps mixing.  The status_code of odr_set_seafloor_action carries both: ODR_SEAFLOOR_SPECIES(slot, mask).  The
+        * species number itself is changed by odr_radio_resuspend.  Accepted by odr_set_seafloor_action only; odr_vmix* and
+        * odr_vertical_buoyancy return ODR_ERR_STATE when the slot has not been set on their particle set. */
+       ODR_SEAFLOOR_SETTLE_SPECIES = 5 };
+#define ODR_SEAFLOOR_SPECIES(slot, mask) ((int32_t)(((mask) & 127) | ((slot) << 16)))
 int odr_seafloor_action(odr_ctx *ctx, odr_particles *p, int action, int32_t status_code, int64_t *n_below);
 /* The reference calls interact_with_seafloor() again INSIDE update(): from vertical_buoyancy (oceandrift.py:362-368)
  * and from every sub-step of vertical_mixing (:555-559).  This sets what odr_vertical_buoyancy / odr_vmix* do with an
@@ -567,6 +575,64 @@ int odr_set_seafloor_action(odr_ctx *ctx, int action, int32_t status_code);
  * moving = 1 and z + 0.01 (float64).  *n_resuspended: how many (NULL: not counted, no host synchronisation).
  * ODR_ERR_STATE when the two current components have not been sampled (csrc/odr_sediment.hip.h). */
 int odr_resuspend(odr_ctx *ctx, odr_particles *p, float threshold, int64_t *n_resuspended);
+/* RadionuclideDrift (models/radionuclides.py).  Element properties in the float32 property slots: diameter,
+ * neutral_buoyancy_salinity, density, and `specie` (int32 there): a small integer held exactly. */
+enum { ODR_RADIO_DIAMETER = 0, ODR_RADIO_NEUTRAL_BUOYANCY_SALINITY = 1, ODR_RADIO_DENSITY = 2, ODR_RADIO_SPECIE = 3 };
+enum { ODR_RADIO_MAX_SPECIES = 7, ODR_RADIO_MAX_SALINITY_INTERVALS = 4 };
+/* What init_species / init_transfer_rates (:233-278, :512-654) and the configuration give the device.  Species numbers are -1
+ * where the setup has none: either lmm (the four 'LMM + ...' setups) or lmmcation, lmmanion and polymer ('LMM + Colloid + Rev')
+ * are set.  rates[a][in][out] in 1/s, a = 0 for the LMM setups (nsalinity 1), the four salinity intervals (0,1], (1,10],
+ * (10,20], (20,inf) of :597-644 for the other (nsalinity 4); only [nsalinity][nspecies][nspecies] is read.  lognormal: 0
+ * radionuclide:particlesize_distribution 'normal', 1 'lognormal'.  The remaining members are the radionuclide:* configuration
+ * values of the same names (diameter_uncertainty: particle_diameter_uncertainty). */
+typedef struct {
+  int32_t nspecies, nsalinity, lognormal;
+  int32_t lmm, lmmcation, lmmanion, polymer, particle_rev, sediment_rev, particle_slow, sediment_slow, particle_irrev, sediment_irrev;
+  double rates[4 * 7 * 7];
+  double layer_thick, particle_diameter, dissolved_diameter, diameter_uncertainty, desorption_depth, desorption_depth_uncert,
+      resuspension_depth, resuspension_depth_uncert, resuspension_critvel;
+} odr_radio_setup;
+/* The setup on the device, with the counters ntransformations[in][out] (:528), which the launches below add to.
+ * ODR_ERR_INVALID for species numbers outside the table, a rate that is negative or not finite, a NaN.
+ * odr_radio_counts: counts49[in * 7 + out] since creation or the last reset (reset != 0 clears them); waits for the context's
+ * stream; ODR_ERR_STATE (after filling counts49) when a launch met an element whose species number is outside 0 .. nspecies - 1
+ * -- such an element is left unchanged, nothing is read outside the table.  odr_radio_destroy waits for the context's stream. */
+typedef struct odr_radio odr_radio;
+int odr_radio_create(odr_ctx *ctx, const odr_radio_setup *setup, odr_radio **out);
+int odr_radio_counts(odr_ctx *ctx, odr_radio *radio, int64_t *counts49, int reset);
+int odr_radio_destroy(odr_ctx *ctx, odr_radio *radio);
+/* update_transfer_rates + update_speciation (models/radionuclides.py:728-810) with update_radionuclide_diameter (:866-902, and
+ * set_init_diameter :281-315), sorption_to_sediments (:814-830) and desorption_from_sediments (:834-860), over the active set in
+ * ONE launch (csrc/odr_radio.hip.h).  The element's row of the rate table -- by species, for nsalinity 4 also by
+ * np.searchsorted([0,1,10,20], S) - 1 of the sampled float32 salinity, S <= 0 taking the last table as the index -1 does there;
+ * for an LMM element the rate to sediment is 0 further than layer_thick above the sea bed and the rate to particles is scaled by
+ * conc3 / 1e-3, conc3 being the sampled float32 variable conc3_var (the variable has no id of its own: the caller names the slot
+ * it rides); p = 1 - exp(-k dt) in float64; the element transforms when u1 < sum(p), to species
+ * searchsorted(cumsum(p / sum(p)), u2), clamped to the last species with p > 0 where rounding pushes it past the table (the
+ * reference stores the number nspecies there and fails on it a step later).  A new particle / dissolved element gets
+ * particle_diameter / dissolved_diameter + noise (lognormal: * noise) rounded to float32, without the reference's clipping,
+ * which assigns into a copy; a diameter of 0 gets none.  LMM(cation) -> sediment reversible: z = -depth, moving = 0; the reverse:
+ * z = float32(-depth + desorption_depth) + N(0, desorption_depth_uncert), moving = 1, possibly below the sea floor as there.
+ * z > 0 becomes 0 (the reference does that only in a step in which some element transforms).  Only elements that change are
+ * written.  ODR_RNG_HOST: u1, u2 uniform in [0, 1), diameter_noise and depth_noise the values the reference ADDS (or multiplies
+ * with), one per element of the active set in device order; ODR_RNG_DEVICE (the four pointers are not read): Philox streams keyed
+ * by (ID, step).  ODR_ERR_STATE when a slot has not been set or depth, conc3 (LMM setups) or salinity (nsalinity 4) have not been
+ * sampled.  No host synchronisation in ODR_RNG_DEVICE mode. */
+int odr_radio_speciation(odr_ctx *ctx, odr_particles *p, odr_radio *radio, int specie_slot, int diameter_slot, int32_t conc3_var,
+                         double dt_seconds, int rng_mode, const double *u1, const double *u2, const double *diameter_noise,
+                         const double *depth_noise, uint64_t step);
+/* update_terminal_velocity without profiles (models/radionuclides.py:665-721): Stokes' law W = (1/mu)(1/18) g d^2 (rho_w - rho)
+ * from the sampled float32 temperature and salinity and the diameter and density slots, times moving, in the reference's
+ * float32 operation order.  ODR_ERR_STATE when temperature or salinity have not been sampled or a slot has not been set. */
+int odr_radio_terminal_velocity(odr_ctx *ctx, odr_particles *p, int diameter_slot, int density_slot);
+/* bottom_interaction's change of species (models/radionuclides.py:912-942) for the elements ODR_SEAFLOOR_SETTLE_SPECIES has
+ * settled -- moving == 0 with a particle species: the matching sediment species, counted -- and then resuspension (:946-997):
+ * every element with z <= -depth and float32 sqrt(u^2 + v^2) >= resuspension_critvel, whatever its species, gets moving = 1 and
+ * z = float32(-depth + resuspension_depth) + N(0, resuspension_depth_uncert); z > 0 becomes 0; the three sediment species become
+ * the matching particle species, counted, with the diameter update of odr_radio_speciation.  ODR_RNG_HOST: the two noise arrays
+ * as there.  ODR_ERR_STATE when the current or the depth have not been sampled or a slot has not been set. */
+int odr_radio_resuspend(odr_ctx *ctx, odr_particles *p, odr_radio *radio, int specie_slot, int diameter_slot, int rng_mode,
+                        const double *diameter_noise, const double *depth_noise, uint64_t step);
 /* number of active-set elements currently flagged with status_code (not yet removed by odr_compact) */
 int odr_particles_count_status(odr_ctx *ctx, odr_particles *p, int32_t status_code, int64_t *n);
 /* status_categories grow in the order in which reasons FIRST OCCUR (deactivate_elements, :1778-1781): a caller hands

@@ -15,4 +15,7 @@ def __getattr__(name):      # the model classes import the device binding: resol
     if name == 'ShipDrift':
         from .shipdrift import ShipDrift
         return ShipDrift
+    if name == 'RadionuclideDrift':
+        from .radionuclides import RadionuclideDrift
+        return RadionuclideDrift
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

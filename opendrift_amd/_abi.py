@@ -48,6 +48,15 @@ class StepExtras(C.Structure):   # odr_step_extras
                 ('vmix', C.c_int32), ('vmix_at_surface', C.c_int32), ('vmix_vadv', C.c_int32), ('pad', C.c_int32),
                 ('vmix_dt_mix', C.c_double), ('vmix_step', C.c_uint64)]
 ANALYTIC_DOUBLE_GYRE, ANALYTIC_OSCILLATING = 1, 2
+RADIO_MAX_SPECIES, RADIO_MAX_SALINITY_INTERVALS = 7, 4     # ODR_RADIO_MAX_*
+
+
+class RadioSetup(C.Structure):   # odr_radio_setup
+    _fields_ = [(k, C.c_int32) for k in ('nspecies', 'nsalinity', 'lognormal', 'lmm', 'lmmcation', 'lmmanion', 'polymer', 'particle_rev',
+                                         'sediment_rev', 'particle_slow', 'sediment_slow', 'particle_irrev', 'sediment_irrev')] + \
+        [('rates', C.c_double * (RADIO_MAX_SALINITY_INTERVALS * RADIO_MAX_SPECIES * RADIO_MAX_SPECIES))] + \
+        [(k, C.c_double) for k in ('layer_thick', 'particle_diameter', 'dissolved_diameter', 'diameter_uncertainty', 'desorption_depth',
+                                   'desorption_depth_uncert', 'resuspension_depth', 'resuspension_depth_uncert', 'resuspension_critvel')]
 
 
 class ProjDesc(C.Structure):
@@ -141,6 +150,12 @@ _SIGNATURES = {
     'odr_ship_table_classes': [_vp, _ip],
     'odr_ship_table_destroy': [_vp, _vp],
     'odr_ship_drift': [_vp, _vp] + [C.c_int] * 8 + [_vp] + [C.c_int] * 4 + [C.c_double, _vp],
+    'odr_radio_create': [_vp, _vp, _P(_vp)],
+    'odr_radio_counts': [_vp, _vp, _i64p, C.c_int],
+    'odr_radio_destroy': [_vp, _vp],
+    'odr_radio_speciation': [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int32, C.c_double, C.c_int, _dp, _dp, _dp, _dp, C.c_uint64],
+    'odr_radio_terminal_velocity': [_vp, _vp, C.c_int, C.c_int],
+    'odr_radio_resuspend': [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_uint64],
     'odr_vertical_advection': [_vp, _vp, C.c_double, C.c_int],
     'odr_vertical_buoyancy': [_vp, _vp, C.c_double],
     'odr_store_previous': [_vp, _vp],
@@ -238,7 +253,8 @@ NOISE_NORMAL, NOISE_UNIFORM = 0, 1
 DIFFUSIVITY = {'windspeed_Large1994': 1, 'windspeed_Sundby1983': 2}
 DROPLETS = {'Johansen et al. (2015)': 1, 'Li et al. (2017)': 2}
 OIL_PROPERTIES = ['diameter', 'density', 'viscosity', 'oil_film_thickness', 'diameter_if_entrained']
-SEAFLOOR = {'none': 0, 'lift_to_seafloor': 1, 'deactivate': 2, 'previous': 3, 'settle': 4}     # include/odrift.h ODR_SEAFLOOR_*
+SEAFLOOR = {'none': 0, 'lift_to_seafloor': 1, 'deactivate': 2, 'previous': 3, 'settle': 4, 'settle_species': 5}     # include/odrift.h ODR_SEAFLOOR_*
+RADIO_PROPERTIES = ['diameter', 'neutral_buoyancy_salinity', 'density', 'specie']     # ODR_RADIO_*
 EGG_PROPERTIES = ['diameter', 'neutral_buoyancy_salinity', 'density', 'hatched']     # include/odrift.h ODR_EGG_*
 BERG_PROPERTIES = ['sail', 'draft', 'length', 'width', 'iceb_x_velocity', 'iceb_y_velocity']     # ODR_BERG_*
 SHIP_PROPERTIES = ['length', 'height', 'draft', 'beam', 'wind_drag_coeff', 'water_drag_coeff', 'orientation', 'ship_class']     # ODR_SHIP_*

@@ -227,6 +227,13 @@ static inline int ensure_env(odr_ctx *c, odr_particles *p, int var) {
   return 0;
 }
 
+// ODR_SEAFLOOR_SETTLE_SPECIES reads the species from a property slot of the particle set the launch runs on
+static inline int seafloor_species_slot_ok(const odr_ctx *c, const odr_particles *p) {
+  if ((c->seafloor & 255) == ODR_SEAFLOOR_SETTLE_SPECIES && !p->aux[(c->seafloor >> 24) & 15])
+    return fail(ODR_ERR_STATE, "ODR_SEAFLOOR_SETTLE_SPECIES: property slot %d has not been set", (c->seafloor >> 24) & 15);
+  return 0;
+}
+
 static inline int scratch(odr_ctx *c, odr_particles *p, size_t bytes, void **out) {
   if (p->scratch_bytes < bytes) {
     SlowSpan sp("scratch: synchronize + hipFree + hipMalloc");

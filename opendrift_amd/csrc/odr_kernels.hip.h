@@ -58,6 +58,14 @@ struct PView {  // device pointers of the active set
   const int *rank;  // position among the present elements in ascending ID (ensemble member = rank % members), or null
 };
 
+// ODR_SEAFLOOR_SETTLE_SPECIES (sfl = 5 | species mask << 8 | property slot << 24): the sf_flags value 8 (bit 3) when element i is of a species
+// that settles where it meets the sea floor, else 0.  Read once per element, and only under that action.
+__device__ __forceinline__ int sf_species_flag(const PView &p, int sfl, long long i) {
+  if ((sfl & 255) != 5) return 0;
+  const int sp = (int)p.aux[(sfl >> 24) & 15][i];
+  return (sp >= 0 && sp < 7 && (((sfl >> 8) >> sp) & 1)) ? 8 : 0;
+}
+
 // OpenOil.advect_oil in sea ice (openoil.py:1182-1201; Nordam et al. 2019, Arneborg 2017), float32 like NumPy on the
 // float32 environment array: k_ice = (A - 0.3) / (0.8 - 0.3), 0 below 30 %, 1 above 80 %;
 // factor_stokes = (0.7 - A) / 0.7, 0 above 70 %
@@ -590,7 +598,7 @@ __device__ __forceinline__ void vmix_col_fill(const DevSource &s, const VMixDesc
 
 // The ntimes_mix random-walk sub-steps of one particle on its K column in LDS (oceandrift.py:505-565).  Returns the
 // new z; sf_flags: 1 deactivated on the sea floor, 2 moved back horizontally (general:seafloor_action), 4 settled
-// (ODR_SEAFLOOR_SETTLE: moving = 0, the element stays active).
+// (ODR_SEAFLOOR_SETTLE: moving = 0, the element stays active); in: the value 8 (bit 3), the element's species settles (sf_species_flag).
 struct VMixArgs {
   double dt, dt_mix_cfg;
   int mix_at_surface, rng_mode, sfl, pad;
@@ -729,6 +737,7 @@ __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, con
         z = (double)Zmin;                                // lift_to_seafloor / deactivate / settle
         if (act == 2) { sf_flags |= 1; moving = 0; wstep = 0.0; }
         else if (act == 4) { sf_flags |= 4; moving = 0; wstep = 0.0; }   // SedimentDrift.bottom_interaction (sedimentdrift.py:108-116)
+        else if (act == 5 && (sf_flags & 8)) { sf_flags |= 4; moving = 0; wstep = 0.0; }   // RadionuclideDrift.bottom_interaction (radionuclides.py:912-942): a particle species
       }
     }
   }
@@ -1853,7 +1862,7 @@ __global__ __launch_bounds__(BLOCK) void k_vmix(const DevWorld *__restrict__ W, 
   const double r = 1.0 / 3, ir = 1.0 / r;
   double z = p.z[i];
   int moving = p.moving[i];
-  int sf_flags = 0;   // 1: deactivated on the sea floor, 2: moved back horizontally (general:seafloor_action)
+  int sf_flags = sf_species_flag(p, sfl_in, i);   // 1: deactivated on the sea floor, 2: moved back horizontally (general:seafloor_action)
   const float Zmin = __fmul_rn(-1.f, __fadd_rn(p.env[VAR_DEPTH][i], p.env[VAR_SSH][i]));  // float32 (:408)
   // w*dt_mix*moving: dt_mix is a NumPy float64 scalar (np.sign, oceandrift.py:416) -> float64 product under NumPy 2
   double wstep = __dmul_rn(__dmul_rn((double)p.tv[i], dt_mix), (double)moving);
@@ -1915,6 +1924,7 @@ __global__ __launch_bounds__(BLOCK) void k_vmix(const DevWorld *__restrict__ W, 
         z = (double)Zmin;                                // lift_to_seafloor / deactivate / settle
         if (act == 2) { sf_flags |= 1; moving = 0; wstep = 0.0; }
         else if (act == 4) { sf_flags |= 4; moving = 0; wstep = 0.0; }   // SedimentDrift.bottom_interaction (sedimentdrift.py:108-116)
+        else if (act == 5 && (sf_flags & 8)) { sf_flags |= 4; moving = 0; wstep = 0.0; }   // RadionuclideDrift.bottom_interaction (radionuclides.py:912-942): a particle species
       }
     }
   }
@@ -1963,7 +1973,7 @@ __device__ __forceinline__ void vmix_col_particle(const DevSource &s, const PVie
   R0.key = mix_key(A.seed, A.step, id0); R0.q = make_uint4(0u, 0u, 0u, 0u); R0.primed = false;
   // the stream's first block behind the first gathers of the column: its arithmetic runs while they are in flight
   vmix_col_fill<NQ, TL, VM>(s, D, slon, slat, Kp, tid, [&]() { R0 = mix_rng_begin<VM>(A, id0); });
-  int sf_flags = 0;
+  int sf_flags = VM::sf_action(sfl & 255) == 5 ? sf_species_flag(p, sfl, i) : 0;
   const float Zmin = __fmul_rn(-1.f, __fadd_rn(dep0, ssh0));  // float32 (:408)
   double z = vmix_col_walk<NQ, VM>(s, nzp, Kp, gsh, tid, A, i, p.n, id0, z0, moving, Zmin, tv0, sf_flags, &R0);
   if (sf_flags & 1) {   // deactivate_elements(reason='seafloor') (basemodel/__init__.py:1774-1795)
@@ -2146,7 +2156,7 @@ __global__ __launch_bounds__(BLOCK, ODR_VWIN_WAVES) void k_vmix_win(const DevWor
     }
   };
   double z = z0;
-  int sf_flags = 0, it = 0;
+  int sf_flags = sf_species_flag(p, sfl, i), it = 0;
   // one random-walk sub-step on the window (vmix_col_walk's loop body; oceandrift.py:531-559); false: the particle is on a
   // level outside the window and nothing was done.  x: the sub-step's 24-bit draw (ODR_RNG_DEVICE)
   auto substep = [&](int lv0, unsigned x) -> bool {
@@ -2177,6 +2187,7 @@ __global__ __launch_bounds__(BLOCK, ODR_VWIN_WAVES) void k_vmix_win(const DevWor
         z = (double)Zmin;                                // lift_to_seafloor / deactivate / settle
         if (act == 2) { sf_flags |= 1; moving = 0; wstep = 0.0; }
         else if (act == 4) { sf_flags |= 4; moving = 0; wstep = 0.0; }   // SedimentDrift.bottom_interaction (sedimentdrift.py:108-116)
+        else if (act == 5 && (sf_flags & 8)) { sf_flags |= 4; moving = 0; wstep = 0.0; }   // RadionuclideDrift.bottom_interaction (radionuclides.py:912-942): a particle species
       }
     }
     return true;
@@ -2293,7 +2304,7 @@ __global__ __launch_bounds__(BLOCK) void k_vmix_wind(PView p, const double *__re
   const double r = 1.0 / 3, ir = 1.0 / r;
   double z = p.z[i];
   int moving = p.moving[i];
-  int sf_flags = 0;   // 1: deactivated on the sea floor, 2: moved back horizontally (general:seafloor_action)
+  int sf_flags = sf_species_flag(p, sfl, i);   // 1: deactivated on the sea floor, 2: moved back horizontally (general:seafloor_action)
   const float Zmin = __fmul_rn(-1.f, __fadd_rn(p.env[VAR_DEPTH][i], p.env[VAR_SSH][i]));
   double wstep = __dmul_rn(__dmul_rn((double)p.tv[i], dt_mix), (double)moving);
   const MixKey st = mix_key(seed, step, rng_mode == 0 ? p.id[i] : 0);
@@ -2339,6 +2350,7 @@ __global__ __launch_bounds__(BLOCK) void k_vmix_wind(PView p, const double *__re
         z = (double)Zmin;                                // lift_to_seafloor / deactivate / settle
         if (act == 2) { sf_flags |= 1; moving = 0; wstep = 0.0; }
         else if (act == 4) { sf_flags |= 4; moving = 0; wstep = 0.0; }   // SedimentDrift.bottom_interaction (sedimentdrift.py:108-116)
+        else if (act == 5 && (sf_flags & 8)) { sf_flags |= 4; moving = 0; wstep = 0.0; }   // RadionuclideDrift.bottom_interaction (radionuclides.py:912-942): a particle species
       }
     }
   }
@@ -2373,7 +2385,8 @@ __global__ __launch_bounds__(BLOCK) void k_vadvect(PView p, double dt, int at_su
 }
 
 // vertical_buoyancy (oceandrift.py:352-368); elements below the sea floor "interact_with_seafloor" again, here
-// inside update(): sfl = action | status_code << 8 (0 none, 1 lift_to_seafloor, 2 deactivate, 3 previous, 4 settle)
+// inside update(): sfl = action | status_code << 8 (0 none, 1 lift_to_seafloor, 2 deactivate, 3 previous, 4 settle, 5 settle by
+// species: sf_species_flag)
 __global__ __launch_bounds__(BLOCK) void k_vbuoy(PView p, double dt, int sfl) {
   long long i = (long long)blockIdx.x * BLOCK + threadIdx.x;
   if (i >= p.n) return;
@@ -2392,6 +2405,7 @@ __global__ __launch_bounds__(BLOCK) void k_vbuoy(PView p, double dt, int sfl) {
         if (p.status[i] == 0) p.status[i] = sfl >> 8;
         p.moving[i] = 0;
       } else if (act == 4) p.moving[i] = 0;   // settle (sedimentdrift.py:108-116): the element stays active
+      else if (act == 5 && sf_species_flag(p, sfl, i)) p.moving[i] = 0;   // a particle species settles (radionuclides.py:912-942)
     }
   }
   p.z[i] = z;

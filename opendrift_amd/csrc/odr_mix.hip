@@ -47,6 +47,7 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
   p->epoch++;  // invalidates the cached reductions (reduce())
   REQUIRE(dt_mix > 0 && dt != 0, "bad time steps");
   if (!p->env[VAR_DEPTH]) return fail(ODR_ERR_STATE, "sea_floor_depth_below_sea_level has not been sampled");
+  if (int rs = seafloor_species_slot_ok(c, p)) return rs;
   int rc = ensure_env(c, p, VAR_SSH);
   if (rc) return rc;
   if ((rc = flush_world(c))) return rc;
@@ -179,6 +180,7 @@ int odr_vmix_wind_profile(odr_ctx *c, odr_particles *p, int model, double backgr
   REQUIRE(dt_mix > 0 && dt != 0, "bad time steps");
   if (!p->env[VAR_DEPTH]) return fail(ODR_ERR_STATE, "sea_floor_depth_below_sea_level has not been sampled");
   int rc;
+  if ((rc = seafloor_species_slot_ok(c, p))) return rc;
   for (int v : {VAR_SSH, VAR_XWIND, VAR_YWIND, VAR_MLD})
     if ((rc = ensure_env(c, p, v))) return rc;
   if ((rc = flush_world(c))) return rc;

@@ -1989,6 +1989,7 @@ int odr_vertical_buoyancy(odr_ctx *c, odr_particles *p, double dt) {
   p->status_epoch++;
   p->epoch++;  // invalidates the cached reductions (reduce())
   if (!p->env[VAR_DEPTH]) return fail(ODR_ERR_STATE, "sea_floor_depth_below_sea_level has not been sampled");
+  if (int rs = seafloor_species_slot_ok(c, p)) return rs;
   int rc = ensure_env(c, p, VAR_SSH);
   if (rc) return rc;
   if (p->n == 0) return 0;
@@ -2101,7 +2102,13 @@ int odr_seafloor_action(odr_ctx *c, odr_particles *p, int action, int32_t code, 
 }
 
 int odr_set_seafloor_action(odr_ctx *c, int action, int32_t code) {
-  REQUIRE(action >= 0 && action <= ODR_SEAFLOOR_SETTLE, "unknown seafloor action %d", action);
+  REQUIRE(action >= 0 && action <= ODR_SEAFLOOR_SETTLE_SPECIES, "unknown seafloor action %d", action);
+  if (action == ODR_SEAFLOOR_SETTLE_SPECIES) {   // code = ODR_SEAFLOOR_SPECIES(slot, mask): 5 | mask << 8 | slot << 24 (sf_species_flag)
+    const int slot = (int)code >> 16, mask = (int)code & 0xffff;
+    REQUIRE(slot >= 0 && slot < 9 && mask < 128, "ODR_SEAFLOOR_SETTLE_SPECIES: property slot %d, species mask 0x%x", slot, mask);
+    c->seafloor = action | (mask << 8) | (slot << 24);
+    return 0;
+  }
   c->seafloor = action | ((int)code << 8);
   return 0;
 }

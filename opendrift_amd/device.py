@@ -375,6 +375,16 @@ class Context:
         a = _abi.SEAFLOOR[action]      # ('settle': SedimentDrift.bottom_interaction, sedimentdrift.py:108-116)
         check(self.lib.odr_set_seafloor_action(self.h, a, int(status_code)))
 
+    def set_seafloor_settle_species(self, slot, species):
+        """The sea-floor action 'settle_species' (RadionuclideDrift.bottom_interaction, radionuclides.py:912-942): an element below
+        the sea floor is lifted onto it and settles only if the species number in property slot `slot` is one of `species`."""
+        mask = 0
+        for k in species:
+            if not 0 <= int(k) < _abi.RADIO_MAX_SPECIES:
+                raise ValueError('species number %s outside 0 .. %d' % (k, _abi.RADIO_MAX_SPECIES - 1))
+            mask |= 1 << int(k)
+        check(self.lib.odr_set_seafloor_action(self.h, _abi.SEAFLOOR['settle_species'], mask | (int(slot) << 16)))
+
     def set_time_coverage(self, sid, t_start, t_end, always_valid=False):
         check(self.lib.odr_source_time_coverage(self.h, sid, float(t_start), float(t_end), int(always_valid)))
 
@@ -904,6 +914,50 @@ class Particles:
         check(self.lib.odr_resuspend(self.ctx.h, self.h, C.c_float(np.float32(threshold)), C.byref(n) if count else None))
         return n.value if count else None
 
+    def radio_setup(self, **setup):
+        """The species setup of RadionuclideDrift on the device with its transformation counters (odr_radio_create): the members
+        of odr_radio_setup by name (include/odrift.h), `rates` as [nsalinity][nspecies][nspecies] or [nspecies][nspecies].
+        Returns a RadioSetup (counts() reads the counters, close() frees it)."""
+        return RadioSetup(self.ctx, **setup)
+
+    @staticmethod
+    def _draws(arrays, n):
+        out = []
+        for a in arrays:
+            a = np.ascontiguousarray(a, dtype=np.float64)
+            if a.shape != (n,):
+                raise ValueError('host draws of shape %s for %d elements' % (a.shape, n))
+            out.append(a)
+        return out
+
+    def radio_speciation(self, setup, dt, conc3='conc3', specie_slot=3, diameter_slot=0, step=0, u1=None, u2=None, diameter_noise=None,
+                         depth_noise=None):
+        """RadionuclideDrift.update_transfer_rates + update_speciation (radionuclides.py:728-860, :866-902) over the active set:
+        every element may change its species; a new particle or dissolved element gets a new diameter, sorption puts it on the
+        sea bed (moving 0), desorption takes it off.  conc3: the variable whose slot carries conc3 (Context.slot_aliases).  With
+        u1 (one uniform per element) the numbers are the caller's -- u2, diameter_noise, depth_noise too, one per element --
+        else Philox streams keyed by (ID, step)."""
+        host = u1 is not None
+        d = self._draws((u1, u2, diameter_noise, depth_noise), len(self)) if host else [None] * 4
+        check(self.lib.odr_radio_speciation(self.ctx.h, self.h, setup.ptr, int(specie_slot), int(diameter_slot), self.ctx._vid(conc3),
+                                            float(dt), _abi.RNG_HOST if host else _abi.RNG_DEVICE,
+                                            *[a.ctypes.data_as(_dp) if host else None for a in d], int(step)))
+
+    def radio_terminal_velocity(self, diameter_slot=0, density_slot=2):
+        """RadionuclideDrift.update_terminal_velocity without profiles (radionuclides.py:665-721): Stokes' law from the sampled
+        temperature and salinity and the element's diameter and density, times moving."""
+        check(self.lib.odr_radio_terminal_velocity(self.ctx.h, self.h, int(diameter_slot), int(density_slot)))
+
+    def radio_resuspend(self, setup, specie_slot=3, diameter_slot=0, step=0, diameter_noise=None, depth_noise=None):
+        """The change of species of RadionuclideDrift.bottom_interaction for the elements the sea-floor action 'settle_species' has
+        settled, then resuspension (radionuclides.py:912-942, :946-997).  With diameter_noise / depth_noise (one per element) the
+        numbers are the caller's, else Philox streams keyed by (ID, step)."""
+        host = depth_noise is not None
+        d = self._draws((diameter_noise, depth_noise), len(self)) if host else [None] * 2
+        check(self.lib.odr_radio_resuspend(self.ctx.h, self.h, setup.ptr, int(specie_slot), int(diameter_slot),
+                                           _abi.RNG_HOST if host else _abi.RNG_DEVICE, *[a.ctypes.data_as(_dp) if host else None for a in d],
+                                           int(step)))
+
     def vertical_advection(self, dt, at_surface=False):
         check(self.lib.odr_vertical_advection(self.ctx.h, self.h, float(dt), int(at_surface)))
 
@@ -1124,7 +1178,8 @@ for _name in ('append', 'upload', 'env_sample', 'env_upload', 'env_add_noise', '
               'vmix', 'vmix_analytic', 'vmix_oil', 'vertical_advection', 'vertical_buoyancy', 'coastline', 'coastline_crossing',
               'increase_age', 'deactivate_missing', 'remap_status', 'seafloor', 'deactivate', 'deactivate_outside', 'compact',
               'compact_apply', 'sort_by_cell', 'store_previous', 'oil_prepare_mixing', 'env_coast_leeway', 'egg_terminal_velocity',
-              'resuspend', 'larval_update', 'larval_migrate', 'berg_roll_over', 'berg_advect', 'ship_drift'):
+              'resuspend', 'larval_update', 'larval_migrate', 'berg_roll_over', 'berg_advect', 'ship_drift', 'radio_speciation',
+              'radio_terminal_velocity', 'radio_resuspend'):
     setattr(Particles, _name, _touching(getattr(Particles, _name)))
 
 
@@ -1165,6 +1220,50 @@ class ShipTable:
     def close(self):
         if self.ptr and self.ctx.h:
             self.ctx.lib.odr_ship_table_destroy(self.ctx.h, self.ptr)
+        self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RadioSetup:
+    """Device copy of RadionuclideDrift's species setup with the counters ntransformations (odr_radio_create / _destroy)."""
+    SPECIES = ('lmm', 'lmmcation', 'lmmanion', 'polymer', 'particle_rev', 'sediment_rev', 'particle_slow', 'sediment_slow',
+               'particle_irrev', 'sediment_irrev')
+
+    def __init__(self, ctx, rates, nspecies, lognormal=False, **members):
+        r = np.asarray(rates, dtype=np.float64)
+        r = r[None] if r.ndim == 2 else r
+        M, A = _abi.RADIO_MAX_SPECIES, _abi.RADIO_MAX_SALINITY_INTERVALS
+        if r.ndim != 3 or r.shape[0] not in (1, A) or r.shape[1:] != (nspecies, nspecies) or not 1 <= nspecies <= M:
+            raise ValueError('transfer rates of shape %s for %s species (at most %d, 1 or %d salinity intervals)' % (r.shape, nspecies, M, A))
+        st = _abi.RadioSetup()
+        st.nspecies, st.nsalinity, st.lognormal = int(nspecies), r.shape[0], int(bool(lognormal))
+        full = np.zeros((A, M, M))
+        full[:r.shape[0], :nspecies, :nspecies] = r
+        st.rates[:] = full.ravel().tolist()
+        for k in self.SPECIES:
+            setattr(st, k, int(members.pop(k, -1)))
+        for k, _ in _abi.RadioSetup._fields_[-9:]:
+            setattr(st, k, float(members.pop(k)))
+        if members:
+            raise TypeError('unknown members of the setup: %s' % sorted(members))
+        self.ctx, self.ptr, self.nspecies, self.struct = ctx, C.c_void_p(), int(nspecies), st
+        check(ctx.lib.odr_radio_create(ctx.h, C.byref(st), C.byref(self.ptr)))
+
+    def counts(self, reset=False):
+        """ntransformations[in][out] since creation (or the last reset); the host waits for the context's stream.  OdrError when a
+        launch met an element whose species number is outside the table."""
+        c = np.zeros(_abi.RADIO_MAX_SPECIES ** 2, np.int64)
+        check(self.ctx.lib.odr_radio_counts(self.ctx.h, self.ptr, c.ctypes.data_as(C.POINTER(C.c_int64)), int(bool(reset))))
+        return c.reshape(_abi.RADIO_MAX_SPECIES, _abi.RADIO_MAX_SPECIES)[:self.nspecies, :self.nspecies].copy()
+
+    def close(self):
+        if self.ptr and self.ctx.h:
+            self.ctx.lib.odr_radio_destroy(self.ctx.h, self.ptr)
         self.ptr = C.c_void_p()
 
     def __del__(self):
