@@ -452,6 +452,36 @@ int odr_larval_update(odr_ctx *ctx, odr_particles *p, int stage_fraction_slot, i
  * slot has not been set.  No host synchronisation. */
 int odr_larval_migrate(odr_ctx *ctx, odr_particles *p, int hatched_slot, int length_slot, double fraction_swimming,
                        double dt_seconds, int direction);
+/* OceanDrift.solar_elevation (models/physics_methods.py:977-979 with solar_elevation :1036-1043 and hour_angle :1026-1033): the
+ * solar elevation [deg] of every active element, out_host[0 .. n), float64.  What depends on the time only is the caller's, as
+ * float64 scalars: declination_rad = deg2rad(solar_declination(time)) (:997-1010), time_offset_minutes = equation_of_time(time)
+ * (:1013-1023), day_minutes = hour * 60 + minute + second / 60.  The element part is float64 in the reference's operation order
+ * (csrc/odr_solar.hip.h).  Waits for the context's stream. */
+int odr_solar_elevation(odr_ctx *ctx, odr_particles *p, double declination_rad, double time_offset_minutes, double day_minutes,
+                        double *out_host);
+/* LarvalFishExtended (models/larvalfish_extended.py).  The element properties of LarvalFishExtendedElement (:28-41) in the property
+ * slots of odr_particles_set_property, float32 both: `hatched` (uint8 in the reference) holds 0 (egg) or 1 (larva). */
+enum { ODR_LARVALX_STAGE_FRACTION = 0, ODR_LARVALX_HATCHED = 1 };
+enum { ODR_LARVALX_DEPTH = 1, ODR_LARVALX_DVM = 2 };     /* biology:vertical_behavior_mode ('none' launches nothing: no call) */
+/* LarvalFishExtended.update_fish_larvae (models/larvalfish_extended.py:292-318) over the active set: an egg (hatched == 0) adds
+ * float32(increment) to stage_fraction -- increment = (dt / 86400) / egg:hatch_time_days, formed by the caller in float64 -- and
+ * hatches when the float32 sum is >= 1; larvae are untouched.  ODR_ERR_STATE when a slot has not been set.  Enqueued on the
+ * context's stream; no host synchronisation. */
+int odr_larvalx_hatch(odr_ctx *ctx, odr_particles *p, int stage_fraction_slot, int hatched_slot, double increment);
+/* LarvalFishExtended._apply_vertical_behavior (models/larvalfish_extended.py:206-290, with _target_into_band :188-200) in ONE
+ * launch: z of every moving element goes towards its depth band by at most w_active * dt_seconds, then min(z, 0) and
+ * max(z, -sea_floor_depth) with the sampled float32 depth.  mode ODR_LARVALX_DEPTH: band 0 for every element; ODR_LARVALX_DVM:
+ * band 1 (day) where the element's solar elevation is > 0, else band 0 (night); the three time scalars are those of
+ * odr_solar_elevation (ignored for ODR_LARVALX_DEPTH).  A band is its centre and its half-width
+ * clamp(dz_rel * |centre|, dz_min, dz_max) (_compute_band_half_width, :177-186), formed by the caller.  active_only_hatched != 0:
+ * the larva case, only elements whose hatched slot is 1 move and the others keep their z bits; 0: the phytoplankton case, every
+ * element moves and hatched_slot is not read.  z_is_float32 != 0: the reference still holds z in float32 (no vertical mixing has
+ * run) and its float32 roundings are reproduced (csrc/odr_larvalx.hip.h).  w_active <= 0 or dt_seconds <= 0 launches nothing
+ * (:246-247).  ODR_ERR_STATE when sea_floor_depth_below_sea_level has not been sampled or the slot has not been set.  No host
+ * synchronisation. */
+int odr_larvalx_behave(odr_ctx *ctx, odr_particles *p, int hatched_slot, int mode, int active_only_hatched, int z_is_float32,
+                       double band0_centre, double band0_half_width, double band1_centre, double band1_half_width, double w_active,
+                       double dt_seconds, double declination_rad, double time_offset_minutes, double day_minutes);
 /* OpenBerg (models/openberg.py; Keghouche et al. 2010).  The element properties of IcebergObj (:45-100) that differ between
  * elements in the property slots of odr_particles_set_property, float32 all six; the six coefficients (weight_coef, the four drag
  * coefficients, wave_drag_coef) are scalars of a call. */

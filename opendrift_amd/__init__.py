@@ -18,4 +18,7 @@ def __getattr__(name):      # the model classes import the device binding: resol
     if name == 'RadionuclideDrift':
         from .radionuclides import RadionuclideDrift
         return RadionuclideDrift
+    if name == 'LarvalFishExtended':
+        from .larvalfish_extended import LarvalFishExtended
+        return LarvalFishExtended
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

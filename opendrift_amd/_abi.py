@@ -144,6 +144,9 @@ _SIGNATURES = {
     'odr_resuspend': [_vp, _vp, C.c_float, _i64p],
     'odr_larval_update': [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double],
     'odr_larval_migrate': [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int],
+    'odr_solar_elevation': [_vp, _vp, C.c_double, C.c_double, C.c_double, _dp],
+    'odr_larvalx_hatch': [_vp, _vp, C.c_int, C.c_int, C.c_double],
+    'odr_larvalx_behave': [_vp, _vp] + [C.c_int] * 4 + [C.c_double] * 9,
     'odr_berg_roll_over': [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int],
     'odr_berg_advect': [_vp, _vp] + [C.c_int] * 6 + [C.c_double] * 8 + [C.c_int] * 5 + [C.c_double, _ip, _ip, _vp],
     'odr_ship_table_create': [_vp, _dp, C.c_int, _P(_vp)],
@@ -259,6 +262,8 @@ EGG_PROPERTIES = ['diameter', 'neutral_buoyancy_salinity', 'density', 'hatched']
 BERG_PROPERTIES = ['sail', 'draft', 'length', 'width', 'iceb_x_velocity', 'iceb_y_velocity']     # ODR_BERG_*
 SHIP_PROPERTIES = ['length', 'height', 'draft', 'beam', 'wind_drag_coeff', 'water_drag_coeff', 'orientation', 'ship_class']     # ODR_SHIP_*
 SHIP_TABLE_ROWS = 49     # spectrum points below omega = 7 (odr_ship_table_create)
+LARVALX_PROPERTIES = ['stage_fraction', 'hatched']     # ODR_LARVALX_*
+LARVALX_MODES = {'depth': 1, 'dvm': 2}     # ODR_LARVALX_DEPTH / _DVM
 LARVA_PROPERTIES = ['diameter', 'neutral_buoyancy_salinity', 'stage_fraction', 'hatched', 'length', 'weight', 'survival']     # ODR_LARVA_*
 
 

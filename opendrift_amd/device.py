@@ -850,6 +850,30 @@ class Particles:
         check(self.lib.odr_larval_migrate(self.ctx.h, self.h, int(hatched_slot), int(length_slot), float(fraction_swimming),
                                           float(dt), int(direction)))
 
+    def solar_elevation(self, declination_rad, time_offset_minutes, day_minutes):
+        """OceanDrift.solar_elevation (physics_methods.py:977-979, :1036-1043): the solar elevation [deg] of the active elements,
+        float64.  The three scalars depend on the time only (oceandrift.solar_time_scalars)."""
+        out = np.zeros(len(self), np.float64)
+        check(self.lib.odr_solar_elevation(self.ctx.h, self.h, float(declination_rad), float(time_offset_minutes), float(day_minutes),
+                                           out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def larvalx_hatch(self, increment, stage_fraction_slot=0, hatched_slot=1):
+        """LarvalFishExtended.update_fish_larvae (larvalfish_extended.py:292-318) over the active set: eggs add float32(increment)
+        = (dt / 86400) / hatch_time_days to stage_fraction and hatch at >= 1.  `hatched` is uint8 in the reference; here it is a
+        float32 property slot holding 0 (egg) or 1 (larva), like LarvalFish's."""
+        check(self.lib.odr_larvalx_hatch(self.ctx.h, self.h, int(stage_fraction_slot), int(hatched_slot), float(increment)))
+
+    def larvalx_behave(self, mode, dt, w_active, band0, band1=(0.0, 0.0), solar=(0.0, 0.0, 0.0), active_only_hatched=True,
+                       z_is_float32=False, hatched_slot=1):
+        """LarvalFishExtended._apply_vertical_behavior (larvalfish_extended.py:206-290) in one launch.  mode 'depth': every moving
+        element goes towards band0; 'dvm': towards band1 (day) where its solar elevation is > 0, else band0 (night).  A band is
+        (centre, half-width); solar: the three scalars of solar_elevation.  active_only_hatched: only larvae (hatched slot == 1)
+        move, else every element.  z_is_float32: the reference's roundings while it holds z in float32 (no mixing has run)."""
+        check(self.lib.odr_larvalx_behave(self.ctx.h, self.h, int(hatched_slot), _abi.LARVALX_MODES[mode], int(bool(active_only_hatched)),
+                                          int(bool(z_is_float32)), float(band0[0]), float(band0[1]), float(band1[0]), float(band1[1]),
+                                          float(w_active), float(dt), float(solar[0]), float(solar[1]), float(solar[2])))
+
     def berg_roll_over(self, sail_slot=0, draft_slot=1, length_slot=2, width_slot=3):
         """OpenBerg.roll_over (openberg.py:587-614) over the active set: length >= width, bergs that fail the stability criterion of
         Wagner et al. roll, and every berg's thickness is split again into draft and sail."""
@@ -1178,7 +1202,7 @@ for _name in ('append', 'upload', 'env_sample', 'env_upload', 'env_add_noise', '
               'vmix', 'vmix_analytic', 'vmix_oil', 'vertical_advection', 'vertical_buoyancy', 'coastline', 'coastline_crossing',
               'increase_age', 'deactivate_missing', 'remap_status', 'seafloor', 'deactivate', 'deactivate_outside', 'compact',
               'compact_apply', 'sort_by_cell', 'store_previous', 'oil_prepare_mixing', 'env_coast_leeway', 'egg_terminal_velocity',
-              'resuspend', 'larval_update', 'larval_migrate', 'berg_roll_over', 'berg_advect', 'ship_drift', 'radio_speciation',
+              'resuspend', 'larval_update', 'larval_migrate', 'larvalx_hatch', 'larvalx_behave', 'berg_roll_over', 'berg_advect', 'ship_drift', 'radio_speciation',
               'radio_terminal_velocity', 'radio_resuspend'):
     setattr(Particles, _name, _touching(getattr(Particles, _name)))
 
@@ -1200,7 +1224,7 @@ def _reading(fn):
 
 
 for _name in ('download', 'download_f32', 'env_download', 'get_property', 'reduce_scalars', 'reduce_global', 'reduce_local', 'oil_global_stats',
-              'scan_status', 'count_status'):
+              'scan_status', 'count_status', 'solar_elevation'):
     setattr(Particles, _name, _reading(getattr(Particles, _name)))
 
 

@@ -1725,6 +1725,22 @@ class _ResultBuffer:
         return out
 
 
+def solar_time_scalars(time):
+    """What physics_methods.solar_elevation (:1036-1043) derives from the time alone, with Python's and NumPy's own arithmetic in
+    the reference's operation order: (deg2rad(solar_declination(time)) (:997-1010), equation_of_time(time) [minutes] (:1013-1023,
+    evaluated on one-element arrays as there), the minutes of the day (:1030)), float64.  The element part runs on the device
+    (csrc/odr_solar.hip.h)."""
+    day_of_year = time.timetuple().tm_yday
+    declination = np.arcsin(np.deg2rad(-23.44) * np.cos(np.radians((360.0 / 365.24) * (day_of_year + 10) + (360.0 / np.pi) * 0.0167 *
+                                                                   np.sin(np.radians((360.0 / 365.24) * (day_of_year - 2))))))
+    d_rad = np.deg2rad(np.rad2deg(declination))
+    day, hour = np.asarray([day_of_year]), np.asarray([time.hour])
+    gamma = 2 * np.pi / 365.0 * (day - 1. + (hour - 12.) / 24.)
+    eqtime = 229.18 * (0.000075 + 0.001868 * np.cos(gamma) - 0.032077 * np.sin(gamma) - 0.014615 * np.cos(2 * gamma) -
+                       0.040849 * np.sin(2 * gamma))
+    return float(d_rad), float(eqtime[0]), time.hour * 60.0 + time.minute + time.second / 60.0
+
+
 class OceanDrift(OpenDriftSimulation):
     """opendrift/models/oceandrift.py:54-211"""
     element_properties = {'wind_drift_factor': 0.02, 'current_drift_factor': 1.0, 'terminal_velocity': 0.0}
@@ -1860,6 +1876,10 @@ class OceanDrift(OpenDriftSimulation):
 
     def update_terminal_velocity(self, Tprofiles=None, Sprofiles=None, z_index=None):
         pass
+
+    def solar_elevation(self):   # physics_methods.py:977-979
+        """Solar elevation [deg] at the present time and the positions of the active elements (float64; odr_solar_elevation)."""
+        return self.P.solar_elevation(*solar_time_scalars(self.time))
 
     def water_column_stretching(self):   # oceandrift.py:299-313
         """z + (sea_surface_height - its value of the previous step) * z / sea_floor_depth: the elements follow the water column.
