@@ -847,6 +847,28 @@ int odr_history_host_ptr(odr_ctx *ctx, odr_history *h, int32_t var_index, float 
 int odr_history_reset(odr_ctx *ctx, odr_history *h);   /* new buffer: NaN (:2493-2499) */
 int odr_history_minmax(odr_ctx *ctx, odr_history *h, int32_t var_index, double *minval, double *maxval); /* :2409-2414 */
 
+/* ---------------------------------------------------------------- density maps
+ * OpenDriftSimulation.get_density_array (models/basemodel/__init__.py:4091-4146) for GIVEN bin edges: per output time the three
+ * np.histogram2d of the reference -- H: every entry unless z < 0; H_submerged: unless z >= 0 (a NaN z at a finite position counts
+ * in both, z = -0.0 is surface); H_stranded: status == stranded_code (:4122-4128; < 0: no such category, H_stranded may be NULL and
+ * is zero-filled if given).  The bin of a float32 lon / lat is np.histogram2d's on the edge arrays themselves:
+ * searchsorted(edges, (double)v, side='right') - 1, a value equal to the last edge in the last bin, NaN and everything outside
+ * dropped (csrc/odr_density.hip.h).  The edges are the caller's (:4095-4103 is NumPy arithmetic on the result arrays).
+ * lon, lat, z, status, weight: [trajectory][time] float32, the layout of odr_history_flush, each in host OR device memory (device
+ * arrays must be complete: no stream is waited for); weight NULL: counts, else each bin holds the float64 sum of its float32
+ * weights (float64 atomic adds: the last bits depend on the order of arrival; counts are integer adds and exact).
+ * lon_edges / lat_edges: host, strictly increasing, finite.  H, H_submerged, H_stranded: host, float64 [time][lon_bin][lat_bin].
+ * Host inputs are uploaded in slabs of whole trajectories within a byte budget (256 MiB; the environment variable
+ * ODR_DENSITY_SLAB_BYTES overrides it); the histograms stay on the device for all of them.  Synchronous.
+ * ODR_ERR_INVALID: fewer than two edges, edges not finite or not strictly increasing, more than 2^28 bins per output time,
+ * n_trajectories >= 2^32 (the counts are 32-bit), a NULL pointer other than weight and (stranded_code < 0) H_stranded -- checked
+ * before anything is launched. */
+int odr_density_map(odr_ctx *ctx, int64_t n_trajectories, int32_t n_times, const float *lon, const float *lat, const float *z,
+                    const float *status, const float *weight, int32_t stranded_code, int32_t n_lon_edges, const double *lon_edges,
+                    int32_t n_lat_edges, const double *lat_edges, double *H, double *H_submerged, double *H_stranded);
+/* device time [ms] of the kernel launches of this process's last odr_density_map, summed over its slabs (tools/bench_density.py) */
+int odr_density_last_kernel_ms(odr_ctx *ctx, float *ms);
+
 /* ---------------------------------------------------------------- ROMS sigma grid
  * The sigma -> z regridding reader_ROMS_native.get_variables applies to every 4-D variable of a block
  * (reader_ROMS_native.py:512-538,617-684) with roppy (readers/roppy/depth.py): sdepth (:31-113, rho points,

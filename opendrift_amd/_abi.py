@@ -225,6 +225,8 @@ _SIGNATURES = {
     'odr_history_host_ptr': [_vp, _vp, C.c_int32, _P(_fp), _P(C.c_int32)],
     'odr_history_reset': [_vp, _vp],
     'odr_history_minmax': [_vp, _vp, C.c_int32, _dp, _dp],
+    'odr_density_map': [_vp, C.c_int64, C.c_int32] + [_vp] * 5 + [C.c_int32, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp],
+    'odr_density_last_kernel_ms': [_vp, _fp],
 }
 EXPORTS = sorted(list(_SIGNATURES) + ['odr_last_error', 'odr_version'])
 

@@ -418,6 +418,40 @@ class Context:
     def history(self, n_trajectories, n_times, variables, id_base=0):
         return History(self, n_trajectories, n_times, variables, id_base=id_base)
 
+    def density_map(self, lon, lat, z, status, lon_edges, lat_edges, weight=None, stranded_code=-1, shape=None):
+        """The three histograms per output time of get_density_array for given bin edges (odr_density_map): (H, H_submerged,
+        H_stranded), float64 [time, lon_bin, lat_bin].  lon, lat, z, status, weight: [trajectory, time] float32 arrays, or device
+        addresses (int) with `shape` = (n_trajectories, n_times).  stranded_code < 0: no such category, H_stranded stays zero."""
+        arrays = [lon, lat, z, status] + ([weight] if weight is not None else [])
+        keep, ptrs = [], []
+        for a in arrays:
+            if isinstance(a, (int, np.integer)):
+                if shape is None:
+                    raise ValueError('device addresses need shape=(n_trajectories, n_times)')
+                ptrs.append(C.c_void_p(int(a)))
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 2 or (shape is not None and a.shape != tuple(shape)):
+                raise ValueError('density_map: an input of shape %s, not [trajectory, time] %s' % (a.shape, shape or ''))
+            shape = a.shape
+            keep.append(a)
+            ptrs.append(C.c_void_p(a.ctypes.data))
+        if weight is None:
+            ptrs.append(None)
+        ntraj, nt = int(shape[0]), int(shape[1])
+        le, pe = _d(np.asarray(lon_edges, dtype=np.float64).ravel())
+        la, pa = _d(np.asarray(lat_edges, dtype=np.float64).ravel())
+        dims = (nt, max(len(le) - 1, 0), max(len(la) - 1, 0))
+        out = [np.zeros(dims) for _ in range(3)]
+        check(self.lib.odr_density_map(self.h, ntraj, nt, *ptrs, int(stranded_code), len(le), pe, len(la), pa,
+                                       *(o.ctypes.data_as(_dp) for o in out)))
+        return tuple(out)
+
+    def density_last_kernel_ms(self):
+        ms = C.c_float()
+        check(self.lib.odr_density_last_kernel_ms(self.h, C.byref(ms)))
+        return ms.value
+
     def particles(self, capacity):
         return Particles(self, capacity)
 

@@ -1586,6 +1586,41 @@ class OpenDriftSimulation(Configurable):
         self.result_minmax = self._hist.minmax
         return self.result
 
+    def get_density_array(self, pixelsize_m, weight=None, bins=None):
+        """basemodel/__init__.py:4091-4146: (H, H_submerged, H_stranded, lon_array, lat_array), the number of elements -- or, with
+        `weight` (the name of an exported variable), the sum of that variable -- per pixel of about pixelsize_m metres and output
+        time, float64 [time, lon_bin, lat_bin]: all elements not below the surface, the submerged ones, the stranded ones.
+        The edges are the reference's NumPy expressions on the float32 result arrays (lower longitude edge: deltalat, as there);
+        the binning runs on the device (odr_density_map).  bins=(lon_array, lat_array), not in the reference: the caller's edges
+        instead -- what a sharded run needs, whose ranks each hold their own rows and return their share of every map."""
+        result = getattr(self, 'result', None)
+        if result is None:
+            raise RuntimeError('get_density_array needs the result of run()')
+        for name in ('lon', 'lat', 'z', 'status') + ((weight, ) if weight is not None else ()):
+            if name not in result:
+                raise KeyError('%s is not in self.result (export_variables)' % name)
+        if bins is None:
+            if self._world > 1:
+                raise NotImplementedError('get_density_array of a sharded run needs bins=(lon_array, lat_array), the same on every '
+                                          'rank: the edges the reference derives come from the elements of all ranks')
+            lon_array, lat_array = density_edges(result['lon'], result['lat'], pixelsize_m)
+        else:
+            lon_array, lat_array = (np.asarray(b, dtype=np.float64) for b in bins)
+        try:
+            strandnum = self.status_categories.index('stranded')
+        except ValueError:
+            strandnum = -1
+        H, H_submerged, H_stranded = self.ctx.density_map(
+            result['lon'], result['lat'], result['z'], result['status'], lon_array, lat_array,
+            weight=None if weight is None else result[weight], stranded_code=strandnum)
+        return H, H_submerged, H_stranded, lon_array, lat_array
+
+    def get_residence_time(self, pixelsize_m):
+        """basemodel/__init__.py:4247-4251: (H summed over the output times, lon_array, lat_array)."""
+        H, H_sub, H_str, lon_array, lat_array = self.get_density_array(pixelsize_m)
+        residence = np.sum(H, axis=0)
+        return residence, lon_array, lat_array
+
     def _history_variables(self, export_variables):
         """Variables of the result buffer (:2068-2105): every element property and every required environment
         variable, or `export_variables` + ['lon', 'lat', 'status']."""
@@ -1723,6 +1758,18 @@ class _ResultBuffer:
         self.H.close()
         out = {v: np.concatenate([c[v] for c in self.chunks], axis=1)[:, :ntimes_written] for v in self.variables}
         return out
+
+
+def density_edges(lon, lat, pixelsize_m):
+    """(lon_array, lat_array) of get_density_array (basemodel/__init__.py:4095-4103) from the [trajectory, time] float32 lon / lat of
+    a result: the reference's NumPy expressions in its order on the float32 arrays and NumPy scalars -- the mid latitude, its cosine
+    and deltalon are float32 there, and the lower longitude edge is one deltaLAT below the smallest longitude."""
+    lon_lo, lon_hi, lat_lo, lat_hi = np.nanmin(lon), np.nanmax(lon), np.nanmin(lat), np.nanmax(lat)      # float32 scalars
+    dlat = pixelsize_m / 111000.0                                  # Python float
+    dlon = dlat / np.cos(np.radians((lat_lo + lat_hi) / 2))        # float32 sum, half, radians, cosine and quotient
+    lat_array = np.arange(lat_lo - dlat, lat_hi + dlat, dlat)
+    lon_array = np.arange(lon_lo - dlat, lon_hi + dlon, dlon)
+    return lon_array, lat_array
 
 
 def solar_time_scalars(time):
