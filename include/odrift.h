@@ -869,6 +869,29 @@ int odr_density_map(odr_ctx *ctx, int64_t n_trajectories, int32_t n_times, const
 /* device time [ms] of the kernel launches of this process's last odr_density_map, summed over its slabs (tools/bench_density.py) */
 int odr_density_last_kernel_ms(odr_ctx *ctx, float *ms);
 
+/* ---------------------------------------------------------------- FTLE maps
+ * physics_methods.ftle (models/physics_methods.py:458-484) of the displacements that OpenDriftSimulation.calculate_ftle
+ * (models/basemodel/__init__.py:4844-4923) forms from the last positions of one run of a grid of elements (:4898-4902, :4911-4915).
+ * proj: the projection the grid is regular in -- every kind odr_source_grid takes (ODR_PROJ_LATLONG by a descriptor of that kind),
+ * not ODR_PROJ_CURVILINEAR.  xs[nx], ys[ny]: host, the caller's np.arange values (they are not equidistant to the last bit and
+ * are never recomputed from a start and delta).  lon, lat: float32 [ny][nx], row j column i the last valid position of the element
+ * seeded at (xs[i], ys[j]), each in host OR device memory (device arrays must be complete: no stream is waited for); a position
+ * that is not finite gives a NaN displacement.
+ * Displacement, float64: (x, y) = proj(lon, lat) on the device; dX = x - xs[i], dY = y - ys[j].  The reference differentiates this
+ * displacement, not the flow map, with np.gradient at unit spacing (interior (f[k+1] - f[k-1]) / 2, ends f[1] - f[0] and
+ * f[n-1] - f[n-2]) and divides by 2 * delta once more (:467-474); both are kept.  J float32 (each float64 quotient rounded once),
+ * D = J^T J in float32 without fused multiply-adds, the largest eigenvalue of the symmetric 2 x 2 in closed form in float64 rounded
+ * to float32, ftle = log(sqrt(lambda)) / |duration_seconds| in float64 rounded to float32 (csrc/odr_ftle.hip.h).  lambda == 0:
+ * -inf.  A NaN anywhere in a cell's stencil: NaN (the reference's LAPACK call raises there).
+ * ftle: host, float32 [ny][nx].  displacement: host, 2 * ny * nx float64, the x plane then the y plane, or NULL (not reported).
+ * Two launches, no atomics: two calls give the same bits.  Synchronous.
+ * ODR_ERR_INVALID: nx < 2 or ny < 2, nx * ny >= 2^31, xs / ys / delta not finite, delta <= 0, duration_seconds 0 or not finite, a
+ * NULL pointer other than displacement, ODR_PROJ_CURVILINEAR or an unknown kind -- checked before anything is launched. */
+int odr_ftle_map(odr_ctx *ctx, const odr_proj_desc *proj, int32_t nx, int32_t ny, const double *xs, const double *ys, double delta,
+                 double duration_seconds, const float *lon, const float *lat, float *ftle, double *displacement);
+/* device time [ms] of the two kernel launches of this process's last odr_ftle_map that launched (tools/bench_ftle.py) */
+int odr_ftle_last_kernel_ms(odr_ctx *ctx, float *ms);
+
 /* ---------------------------------------------------------------- ROMS sigma grid
  * The sigma -> z regridding reader_ROMS_native.get_variables applies to every 4-D variable of a block
  * (reader_ROMS_native.py:512-538,617-684) with roppy (readers/roppy/depth.py): sdepth (:31-113, rho points,

@@ -227,6 +227,8 @@ _SIGNATURES = {
     'odr_history_minmax': [_vp, _vp, C.c_int32, _dp, _dp],
     'odr_density_map': [_vp, C.c_int64, C.c_int32] + [_vp] * 5 + [C.c_int32, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp],
     'odr_density_last_kernel_ms': [_vp, _fp],
+    'odr_ftle_map': [_vp, _P(ProjDesc), C.c_int32, C.c_int32, _dp, _dp, C.c_double, C.c_double, _vp, _vp, _fp, _dp],
+    'odr_ftle_last_kernel_ms': [_vp, _fp],
 }
 EXPORTS = sorted(list(_SIGNATURES) + ['odr_last_error', 'odr_version'])
 

@@ -362,6 +362,7 @@ int odr_i_ensure_ranks(odr_ctx *c, odr_particles *p);
 
 // defined in odrift.hip
 bool odr_i_build_env_group(const odr_ctx *c, const int *grp, int ng, double t, EnvGroupDesc &G);
+void odr_i_proj_init(odr::DevProj &p, const odr_proj_desc *d);   // the device image of a projection (NULL: latlong)
 // odr_comm.hip: the process's RCCL communicators
 bool odr_i_comm_on();
 int odr_i_comm_rank();
@@ -380,6 +381,7 @@ int odr_i_read_counter(odr_ctx *c, int64_t *out);
 int odr_i_env_noise(odr_ctx *c, odr_particles *p, int vx, int vy, double std, int distribution, int rng_mode,
                     const double *dev_nx, const double *dev_ny, unsigned long long step);
 #define build_env_group odr_i_build_env_group
+#define proj_init odr_i_proj_init
 #define uv_fast_source odr_i_uv_fast_source
 #define gyre_source odr_i_gyre_source
 #define env_sample_impl odr_i_env_sample

@@ -296,7 +296,7 @@ int odr_particles_download_f32(odr_ctx *c, odr_particles *p, const char *name, f
 }
 
 // --------------------------------------------------------------------- sources
-static void proj_init(DevProj &p, const odr_proj_desc *d) {
+void odr_i_proj_init(DevProj &p, const odr_proj_desc *d) {
   memset(&p, 0, sizeof p);
   if (!d) { p.kind = PROJ_LATLONG; p.a = 1; p.k0 = 1; return; }
   p.kind = d->kind;

@@ -452,6 +452,39 @@ class Context:
         check(self.lib.odr_density_last_kernel_ms(self.h, C.byref(ms)))
         return ms.value
 
+    def ftle_map(self, proj, xs, ys, delta, duration_seconds, lon, lat, displacement=False):
+        """physics_methods.ftle of the displacements of a grid of elements (odr_ftle_map): float32 [ny, nx], and with
+        displacement=True also the float64 [2, ny, nx] planes (x, y) the device differentiated.  proj: projection.parse_proj4's
+        dict (None: latlong) or an _abi.ProjDesc; xs, ys: the grid's np.arange axes; lon, lat: float32 [ny, nx] (or ny * nx) last
+        positions, row j column i the element seeded at (xs[i], ys[j]), or device addresses (int)."""
+        xs, px = _d(np.asarray(xs, dtype=np.float64).ravel())
+        ys, py = _d(np.asarray(ys, dtype=np.float64).ravel())
+        nx, ny = len(xs), len(ys)
+        if nx * ny >= 2 ** 31:
+            raise ValueError('ftle_map: %d x %d cells, 2^31 or more' % (ny, nx))
+        if not isinstance(proj, _abi.ProjDesc):
+            proj = proj_desc(proj) or _abi.ProjDesc(_abi.PROJ_LATLONG, 6378137.0, 0.0, 0.0, 0.0, 90.0, 1.0, 0.0, 0.0, 0.0, 0.0)
+        keep, ptrs = [], []
+        for a in (lon, lat):
+            if isinstance(a, (int, np.integer)):
+                ptrs.append(C.c_void_p(int(a)))
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.size != nx * ny:
+                raise ValueError('ftle_map: %d positions for %d x %d cells' % (a.size, ny, nx))
+            keep.append(a)
+            ptrs.append(C.c_void_p(a.ctypes.data))
+        out = np.empty((ny, nx), np.float32)
+        disp = np.empty((2, ny, nx)) if displacement else None
+        check(self.lib.odr_ftle_map(self.h, C.byref(proj), nx, ny, px, py, float(delta), float(duration_seconds), *ptrs,
+                                    out.ctypes.data_as(_fp), None if disp is None else disp.ctypes.data_as(_dp)))
+        return (out, disp) if displacement else out
+
+    def ftle_last_kernel_ms(self):
+        ms = C.c_float()
+        check(self.lib.odr_ftle_last_kernel_ms(self.h, C.byref(ms)))
+        return ms.value
+
     def particles(self, capacity):
         return Particles(self, capacity)
 

@@ -77,6 +77,7 @@ class Leeway(OpenDriftSimulation):
             raise FileNotFoundError(d)                        # the reference's open(d) (leeway.py:193)
         path = find_objectprop(d)
         self.leewayprop = read_objectprop(path) if path is not None else None
+        self._objectprop_argument = d
         super().__init__(*args, **kwargs)
         if self.leewayprop:
             descriptions = [self.leewayprop[p]['Description'] for p in self.leewayprop]
@@ -94,6 +95,9 @@ class Leeway(OpenDriftSimulation):
             'drift:stokes_drift': {'type': 'bool', 'default': False, 'level': CONFIG_LEVEL_ADVANCED, 'description': ''},
         })
         self._set_config_default('drift:max_speed', 5)
+
+    def _clone_arguments(self):
+        return dict(super()._clone_arguments(), d=self._objectprop_argument)
 
     def _object_class(self, object_type):
         """leeway.py:305-322: the class number given, or looked up from `seed:object_type` (OBJKEY or description)."""

@@ -24,7 +24,7 @@ import os
 
 import numpy as np
 
-from . import _abi
+from . import _abi, projection
 from .config import Configurable, CONFIG_LEVEL_BASIC, CONFIG_LEVEL_ADVANCED, CONFIG_LEVEL_ESSENTIAL
 from .device import Context
 from .readers import BaseReader, ConstantReader, DeviceReaderBinding, ReaderLevelsError, _epoch
@@ -1621,6 +1621,142 @@ class OpenDriftSimulation(Configurable):
         residence = np.sum(H, axis=0)
         return residence, lon_array, lat_array
 
+    def clone(self):
+        """basemodel/__init__.py:572-581: a new instance of the same class (on the same device, with the same random-number and
+        stage arithmetic settings) with every config value copied and the same reader OBJECTS added under the same names, every
+        variable's priority list in the same order.  A reader object holds nothing of a model's device context -- the device image
+        of a reader is the model's DeviceReaderBinding, made anew by every run -- except the host-side lonlat2xy of a reader without
+        a projection, which calculate_ftle hands back (_release_device); so the original and any number of clones can use the same
+        readers one after the other.  The constant reader that a run makes from environment:constant:* is not copied: the clone's
+        run makes its own from the copied config."""
+        c = self.__class__(**self._clone_arguments())
+        c._config.clear()
+        for k, v in self._config.items():
+            c._config[k] = dict(v)
+        own = 'constant_reader_config'
+        for name, (r, vs) in self._readers_host.items():
+            if name != own:
+                c.add_reader(r, variables=list(vs))
+        assert list(c._readers_host) == [n for n in self._readers_host if n != own]
+        c.priority_list = {v: [n for n in lst if n != own] for v, lst in self.priority_list.items()}
+        return c
+
+    def _clone_arguments(self):
+        """The constructor arguments of a clone (models whose constructor takes more add theirs)."""
+        return dict(seed=self._seed, device=self._device, rng=self.rng, stage_math=self.stage_math)
+
+    def _release_device(self):
+        """Free what this model holds on the device: reader blocks, elements, result buffer, the context itself.  The result of a
+        finished run stays (host arrays).  A reader without a projection gets back the lonlat2xy it had before this model's run."""
+        for b in self.readers.values():
+            if hasattr(b, 'close_read_ahead'):
+                b.close_read_ahead()
+            if getattr(b, 'sgrid', None) is not None:
+                b.sgrid.close()
+            if hasattr(b.reader, '_device_lookup') and b.ctx is self._ctx:
+                b.reader._device_lookup = getattr(self, '_lookups_before', {}).get(id(b.reader))
+        self.readers = {}
+        H = getattr(getattr(self, '_hist', None), 'H', None)
+        if H is not None:
+            H.close()
+        if self.P is not None:
+            self.P.close()
+            self.P = None
+        if self._ctx is not None:
+            self._ctx.close()
+            self._ctx = None
+
+    def calculate_ftle(self, reader=None, delta=None, domain=None, time=None, time_step=None, duration=None, z=0, RLCS=True,
+                       ALCS=True):
+        """basemodel/__init__.py:4844-4923: finite-time Lyapunov exponents of the flow on a regular grid of `delta` in the
+        coordinates of `reader` (a reader object, a projection.Proj or a proj4 string; None: the first reader) over the reader's
+        bounds or domain = [xmin, xmax, ymin, ymax]: {'time': [...], 'lon', 'lat': [ny, nx], 'RLCS', 'ALCS': float64 masked arrays
+        [time, ny, nx]} -- the repelling structures from a run forwards over `duration` from every `time`, the attracting ones from a
+        run backwards from time + duration; a map that is not asked for stays zero.  One element per cell is seeded in a clone() of
+        this model per direction; the exponents of the last valid positions come from the device (odr_ftle_map), which
+        restates physics_methods.ftle (:458-484).  Masked: cells that are not finite -- -inf where the displacement is uniform around
+        a cell, NaN where an element of the stencil never had a position (the reference's LAPACK call raises there).
+
+        Trajectory order: the reference flips the element IDs of a backward run (:2061-2063) and undoes that with [::-1] (:4913).
+        This project's backward run does not flip them: trajectory k of a result is cell k (row k // nx, column k % nx) in BOTH
+        directions, and nothing is re-ordered here.
+
+        A sharded run (WORLD_SIZE > 1) raises NotImplementedError: each rank would hold a part of the grid's rows."""
+        if self._world > 1:
+            raise NotImplementedError('calculate_ftle of a sharded run: every rank holds a part of the rows of the grid, the '
+                                      'gradient needs the neighbouring ones (DESIGN.md 8h)')
+        if reader is None:
+            if not self._readers_host:
+                raise ValueError('calculate_ftle: no reader given and none added')
+            reader = next(iter(self._readers_host.values()))[0]
+            logger.info('No reader provided, using first available: %s', reader.name)
+        if isinstance(reader, projection.Proj):
+            proj = reader
+        elif isinstance(reader, str):
+            proj = projection.Proj(reader)
+        else:
+            proj = reader.proj
+            if proj is None:
+                raise NotImplementedError('calculate_ftle needs a projection: reader %s has none (2-D lon / lat arrays)' % reader.name)
+        if delta is None or duration is None:
+            raise ValueError('calculate_ftle needs delta and duration')
+        if not isinstance(duration, timedelta):
+            duration = timedelta(seconds=duration)
+        if domain is None:
+            if proj is reader or isinstance(reader, str):
+                raise ValueError('calculate_ftle: a projection has no bounds, give domain=[xmin, xmax, ymin, ymax]')
+            xs = np.arange(reader.xmin, reader.xmax, delta)
+            ys = np.arange(reader.ymin, reader.ymax, delta)
+        else:
+            xmin, xmax, ymin, ymax = domain
+            xs = np.arange(xmin, xmax, delta)
+            ys = np.arange(ymin, ymax, delta)
+        X, Y = np.meshgrid(xs, ys)
+        lons, lats = proj(X, Y, inverse=True)
+        if time is None:
+            time = reader.start_time
+        if not isinstance(time, list):
+            time = [time]
+        if time_step is None:
+            time_step = timedelta(minutes=self.get_config('general:time_step_minutes'))
+        if not isinstance(time_step, timedelta):
+            time_step = timedelta(seconds=time_step)
+        lcs = {'time': time, 'lon': lons, 'lat': lats}
+        lcs['RLCS'] = np.zeros((len(time), len(ys), len(xs)))
+        lcs['ALCS'] = np.zeros((len(time), len(ys), len(xs)))
+        T = np.abs(duration.total_seconds())
+        for i, t in enumerate(time):
+            logger.info('Calculating LCS for %s', t)
+            for key, wanted, start, step in (('RLCS', RLCS, t, time_step), ('ALCS', ALCS, t + duration, -time_step)):
+                if wanted is not True:
+                    continue
+                lon, lat = self._ftle_trajectories(lons.ravel(), lats.ravel(), z, start, step, duration)
+                lcs[key][i, :, :] = self.ctx.ftle_map(proj.params, xs, ys, delta, T, last_valid(lon), last_valid(lat))
+        lcs['RLCS'] = np.ma.masked_invalid(lcs['RLCS'])
+        lcs['ALCS'] = np.ma.masked_invalid(lcs['ALCS'])
+        return lcs
+
+    def _ftle_trajectories(self, lon, lat, z, start, time_step, duration):
+        """One run of calculate_ftle (:4895-4899, :4905-4912): a clone with one element per position released at `start` runs over
+        `duration` with `time_step` (negative: backwards); the float32 [trajectory, time] lon and lat of its result.  Only lon and
+        lat are exported (status comes with them), and when the duration is a whole number of time steps and no output time step
+        is configured the result has two output times, the start and the end -- an element deactivated on the way is recorded with
+        its last position at the end (state_to_buffer's backfill), so nothing the maps need is lost and the device history is
+        24 B per element.  The clone's device memory is released before this returns."""
+        o = self.clone()
+        before = {id(r): getattr(r, '_device_lookup', None) for r, _ in self._readers_host.values()}
+        o._lookups_before = before
+        try:
+            o.seed_elements(lon, lat, time=start, z=z)
+            window = {}
+            steps = duration.total_seconds() / time_step.total_seconds()
+            if o.get_config('general:time_step_output_minutes') is None and float(steps).is_integer() and abs(steps) >= 1:
+                window = dict(time_step_output=abs(duration), export_buffer_length=2)
+            result = o.run(duration=duration, time_step=time_step, export_variables=['lon', 'lat'], **window)
+            return result['lon'], result['lat']
+        finally:
+            o._release_device()
+
     def _history_variables(self, export_variables):
         """Variables of the result buffer (:2068-2105): every element property and every required environment
         variable, or `export_variables` + ['lon', 'lat', 'status']."""
@@ -1770,6 +1906,22 @@ def density_edges(lon, lat, pixelsize_m):
     lat_array = np.arange(lat_lo - dlat, lat_hi + dlat, dlat)
     lon_array = np.arange(lon_lo - dlat, lon_hi + dlon, dlon)
     return lon_array, lat_array
+
+
+def last_valid(a):
+    """The last value along time that is not NaN of every row of a [trajectory, time] array -- what
+    result.<variable>.ffill(dim='time').T[-1] holds in the reference (basemodel/__init__.py:4898-4901); NaN for a row without any.
+    The last column is taken first and only the rows that end in NaN are scanned."""
+    a = np.asarray(a)
+    out = np.array(a[:, -1], copy=True)
+    rows = np.flatnonzero(np.isnan(out))
+    if rows.size:
+        sub = a[rows]
+        ok = ~np.isnan(sub)
+        last = sub.shape[1] - 1 - np.argmax(ok[:, ::-1], axis=1)
+        has = ok.any(axis=1)
+        out[rows[has]] = sub[has, last[has]]
+    return out
 
 
 def solar_time_scalars(time):

@@ -185,6 +185,7 @@ class ShipDrift(OceanDrift):
             raise FileNotFoundError('ShipDrift needs the reference\'s wave-force table wforce.dat, which is not shipped: pass its '
                                     'path as ShipDrift(wforce=...), set ODR_WFORCE or install opendrift')
         self.wforce = read_wforce(path)
+        self._wforce_argument = wforce
         super().__init__(*args, **kwargs)
         self._add_config({'seed:orientation': {      # :149-153
             'type': 'enum', 'enum': ['left', 'right', 'random'], 'default': 'random', 'level': CONFIG_LEVEL_ESSENTIAL,
@@ -198,6 +199,9 @@ class ShipDrift(OceanDrift):
         self.ship_classes = []              # (bl, dl) as float32 pairs, in the order of their class index
         self.ship_class_table = None        # [n_classes][49][2]
         self._device_table = None
+
+    def _clone_arguments(self):
+        return dict(super()._clone_arguments(), wforce=self._wforce_argument)
 
     def add_reader(self, readers, variables=None, first=False):
         for r in readers if isinstance(readers, (list, tuple)) else [readers]:
