@@ -892,6 +892,31 @@ int odr_ftle_map(odr_ctx *ctx, const odr_proj_desc *proj, int32_t nx, int32_t ny
 /* device time [ms] of the two kernel launches of this process's last odr_ftle_map that launched (tools/bench_ftle.py) */
 int odr_ftle_last_kernel_ms(odr_ctx *ctx, float *ms);
 
+/* ---------------------------------------------------------------- inverse geodesics, trajectory lengths
+ * pyproj.Geod(ellps='WGS84').inv as OpenDriftSimulation.get_trajectory_lengths calls it (models/basemodel/__init__.py:4618-4620):
+ * the shortest WGS84 geodesic between n pairs of points, Karney's inverse (J. Geodesy 87:43-55, 2013) at order 6
+ * (csrc/odr_geodinv.hip.h).  lon1, lat1, lon2, lat2: host, float64 degrees.  azi1, azi2: the FORWARD azimuths at both ends in
+ * degrees (pyproj's back azimuth is azi2 turned by 180), s12: metres; host, each may be NULL.  A NaN or infinite coordinate and
+ * |lat| > 90 give NaN; coincident points give 0, 0, 0.  Synchronous.  ODR_ERR_INVALID: n < 0, a NULL input. */
+int odr_geod_inverse(odr_ctx *ctx, int64_t n, const double *lon1, const double *lat1, const double *lon2, const double *lat2,
+                     double *azi1, double *azi2, double *s12);
+/* OpenDriftSimulation.get_trajectory_lengths (models/basemodel/__init__.py:4614-4628).  lon, lat: [trajectory][time] float32, the
+ * layout of odr_history_flush, each in host OR device memory (device arrays must be complete: no stream is waited for).  Per
+ * trajectory and output interval: the float32 positions widened to float64, the geodesic distance in float64, NaN (an end that is
+ * NaN: before seeding, after deactivation) -> 0 (:4621), speed = distance / dt_seconds with the sign of dt (:4622), speed > 100 ->
+ * distance and speed 0 (:4623-4625).  total_length[trajectory]: np.cumsum(distances, 0)[-1] (:4626), the float64 sum in time order.
+ * distances, speeds: [time - 1][trajectory] float64 as in the reference, host; either may be NULL, and with both NULL nothing of
+ * size n_trajectories * n_times leaves the device.  total_length: host.  Host inputs go up in slabs of whole trajectories, lon
+ * and lat of a slab within 256 MiB (ODR_TRAJ_SLAB_BYTES overrides); device inputs are walked in the same slabs.  No atomics: two
+ * calls give the same bits, and the host build of the header gives those bits too.  Synchronous.
+ * ODR_ERR_INVALID: n_times < 2, dt_seconds 0 or not finite, n_trajectories < 0, a NULL lon / lat / total_length -- checked before
+ * anything is launched. */
+int odr_trajectory_lengths(odr_ctx *ctx, int64_t n_trajectories, int32_t n_times, const float *lon, const float *lat,
+                           double dt_seconds, double *total_length, double *distances, double *speeds);
+/* device time [ms] of the kernel launches of this process's last odr_trajectory_lengths, summed over its slabs
+ * (tools/bench_trajectory_lengths.py) */
+int odr_trajectory_lengths_last_kernel_ms(odr_ctx *ctx, float *ms);
+
 /* ---------------------------------------------------------------- ROMS sigma grid
  * The sigma -> z regridding reader_ROMS_native.get_variables applies to every 4-D variable of a block
  * (reader_ROMS_native.py:512-538,617-684) with roppy (readers/roppy/depth.py): sdepth (:31-113, rho points,

@@ -229,6 +229,9 @@ _SIGNATURES = {
     'odr_density_last_kernel_ms': [_vp, _fp],
     'odr_ftle_map': [_vp, _P(ProjDesc), C.c_int32, C.c_int32, _dp, _dp, C.c_double, C.c_double, _vp, _vp, _fp, _dp],
     'odr_ftle_last_kernel_ms': [_vp, _fp],
+    'odr_geod_inverse': [_vp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
+    'odr_trajectory_lengths': [_vp, C.c_int64, C.c_int32, _vp, _vp, C.c_double, _dp, _dp, _dp],
+    'odr_trajectory_lengths_last_kernel_ms': [_vp, _fp],
 }
 EXPORTS = sorted(list(_SIGNATURES) + ['odr_last_error', 'odr_version'])
 

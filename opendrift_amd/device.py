@@ -485,6 +485,51 @@ class Context:
         check(self.lib.odr_ftle_last_kernel_ms(self.h, C.byref(ms)))
         return ms.value
 
+    def geod_inv(self, lon1, lat1, lon2, lat2):
+        """pyproj.Geod(ellps='WGS84').inv on the device (odr_geod_inverse): (az12, az21, dist) as float64 arrays of the broadcast
+        shape -- the forward azimuth at point 1, the BACK azimuth at point 2 (pyproj's convention: the forward azimuth there turned
+        by 180 degrees) and the distance in metres."""
+        arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in
+                np.broadcast_arrays(*(np.asarray(v, dtype=np.float64) for v in (lon1, lat1, lon2, lat2)))]
+        shape = arrs[0].shape
+        out = [np.empty(shape) for _ in range(3)]
+        check(self.lib.odr_geod_inverse(self.h, arrs[0].size, *(a.ctypes.data_as(_dp) for a in arrs),
+                                        *(o.ctypes.data_as(_dp) for o in out)))
+        az12, azi2, dist = out
+        az21 = np.where(azi2 > 0, azi2 - 180.0, azi2 + 180.0)
+        return az12, az21, dist
+
+    def trajectory_lengths(self, lon, lat, dt, segments=True, shape=None):
+        """get_trajectory_lengths (odr_trajectory_lengths): (total_length [trajectory], distances, speeds [time - 1, trajectory]),
+        float64; segments=False: total_length alone, and nothing per output interval leaves the device.  lon, lat: [trajectory,
+        time] float32 arrays, or device addresses (int) with `shape` = (n_trajectories, n_times); dt: seconds between two output
+        times, with its sign."""
+        keep, ptrs = [], []
+        for a in (lon, lat):
+            if isinstance(a, (int, np.integer)):
+                if shape is None:
+                    raise ValueError('device addresses need shape=(n_trajectories, n_times)')
+                ptrs.append(C.c_void_p(int(a)))
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 2 or (shape is not None and a.shape != tuple(shape)):
+                raise ValueError('trajectory_lengths: an input of shape %s, not [trajectory, time] %s' % (a.shape, shape or ''))
+            shape = a.shape
+            keep.append(a)
+            ptrs.append(C.c_void_p(a.ctypes.data))
+        ntraj, nt = int(shape[0]), int(shape[1])
+        total = np.zeros(ntraj)
+        dims = (max(nt - 1, 0), ntraj)
+        dist, speed = (np.zeros(dims), np.zeros(dims)) if segments else (None, None)
+        check(self.lib.odr_trajectory_lengths(self.h, ntraj, nt, *ptrs, float(dt), total.ctypes.data_as(_dp),
+                                              *(None if o is None else o.ctypes.data_as(_dp) for o in (dist, speed))))
+        return (total, dist, speed) if segments else total
+
+    def trajectory_lengths_last_kernel_ms(self):
+        ms = C.c_float()
+        check(self.lib.odr_trajectory_lengths_last_kernel_ms(self.h, C.byref(ms)))
+        return ms.value
+
     def particles(self, capacity):
         return Particles(self, capacity)
 

@@ -1621,6 +1621,20 @@ class OpenDriftSimulation(Configurable):
         residence = np.sum(H, axis=0)
         return residence, lon_array, lat_array
 
+    def get_trajectory_lengths(self):
+        """basemodel/__init__.py:4614-4628: (total_length [trajectory], distances, speeds [time - 1, trajectory]), float64 -- the
+        WGS84 geodesic distance between consecutive output positions of every trajectory, that distance over the output time step
+        (with its sign: negative in a backward run), and their sum along the trajectory.  An interval with a NaN end (before
+        seeding, after deactivation) and one faster than 100 m/s count as 0, as in the reference.  The inverse geodesics run on the
+        device (odr_trajectory_lengths).  In a sharded run every rank returns the rows it holds."""
+        result = getattr(self, 'result', None)
+        if result is None:
+            raise RuntimeError('get_trajectory_lengths needs the result of run()')
+        for name in ('lon', 'lat'):
+            if name not in result:
+                raise KeyError('%s is not in self.result (export_variables)' % name)
+        return self.ctx.trajectory_lengths(result['lon'], result['lat'], self.time_step_output.total_seconds())
+
     def clone(self):
         """basemodel/__init__.py:572-581: a new instance of the same class (on the same device, with the same random-number and
         stage arithmetic settings) with every config value copied and the same reader OBJECTS added under the same names, every

@@ -1,0 +1,27 @@
+"""CPU: the kernels of csrc/odr_geodinv.hip.h keep the inverse geodesic -- its Newton loop, three coefficient series, the astroid
+solve -- in registers: no scratch memory.  k_traj_segments has exactly its two float32 position tiles in LDS (64 trajectories x 65
+output times, each), k_geod_inverse and k_traj_totals none.  DESIGN.md section 8i has the register counts of the build it was written
+with; the test prints the present ones.  Reads the metadata of the library's gfx950 code object."""
+import os
+
+import pytest
+
+from test_layout_spec_resources import READELF
+from test_ship_kernel_resources import kernel_resources
+
+pytestmark = pytest.mark.skipif(not os.path.exists(READELF), reason='needs the ROCm LLVM tools')
+
+LDS = {'k_geod_inverse': 0, 'k_traj_segments': 2 * 64 * 65 * 4, 'k_traj_totals': 0}
+
+
+@pytest.mark.parametrize('kernel', sorted(LDS))
+def test_no_scratch_and_the_designed_lds(kernel):
+    import __graft_entry__ as g
+    g.build()
+    from opendrift_amd import _abi
+    found = kernel_resources(_abi.LIB_PATH, kernel)
+    print(found)
+    assert len(found) == 1, '%s is not in the library exactly once: %s' % (kernel, found)
+    assert found[0]['private_segment_fixed_size'] == 0, found
+    assert found[0]['group_segment_fixed_size'] == LDS[kernel], found
+    assert found[0]['vgpr_count'] <= 256, found      # 256 lanes per workgroup: one workgroup per SIMD quad must fit
