@@ -917,6 +917,36 @@ int odr_trajectory_lengths(odr_ctx *ctx, int64_t n_trajectories, int32_t n_times
  * (tools/bench_trajectory_lengths.py) */
 int odr_trajectory_lengths_last_kernel_ms(odr_ctx *ctx, float *ms);
 
+/* ---------------------------------------------------------------- seeding geometry
+ * pyproj.Geod(ellps='WGS84').npts(lon1, lat1, lon2, lat2, npts) as seed_cone and seed_repeated_segment call it
+ * (models/basemodel/__init__.py:1286-1291, :1432-1437): npts points on the WGS84 geodesic from point 1 to point 2 at
+ * i * s12 / (npts + 1), i = 1 .. npts -- both ends excluded.  One inverse (csrc/odr_geodinv.hip.h) for s12 and the azimuth, then one
+ * direct solve per lane (csrc/odr_geodesic.hip.h); longitudes come out in [-180, 180].  out_lon, out_lat: host, npts float64.
+ * Synchronous.  ODR_ERR_INVALID: npts < 0, a NULL output, a coordinate that is not finite, |lat| > 90. */
+int odr_geod_npts(odr_ctx *ctx, double lon1, double lat1, double lon2, double lat2, int64_t npts, double *out_lon, double *out_lat);
+/* matplotlib.path.Path(ring).contains_points(points): the crossing rule of its point_in_path in float64 for n points (x, y) and a
+ * ring of m vertices (vx, vy), the edge from the last vertex back to the first included; inside[i] = 1 or 0.  All arrays host.
+ * The flags are matplotlib's bit for bit (csrc/odr_seed.hip.h).  Synchronous.
+ * ODR_ERR_INVALID: a NULL pointer, n < 0, m < 3, a vertex that is not finite -- checked before anything is launched. */
+int odr_points_in_polygon(odr_ctx *ctx, int64_t n, const double *x, const double *y, int32_t m, const double *vx, const double *vy,
+                          uint8_t *inside);
+/* OpenDriftSimulation.points_within_polygon (models/basemodel/__init__.py:1487-1558): `number` positions evenly placed within the
+ * polygon of m vertices (lons, lats; host float64 degrees, closed here if the last vertex differs from the first).  A regular grid
+ * of spacing sqrt(area / number) is laid over the ring in the spherical Albers projection the reference asks for (R = 6370997 m,
+ * standard parallels at the extreme latitudes, the four parameters rounded to 6 decimals as its '%f' does), every grid point is
+ * inverse-projected and tested against the ring in lon / lat, and the points inside are kept in grid order (row-major, x fastest).
+ * Element k of out_lon / out_lat (host, `number` float64) is inside point k mod n_inside.  No grid point inside: the caller's
+ * vertices lons[0 : number] take their place, repeated in the same way.  An empty grid (nx * ny == 0): every element is the mean
+ * of the vertices.  n_inside: the inside points of the whole grid (before the cut at `number`); nx, ny: the grid.  The set-up is
+ * O(m) work on the host; no atomics: two calls give the same bits, and the host build of the header gives those bits too.
+ * Synchronous.  ODR_ERR_INVALID: a NULL pointer, m < 3, number < 1, a vertex that is not finite, a cone constant |n| < 1e-10
+ * (parallels symmetric about the equator: PROJ refuses them), an area that is zero or not finite, nx * ny >= 2^31 -- checked
+ * before anything is launched. */
+int odr_polygon_points(odr_ctx *ctx, int32_t m, const double *lons, const double *lats, int64_t number, double *out_lon,
+                       double *out_lat, int64_t *n_inside, int32_t *nx, int32_t *ny);
+/* device time [ms] of the kernel launches of this process's last odr_polygon_points (tools/bench_seed.py); 0 when it launched none */
+int odr_polygon_points_last_kernel_ms(odr_ctx *ctx, float *ms);
+
 /* ---------------------------------------------------------------- ROMS sigma grid
  * The sigma -> z regridding reader_ROMS_native.get_variables applies to every 4-D variable of a block
  * (reader_ROMS_native.py:512-538,617-684) with roppy (readers/roppy/depth.py): sdepth (:31-113, rho points,

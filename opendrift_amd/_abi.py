@@ -232,6 +232,10 @@ _SIGNATURES = {
     'odr_geod_inverse': [_vp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp],
     'odr_trajectory_lengths': [_vp, C.c_int64, C.c_int32, _vp, _vp, C.c_double, _dp, _dp, _dp],
     'odr_trajectory_lengths_last_kernel_ms': [_vp, _fp],
+    'odr_geod_npts': [_vp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int64, _dp, _dp],
+    'odr_points_in_polygon': [_vp, C.c_int64, _dp, _dp, C.c_int32, _dp, _dp, _P(C.c_uint8)],
+    'odr_polygon_points': [_vp, C.c_int32, _dp, _dp, C.c_int64, _dp, _dp, _P(C.c_int64), _P(C.c_int32), _P(C.c_int32)],
+    'odr_polygon_points_last_kernel_ms': [_vp, _fp],
 }
 EXPORTS = sorted(list(_SIGNATURES) + ['odr_last_error', 'odr_version'])
 

@@ -424,7 +424,7 @@ __host__ __device__ __forceinline__ void traj_segment(float lon1, float lat1, fl
   distance = s12; speed = v;
 }
 
-#ifndef ODR_GEODINV_HOST
+#if !defined(ODR_GEODINV_HOST) && !defined(ODR_GEODINV_NO_KERNELS)      // odr_seed.hip.h takes the functions alone
 constexpr int TRAJ_TILE = 64;                     // trajectories and output intervals of one workgroup's tile
 constexpr int TRAJ_TILE_PITCH = TRAJ_TILE + 1;    // floats of a tile row: 65 times, and odd, so that a wave reading a column hits every bank once
 
@@ -485,6 +485,6 @@ __global__ __launch_bounds__(BLOCK) void k_traj_totals(const double *__restrict_
   for (int t = 1; t < n_segments; ++t) sum += dist[(size_t)t * (size_t)pitch + (size_t)r];
   total[r] = sum;
 }
-#endif  // ODR_GEODINV_HOST
+#endif  // kernels
 
 }  // namespace odr

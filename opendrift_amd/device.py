@@ -530,6 +530,44 @@ class Context:
         check(self.lib.odr_trajectory_lengths_last_kernel_ms(self.h, C.byref(ms)))
         return ms.value
 
+    def geod_npts(self, lon1, lat1, lon2, lat2, npts):
+        """pyproj.Geod(ellps='WGS84').npts on the device (odr_geod_npts): (lon, lat) float64 arrays of the npts points at
+        i * s12 / (npts + 1), i = 1 .. npts, on the geodesic from point 1 to point 2 -- both ends excluded."""
+        npts = int(npts)
+        lon, lat = np.empty(max(npts, 0)), np.empty(max(npts, 0))
+        check(self.lib.odr_geod_npts(self.h, float(lon1), float(lat1), float(lon2), float(lat2), npts, lon.ctypes.data_as(_dp),
+                                     lat.ctypes.data_as(_dp)))
+        return lon, lat
+
+    def points_in_polygon(self, x, y, vx, vy):
+        """matplotlib.path.Path(np.c_[vx, vy]).contains_points(np.c_[x, y]) on the device (odr_points_in_polygon): a bool array."""
+        x, y = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (x, y))
+        vx, vy = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (vx, vy))
+        if len(x) != len(y) or len(vx) != len(vy):
+            raise ValueError('points_in_polygon: %d x and %d y, %d vx and %d vy' % (len(x), len(y), len(vx), len(vy)))
+        inside = np.zeros(len(x), np.uint8)
+        check(self.lib.odr_points_in_polygon(self.h, len(x), x.ctypes.data_as(_dp), y.ctypes.data_as(_dp), len(vx),
+                                             vx.ctypes.data_as(_dp), vy.ctypes.data_as(_dp), inside.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return inside.astype(bool)
+
+    def points_within_polygon(self, lons, lats, number, info=False):
+        """OpenDriftSimulation.points_within_polygon on the device (odr_polygon_points): (lonpoints, latpoints), `number` float64
+        each; info=True adds dict(n_inside, nx, ny): the grid and how many of its points lie inside."""
+        lons, lats = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (lons, lats))
+        if len(lons) != len(lats):
+            raise ValueError('lon and lat arrays must have same length.')
+        number = int(number)
+        lon, lat = np.empty(max(number, 0)), np.empty(max(number, 0))
+        n_inside, nx, ny = C.c_int64(), C.c_int32(), C.c_int32()
+        check(self.lib.odr_polygon_points(self.h, len(lons), lons.ctypes.data_as(_dp), lats.ctypes.data_as(_dp), number,
+                                          lon.ctypes.data_as(_dp), lat.ctypes.data_as(_dp), C.byref(n_inside), C.byref(nx), C.byref(ny)))
+        return (lon, lat, dict(n_inside=n_inside.value, nx=nx.value, ny=ny.value)) if info else (lon, lat)
+
+    def polygon_points_last_kernel_ms(self):
+        ms = C.c_float()
+        check(self.lib.odr_polygon_points_last_kernel_ms(self.h, C.byref(ms)))
+        return ms.value
+
     def particles(self, capacity):
         return Particles(self, capacity)
 

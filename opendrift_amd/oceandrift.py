@@ -15,6 +15,7 @@ Every per-particle operation is a call into libodrift_hip.so; this file is orche
 Out of scope (host-side features of the reference that are not on the path): plotting, netCDF
 export, the GSHHG global landmask (`general:use_auto_landmask`), lazy readers.
 """
+import json
 import logging
 import time
 from datetime import datetime, timedelta
@@ -404,6 +405,114 @@ class OpenDriftSimulation(Configurable):
         d = T.download()
         T.close()
         return d['lon'], d['lat']
+
+    # ------------------------------------------------------------------ seeding geometry (:1240-1558)
+    def seed_cone(self, lon, lat, time, radius=0, number=None, **kwargs):
+        """basemodel/__init__.py:1240-1353: elements along a transect from (lon0, lat0) with uncertainty radius r0 at time t0
+        towards (lon1, lat1) with r1 at t1.  The `number` positions are pyproj.Geod.npts' on the WGS84 geodesic between the two
+        points, both ends excluded, solved on the device (odr_geod_npts); everything goes on to seed_elements."""
+        self._require('Config', 'Ready')
+        if number is None:
+            number = self.get_config('seed:number')
+        if number == 1:
+            raise ValueError('For a cone, the number of elements must be at least 2 or more, given is 1')
+        lon, lat = np.atleast_1d(lon).ravel(), np.atleast_1d(lat).ravel()
+        radius = np.atleast_1d(radius).ravel()
+        if len(lon) != len(lat):
+            raise ValueError('Lon and lat must have same length (1 or 2)')
+        elif len(lon) > 2:
+            raise ValueError('Lon and lat must have length 1 or 2, given length is %s' % (len(lon)))
+        elif len(lon) == 1:
+            lonin, latin = None, None
+            lon, lat = lon * np.ones(number), lat * np.ones(number)
+        else:      # segment from (lon0, lat0) to (lon1, lat1); npts places points in between and does not include these
+            lonin, latin = lon, lat
+            lon, lat = self.ctx.geod_npts(lon[0], lat[0], lon[1], lat[1], number)
+        if len(radius) > 2:
+            raise ValueError('Seed radius must have length 1 or 2')
+        elif len(radius) == 2:      # linear increase from r0 to r1
+            radius = np.linspace(radius[0], radius[1], number)
+        if isinstance(time, list) and len(time) == 1:
+            time = time[0]
+        timespan = [time[0], time[-1]] if hasattr(time, '__len__') else [time, time]
+        radius = radius.astype(np.float32)
+        self.seed_cone_arguments = {'lon': lonin if lonin is not None else [lon.min(), lon.max()],
+                                    'lat': latin if latin is not None else [lat.min(), lat.max()],
+                                    'radius': [float(radius[0]), float(radius[-1])], 'time': timespan, 'number': number}
+        self.seed_elements(lon=lon, lat=lat, time=time, radius=radius, number=number, **kwargs)
+
+    def seed_from_geojson(self, gjson):
+        """basemodel/__init__.py:1356-1399: one GeoJSON Feature; a Polygon goes to seed_within_polygon, a LineString to seed_cone,
+        a Point to seed_elements.  Its property `time` (an ISO string or a list of two; a trailing Z is accepted, the time zone
+        dropped) is the seeding time, the other properties are keyword arguments."""
+        self._require('Config', 'Ready')
+        try:
+            gj = json.loads(gjson)
+            properties, geometry = gj['properties'], gj['geometry']
+            gtype, coords = geometry['type'], geometry['coordinates']
+        except Exception:
+            raise ValueError('Could not load GeoJSON string: %s' % gjson)
+        if 'time' not in properties:
+            raise ValueError('Property "time" is not available')
+        iso = lambda s: datetime.fromisoformat(s.replace('Z', '+00:00')).replace(tzinfo=None)
+        t = properties['time']
+        time = [iso(t[0]), iso(t[1])] if isinstance(t, list) else iso(t)
+        kwargs = {k: v for k, v in properties.items() if k != 'time'}
+        if gtype == 'Polygon':      # every position of every ring, as geojson.utils.coords yields them
+            pts = [p for ring in coords for p in ring]
+            self.seed_within_polygon(lons=[p[0] for p in pts], lats=[p[1] for p in pts], time=time, **kwargs)
+        elif gtype == 'LineString':
+            self.seed_cone(lon=[p[0] for p in coords], lat=[p[1] for p in coords], time=time, **kwargs)
+        elif gtype == 'Point':
+            self.seed_elements(lon=coords[0], lat=coords[1], time=time, **kwargs)
+        else:
+            raise ValueError('Not yet implemented')
+
+    def seed_repeated_segment(self, lons, lats, start_time, end_time, time_interval=None, number_per_segment=None,
+                              total_number=None, **kwargs):
+        """basemodel/__init__.py:1402-1456: elements repeatedly in time along the segment from (lons[0], lats[0]) to (lons[1],
+        lats[1]).  Either number_per_segment (the total is that times the number of times) or total_number (per segment:
+        total_number // len(times); the last points are repeated to reach the total)."""
+        self._require('Config', 'Ready')
+        numtimes = int((end_time - start_time).total_seconds() / time_interval.total_seconds() + 1)
+        times = [start_time + i * time_interval for i in range(numtimes)]
+        if number_per_segment is None:
+            number_per_segment = int(np.floor(total_number / numtimes))
+        slon, slat = self.ctx.geod_npts(lons[0], lats[0], lons[1], lats[1], number_per_segment)
+        lon, time = np.meshgrid(slon, np.array(times, dtype=object))
+        lat, time = np.meshgrid(slat, np.array(times, dtype=object))
+        lon, lat, time = lon.ravel(), lat.ravel(), time.ravel()
+        if total_number is not None:
+            additional_elements = total_number - len(lon)
+            lon = np.concatenate((lon, lon[-additional_elements::]))
+            lat = np.concatenate((lat, lat[-additional_elements::]))
+            time = np.concatenate((time, time[-additional_elements::]))
+        self.seed_elements(lon=lon, lat=lat, time=list(time), **kwargs)
+
+    def seed_within_polygon(self, lons, lats, number=None, **kwargs):
+        """basemodel/__init__.py:1459-1484: `number` elements evenly placed within the polygon (lons, lats); the keyword arguments
+        go on to seed_elements."""
+        self._require('Config', 'Ready')
+        if number == 0:
+            return
+        if number is None:
+            number = self.get_config('seed:number')
+        lonpoints, latpoints = self.points_within_polygon(lons, lats, number)
+        self.seed_elements(lonpoints, latpoints, number=number, **kwargs)
+
+    def points_within_polygon(self, lons, lats, number):
+        """basemodel/__init__.py:1487-1558: `number` positions (lon, lat) within the polygon, float64 -- a regular grid in the
+        reference's equal-area projection, the grid points inside the ring in grid order, the first ones repeated when there are
+        too few; the vertices themselves when no grid point is inside, their mean when the grid is empty.  The grid is laid out,
+        tested against the ring and compacted on the device (odr_polygon_points); a static method in the reference,
+        an instance method here because it needs the device context.  Fewer than three vertices: None, as in the reference."""
+        lons, lats = np.asarray(lons, dtype=np.float64), np.asarray(lats, dtype=np.float64)
+        if len(lons) < 3:
+            logger.info('At least three points needed to make a polygon')
+            return
+        if len(lons) != len(lats):
+            raise ValueError('lon and lat arrays must have same length.')
+        return self.ctx.points_within_polygon(lons, lats, number)
 
     # ------------------------------------------------------------------ counts (:841-867)
     def num_elements_active(self):
