@@ -1,18 +1,15 @@
 """Builds libodrift_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU).
 
-The library is nineteen translation units (csrc/odr_comm.hip, csrc/odrift.hip, odr_step.hip, odr_step_noise.hip, odr_step_fast.hip, odr_step_fast_noise.hip,
-odr_mix.hip, odr_step_tile.hip, odr_egg.hip, odr_sediment.hip, odr_larval.hip, odr_berg.hip, odr_ship.hip, odr_radio.hip, odr_larvalx.hip, odr_density.hip, odr_ftle.hip, odr_geodinv.hip, odr_seed.hip) compiled in parallel and
-linked into one shared object; objects are rebuilt only when a source they include changed."""
+The library is one translation unit per csrc/*.hip, compiled in parallel and linked into one shared object; an object is
+rebuilt when its source, any csrc/*.h or include/odrift.h changed."""
 import os
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
-UNITS = ['odr_step_noise.hip', 'odr_step_fast_noise.hip', 'odr_step.hip', 'odr_step_fast.hip', 'odrift.hip', 'odr_mix.hip',
-         'odr_step_tile.hip', 'odr_comm.hip', 'odr_egg.hip', 'odr_sediment.hip', 'odr_larval.hip', 'odr_berg.hip', 'odr_ship.hip', 'odr_radio.hip', 'odr_larvalx.hip', 'odr_density.hip', 'odr_ftle.hip', 'odr_geodinv.hip', 'odr_seed.hip']
-HEADERS = [os.path.join(CSRC, f) for f in ('odr_host.h', 'odr_step_launch.h', 'odr_kernels.hip.h', 'odr_field.hip.h', 'odr_geodesic.hip.h',
-                                           'odr_oil.hip.h', 'odr_seawater.hip.h', 'odr_egg.hip.h', 'odr_sediment.hip.h', 'odr_larval.hip.h', 'odr_berg.hip.h', 'odr_ship.hip.h', 'odr_radio.hip.h', 'odr_larvalx.hip.h', 'odr_density.hip.h', 'odr_ftle.hip.h', 'odr_geodinv.hip.h', 'odr_seed.hip.h', 'odr_solar.hip.h', 'odr_mesh.h', 'odr_tile.hip.h')] + \
+UNITS = sorted(f for f in os.listdir(CSRC) if f.endswith('.hip'))
+HEADERS = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith('.h')) + \
     [os.path.join(os.path.dirname(HERE), 'include', 'odrift.h')]
 LIB = os.path.join(HERE, 'libodrift_hip.so')
 OBJDIR = os.path.join(HERE, 'build')

@@ -3,26 +3,11 @@
 #include "odr_host.h"
 #include "odr_berg.hip.h"
 
-static int berg_slots(const odr_particles *p, std::initializer_list<int> slots, int n_must_be_set) {
-  unsigned seen = 0;
-  for (int k : slots) {
-    REQUIRE(k >= 0 && k < 9, "bad property slot %d", k);
-    if (k == AUX_KMEMBER && p->kmember_on)      // (as odr_particles_set_property)
-      return fail(ODR_ERR_STATE, "property slot %d parks the member of an ensemble ocean_vertical_diffusivity on this particle set", k);
-    REQUIRE(!(seen & (1u << k)), "property slot %d given twice", k);
-    seen |= 1u << k;
-  }
-  int j = 0;
-  for (int k : slots)
-    if (j++ < n_must_be_set && !p->aux[k]) return fail(ODR_ERR_STATE, "property slot %d has not been set", k);
-  return 0;
-}
-
 // length, width, sail and draft of every active element after the stability test of Wagner et al. (models/openberg.py:587-614;
 // odr_berg.hip.h).  Enqueued on the context's stream, no host synchronisation.
 int odr_berg_roll_over(odr_ctx *c, odr_particles *p, int sail_slot, int draft_slot, int length_slot, int width_slot) {
   REQUIRE(c && p, "NULL argument");
-  if (int rc = berg_slots(p, {sail_slot, draft_slot, length_slot, width_slot}, 4)) return rc;
+  if (int rc = property_slots(p, {sail_slot, draft_slot, length_slot, width_slot}, 4)) return rc;
   p->epoch++;  // invalidates the cached reductions (reduce())
   if (p->n == 0) return 0;
   hipLaunchKernelGGL(k_berg_roll_over, dim3(nblk(p->n)), dim3(BLOCK), 0, c->stream, (long long)p->n, p->aux[sail_slot], p->aux[draft_slot],
@@ -77,7 +62,7 @@ int odr_berg_advect(odr_ctx *c, odr_particles *p, int sail_slot, int draft_slot,
   if (!p->env[VAR_U] || !p->env[VAR_V]) return fail(ODR_ERR_STATE, "the current (x_sea_water_velocity, y_sea_water_velocity) must have been sampled");
   if (!p->env[VAR_XWIND] || !p->env[VAR_YWIND]) return fail(ODR_ERR_STATE, "the wind (x_wind, y_wind) must have been sampled");
   if (stokes_drift && (!p->env[VAR_SX] || !p->env[VAR_SY])) return fail(ODR_ERR_STATE, "the Stokes drift must have been sampled when stokes_drift is set");
-  if (int rc = berg_slots(p, {sail_slot, draft_slot, length_slot, width_slot, x_velocity_slot, y_velocity_slot}, 4)) return rc;
+  if (int rc = property_slots(p, {sail_slot, draft_slot, length_slot, width_slot, x_velocity_slot, y_velocity_slot}, 4)) return rc;
   if (n_attempts) *n_attempts = 0;
   if (n_rejected) *n_rejected = 0;
   p->epoch++;  // positions, moving and two properties change

@@ -7,12 +7,9 @@
 // (models/pelagicegg.py:100-179; odr_egg.hip.h).  Enqueued on the context's stream, no host synchronisation.
 int odr_egg_terminal_velocity(odr_ctx *c, odr_particles *p, int diameter_slot, int salinity_slot) {
   REQUIRE(c && p, "NULL argument");
-  REQUIRE(diameter_slot >= 0 && diameter_slot < 9 && salinity_slot >= 0 && salinity_slot < 9 && diameter_slot != salinity_slot,
-          "bad property slots %d, %d", diameter_slot, salinity_slot);
+  if (int rc = property_slots(p, {diameter_slot, salinity_slot})) return rc;
   if (!p->env[VAR_TEMP] || !p->env[VAR_SALT])
     return fail(ODR_ERR_STATE, "sea_water_temperature and sea_water_salinity must have been sampled");
-  for (int k : {diameter_slot, salinity_slot})
-    if (!p->aux[k]) return fail(ODR_ERR_STATE, "property slot %d has not been set", k);
   p->epoch++;  // invalidates the cached reductions (reduce())
   if (p->n == 0) return 0;
   hipLaunchKernelGGL(k_egg_terminal_velocity, dim3(nblk(p->n)), dim3(BLOCK), 0, c->stream, (long long)p->n, p->env[VAR_TEMP],

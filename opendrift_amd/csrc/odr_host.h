@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -243,6 +244,23 @@ static inline int scratch(odr_ctx *c, odr_particles *p, size_t bytes, void **out
     p->scratch_bytes = bytes;
   }
   *out = p->scratch;
+  return 0;
+}
+
+// The property slots a model's entry point was handed: each in 0 .. 8, none given twice, none the slot the library owns on
+// this particle set; the first n_must_be_set of them (default: all) written before (the others are outputs the call allocates)
+static inline int property_slots(const odr_particles *p, std::initializer_list<int> slots, int n_must_be_set = -1 /* all */) {
+  unsigned seen = 0;
+  for (int k : slots) {
+    REQUIRE(k >= 0 && k < 9, "bad property slot %d", k);
+    if (k == AUX_KMEMBER && p->kmember_on)      // (as odr_particles_set_property)
+      return fail(ODR_ERR_STATE, "property slot %d parks the member of an ensemble ocean_vertical_diffusivity on this particle set", k);
+    REQUIRE(!(seen & (1u << k)), "property slot %d given twice", k);
+    seen |= 1u << k;
+  }
+  int j = 0;
+  for (int k : slots)
+    if ((n_must_be_set < 0 || j++ < n_must_be_set) && !p->aux[k]) return fail(ODR_ERR_STATE, "property slot %d has not been set", k);
   return 0;
 }
 

@@ -3,18 +3,6 @@
 #include "odr_host.h"
 #include "odr_larval.hip.h"
 
-static int larval_slots(const odr_particles *p, std::initializer_list<int> slots) {
-  unsigned seen = 0;
-  for (int k : slots) {
-    REQUIRE(k >= 0 && k < 9, "bad property slot %d", k);
-    REQUIRE(!(seen & (1u << k)), "property slot %d given twice", k);
-    seen |= 1u << k;
-  }
-  for (int k : slots)
-    if (!p->aux[k]) return fail(ODR_ERR_STATE, "property slot %d has not been set", k);
-  return 0;
-}
-
 // Hatching, growth and length of every active element from the sampled temperature and four property slots
 // (models/larvalfish.py:185-231; odr_larval.hip.h).  Enqueued on the context's stream, no host synchronisation.
 int odr_larval_update(odr_ctx *c, odr_particles *p, int stage_fraction_slot, int hatched_slot, int weight_slot, int length_slot,
@@ -22,7 +10,7 @@ int odr_larval_update(odr_ctx *c, odr_particles *p, int stage_fraction_slot, int
   REQUIRE(c && p, "NULL argument");
   REQUIRE(dt_seconds == dt_seconds, "dt_seconds is NaN");
   if (!p->env[VAR_TEMP]) return fail(ODR_ERR_STATE, "sea_water_temperature must have been sampled");
-  if (int rc = larval_slots(p, {stage_fraction_slot, hatched_slot, weight_slot, length_slot})) return rc;
+  if (int rc = property_slots(p, {stage_fraction_slot, hatched_slot, weight_slot, length_slot})) return rc;
   p->epoch++;  // invalidates the cached reductions (reduce())
   if (p->n == 0) return 0;
   hipLaunchKernelGGL(k_larval_update, dim3(nblk(p->n)), dim3(BLOCK), 0, c->stream, (long long)p->n, p->env[VAR_TEMP],
@@ -39,7 +27,7 @@ int odr_larval_migrate(odr_ctx *c, odr_particles *p, int hatched_slot, int lengt
   REQUIRE(c && p, "NULL argument");
   REQUIRE(dt_seconds == dt_seconds && fraction_swimming == fraction_swimming, "NaN argument");
   REQUIRE(direction == 1 || direction == -1, "direction is %d, not +1 or -1", direction);
-  if (int rc = larval_slots(p, {hatched_slot, length_slot})) return rc;
+  if (int rc = property_slots(p, {hatched_slot, length_slot})) return rc;
   p->epoch++;  // z changes
   if (p->n == 0) return 0;
   hipLaunchKernelGGL(k_larval_migrate, dim3(nblk(p->n)), dim3(BLOCK), 0, c->stream, (long long)p->n, p->aux[hatched_slot],

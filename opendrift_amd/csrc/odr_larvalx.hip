@@ -4,18 +4,6 @@
 #include "odr_host.h"
 #include "odr_larvalx.hip.h"
 
-static int larvalx_slots(const odr_particles *p, std::initializer_list<int> slots) {
-  unsigned seen = 0;
-  for (int k : slots) {
-    REQUIRE(k >= 0 && k < 9, "bad property slot %d", k);
-    REQUIRE(!(seen & (1u << k)), "property slot %d given twice", k);
-    seen |= 1u << k;
-  }
-  for (int k : slots)
-    if (!p->aux[k]) return fail(ODR_ERR_STATE, "property slot %d has not been set", k);
-  return 0;
-}
-
 // Solar elevation [deg] of every active element into out_host[0 .. n) (models/physics_methods.py:977-979, :1036-1043;
 // odr_solar.hip.h).  Waits for the context's stream: the values are in out_host on return.
 int odr_solar_elevation(odr_ctx *c, odr_particles *p, double declination_rad, double time_offset_minutes, double day_minutes,
@@ -38,7 +26,7 @@ int odr_solar_elevation(odr_ctx *c, odr_particles *p, double declination_rad, do
 int odr_larvalx_hatch(odr_ctx *c, odr_particles *p, int stage_fraction_slot, int hatched_slot, double increment) {
   REQUIRE(c && p, "NULL argument");
   REQUIRE(increment == increment, "increment is NaN");
-  if (int rc = larvalx_slots(p, {stage_fraction_slot, hatched_slot})) return rc;
+  if (int rc = property_slots(p, {stage_fraction_slot, hatched_slot})) return rc;
   p->epoch++;  // invalidates the cached reductions (reduce())
   if (p->n == 0) return 0;
   hipLaunchKernelGGL(k_larvalx_hatch, dim3(nblk(p->n)), dim3(BLOCK), 0, c->stream, (long long)p->n, (float)increment,
@@ -61,7 +49,7 @@ int odr_larvalx_behave(odr_ctx *c, odr_particles *p, int hatched_slot, int mode,
             time_offset_minutes == time_offset_minutes && day_minutes == day_minutes, "NaN argument or negative half-width");
   if (!p->env[VAR_DEPTH]) return fail(ODR_ERR_STATE, "sea_floor_depth_below_sea_level has not been sampled");
   if (active_only_hatched)
-    if (int rc = larvalx_slots(p, {hatched_slot})) return rc;
+    if (int rc = property_slots(p, {hatched_slot})) return rc;
   if (!(w_active > 0.0) || !(dt_seconds > 0.0)) return 0;     // :246-247: nothing moves, nothing is clipped
   p->epoch++;  // z changes
   if (p->n == 0) return 0;

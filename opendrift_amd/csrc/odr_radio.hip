@@ -88,18 +88,6 @@ int odr_radio_counts(odr_ctx *c, odr_radio *r, int64_t *counts49, int reset) {
   return 0;
 }
 
-static int radio_slots(const odr_particles *p, std::initializer_list<int> slots) {
-  unsigned seen = 0;
-  for (int k : slots) {
-    REQUIRE(k >= 0 && k < 9, "bad property slot %d", k);
-    REQUIRE(!(seen & (1u << k)), "property slot %d given twice", k);
-    seen |= 1u << k;
-  }
-  for (int k : slots)
-    if (!p->aux[k]) return fail(ODR_ERR_STATE, "property slot %d has not been set", k);
-  return 0;
-}
-
 // the caller's draws (ODR_RNG_HOST) behind each other in the particle set's scratch buffer
 static int radio_draws(odr_ctx *c, odr_particles *p, std::initializer_list<const double *> host, RadioDraws &H) {
   const size_t n = (size_t)p->n;
@@ -126,7 +114,7 @@ int odr_radio_speciation(odr_ctx *c, odr_particles *p, odr_radio *r, int specie_
   REQUIRE(dt_seconds == dt_seconds, "dt_seconds is NaN");
   REQUIRE(rng_mode == ODR_RNG_DEVICE || rng_mode == ODR_RNG_HOST, "unknown rng_mode %d", rng_mode);
   REQUIRE(conc3_var >= 0 && conc3_var < NVAR, "bad variable id %d for conc3", (int)conc3_var);
-  if (int rc = radio_slots(p, {specie_slot, diameter_slot})) return rc;
+  if (int rc = property_slots(p, {specie_slot, diameter_slot})) return rc;
   if (!p->env[VAR_DEPTH]) return fail(ODR_ERR_STATE, "sea_floor_depth_below_sea_level must have been sampled");
   if (r->S.lmm >= 0 && !p->env[conc3_var]) return fail(ODR_ERR_STATE, "conc3 (variable slot %d) must have been sampled", (int)conc3_var);
   if (r->S.nsal > 1 && !p->env[VAR_SALT]) return fail(ODR_ERR_STATE, "sea_water_salinity must have been sampled");
@@ -149,7 +137,7 @@ int odr_radio_speciation(odr_ctx *c, odr_particles *p, odr_radio *r, int specie_
 // diameter and density, times moving (models/radionuclides.py:665-721 without profiles).  No host synchronisation.
 int odr_radio_terminal_velocity(odr_ctx *c, odr_particles *p, int diameter_slot, int density_slot) {
   REQUIRE(c && p, "NULL argument");
-  if (int rc = radio_slots(p, {diameter_slot, density_slot})) return rc;
+  if (int rc = property_slots(p, {diameter_slot, density_slot})) return rc;
   if (!p->env[VAR_TEMP] || !p->env[VAR_SALT])
     return fail(ODR_ERR_STATE, "sea_water_temperature and sea_water_salinity must have been sampled");
   p->epoch++;  // invalidates the cached reductions (reduce())
@@ -166,7 +154,7 @@ int odr_radio_resuspend(odr_ctx *c, odr_particles *p, odr_radio *r, int specie_s
                         const double *diameter_noise, const double *depth_noise, uint64_t step) {
   REQUIRE(c && p && r, "NULL argument");
   REQUIRE(rng_mode == ODR_RNG_DEVICE || rng_mode == ODR_RNG_HOST, "unknown rng_mode %d", rng_mode);
-  if (int rc = radio_slots(p, {specie_slot, diameter_slot})) return rc;
+  if (int rc = property_slots(p, {specie_slot, diameter_slot})) return rc;
   if (!p->env[VAR_U] || !p->env[VAR_V])
     return fail(ODR_ERR_STATE, "x_sea_water_velocity and y_sea_water_velocity must have been sampled");
   if (!p->env[VAR_DEPTH]) return fail(ODR_ERR_STATE, "sea_floor_depth_below_sea_level must have been sampled");

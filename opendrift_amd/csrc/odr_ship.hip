@@ -3,21 +3,6 @@
 #include "odr_host.h"
 #include "odr_ship.hip.h"
 
-// (the slot check of odr_berg.hip)
-static int ship_slots(const odr_particles *p, std::initializer_list<int> slots) {
-  unsigned seen = 0;
-  for (int k : slots) {
-    REQUIRE(k >= 0 && k < 9, "bad property slot %d", k);
-    if (k == AUX_KMEMBER && p->kmember_on)      // (as odr_particles_set_property)
-      return fail(ODR_ERR_STATE, "property slot %d parks the member of an ensemble ocean_vertical_diffusivity on this particle set", k);
-    REQUIRE(!(seen & (1u << k)), "property slot %d given twice", k);
-    seen |= 1u << k;
-  }
-  for (int k : slots)
-    if (!p->aux[k]) return fail(ODR_ERR_STATE, "property slot %d has not been set", k);
-  return 0;
-}
-
 // The class tables of a run on the device: n_classes x 49 x 2 doubles (F, D at the 49 spectrum points below omega = 7), kept with
 // their count.
 struct odr_ship_table {
@@ -69,7 +54,7 @@ int odr_ship_drift(odr_ctx *c, odr_particles *p, int length_slot, int height_slo
   if (wave_dir_from_stokes && (!p->env[VAR_SX] || !p->env[VAR_SY]))
     return fail(ODR_ERR_STATE, "the Stokes drift must have been sampled when wave_dir_from_stokes is set");
   if ((hs_mode == 0 && !p->env[VAR_HS]) || (tp_mode == 0 && !p->env[VAR_TP])) return fail(ODR_ERR_STATE, "Hs/Tp not sampled");
-  if (int rc = ship_slots(p, {length_slot, height_slot, draft_slot, beam_slot, wind_drag_slot, water_drag_slot, orientation_slot, class_slot}))
+  if (int rc = property_slots(p, {length_slot, height_slot, draft_slot, beam_slot, wind_drag_slot, water_drag_slot, orientation_slot, class_slot}))
     return rc;
   p->epoch++;          // positions, status and moving change
   p->status_epoch++;   // (elements may be deactivated)

@@ -25,10 +25,8 @@ vertical_mixing:TSprofiles = True is not built: set_config refuses it by name, a
 rng='numpy' consumes np.random as the reference does: random(n) once per mixing sub-step.  A sharded run needs nothing new: both
 kernels are per element and every rank reads the same clock.
 """
-import numpy as np
-
 from . import _abi
-from .config import CONFIG_LEVEL_ADVANCED, CONFIG_LEVEL_ESSENTIAL
+from .config import CONFIG_LEVEL_ADVANCED
 from .oceandrift import OceanDrift
 
 
@@ -37,6 +35,7 @@ class LarvalFish(OceanDrift):
     aux_properties = list(_abi.LARVA_PROPERTIES)     # slot order of odr_particles_set_property
     aux_defaults = {'diameter': 0.0014, 'neutral_buoyancy_salinity': 31.25, 'stage_fraction': 0., 'hatched': 0., 'length': 0.,
                     'weight': 0.08, 'survival': 1.}   # :31-52 (NEA cod)
+    fuse_vertical_advection = False     # update(): the reference's has no vertical advection at all
     required_variables = {   # larvalfish.py:69-84
         'x_sea_water_velocity': {'fallback': 0},
         'y_sea_water_velocity': {'fallback': 0},
@@ -59,24 +58,9 @@ class LarvalFish(OceanDrift):
         self._add_config({     # :92-99
             'IBM:fraction_of_timestep_swimming': {'type': 'float', 'default': 0.15, 'min': 0.0, 'max': 1.0, 'units': 'fraction',
                                                   'description': 'Fraction of timestep swimming', 'level': CONFIG_LEVEL_ADVANCED}})
-        self._add_config({'seed:%s' % k: {'type': 'float', 'default': v, 'min': -1e12, 'max': 1e12, 'level': CONFIG_LEVEL_ESSENTIAL, 'description': ''}
-                          for k, v in self.aux_defaults.items()})
         self._set_config_default('drift:vertical_mixing', True)      # :101-103
         self._set_config_default('drift:vertical_mixing_at_surface', True)
         self._set_config_default('drift:vertical_advection_at_surface', True)
-
-    def seed_elements(self, lon, lat, time=None, **kwargs):
-        """The seven properties as scalars or per-element arrays; defaults from seed:<name>."""
-        given = {k: kwargs.pop(k, None) for k in self.aux_properties}
-        n_before = 0 if self._sched is None else len(self._sched['lon'])
-        super().seed_elements(lon, lat, time, **kwargs)
-        n_new = len(self._sched['lon']) - n_before
-        for k, v in given.items():
-            v = self.get_config('seed:%s' % k) if v is None else v
-            if np.size(v) not in (1, n_new):
-                raise ValueError('%s has length %s, but %s elements were seeded' % (k, np.size(v), n_new))
-            v = np.asarray(v, dtype=np.float32) * np.ones(n_new, np.float32)
-            self._sched[k] = v if n_before == 0 else np.concatenate([self._sched[k], v])
 
     def update_terminal_velocity(self, Tprofiles=None, Sprofiles=None, z_index=None):   # :105-183
         if Tprofiles is not None or Sprofiles is not None:
@@ -84,13 +68,6 @@ class LarvalFish(OceanDrift):
         if self.num_elements_active() > 0:
             self.P.egg_terminal_velocity(self.aux_properties.index('diameter'),
                                          self.aux_properties.index('neutral_buoyancy_salinity'))
-
-    def vertical_advection(self):   # oceandrift.py:315-350
-        # A method of this class, so that OceanDrift.vertical_mixing does not fold the vertical advection into the mixing launch
-        # (it does when the stock method follows it directly): the reference's update() has no vertical advection at all
-        if self.get_config('drift:vertical_advection') is False:
-            return
-        self.P.vertical_advection(self.time_step.total_seconds(), self.get_config('drift:vertical_advection_at_surface'))
 
     def update_fish_larvae(self):   # :200-231 (the early return without larvae there is logging only)
         if self.num_elements_active() > 0:

@@ -37,6 +37,7 @@ class LarvalFishExtended(OceanDrift):
     """opendrift/models/larvalfish_extended.py:44-342 (see the module docstring)."""
     aux_properties = list(_abi.LARVALX_PROPERTIES)     # slot order of odr_particles_set_property
     aux_defaults = {'stage_fraction': 0., 'hatched': 0.}   # :34-41
+    fuse_vertical_advection = False     # update(): the reference's has no vertical advection at all
     required_variables = {   # larvalfish_extended.py:73-88
         'x_sea_water_velocity': {'fallback': 0},
         'y_sea_water_velocity': {'fallback': 0},
@@ -81,31 +82,9 @@ class LarvalFishExtended(OceanDrift):
             'egg:hatch_time_days': {'type': 'float', 'default': 2.0, 'min': 0.004, 'max': 416, 'units': 'days', 'level': CONFIG_LEVEL_BASIC,
                                     'description': 'Time to hatching when hatching_method is fixed_time.'},
         })
-        self._add_config({'seed:%s' % k: {'type': 'float', 'default': v, 'min': -1e12, 'max': 1e12, 'level': CONFIG_LEVEL_ESSENTIAL, 'description': ''}
-                          for k, v in self.aux_defaults.items()})
         self._set_config_default('drift:vertical_mixing', True)      # :169-171
         self._set_config_default('drift:vertical_mixing_at_surface', True)
         self._set_config_default('drift:vertical_advection_at_surface', True)
-
-    def seed_elements(self, lon, lat, time=None, **kwargs):
-        """The two properties as scalars or per-element arrays; defaults from seed:<name>."""
-        given = {k: kwargs.pop(k, None) for k in self.aux_properties}
-        n_before = 0 if self._sched is None else len(self._sched['lon'])
-        super().seed_elements(lon, lat, time, **kwargs)
-        n_new = len(self._sched['lon']) - n_before
-        for k, v in given.items():
-            v = self.get_config('seed:%s' % k) if v is None else v
-            if np.size(v) not in (1, n_new):
-                raise ValueError('%s has length %s, but %s elements were seeded' % (k, np.size(v), n_new))
-            v = np.asarray(v, dtype=np.float32) * np.ones(n_new, np.float32)
-            self._sched[k] = v if n_before == 0 else np.concatenate([self._sched[k], v])
-
-    def vertical_advection(self):   # oceandrift.py:315-350
-        # A method of this class, so that OceanDrift.vertical_mixing does not fold the vertical advection into the mixing launch
-        # (it does when the stock method follows it directly): the reference's update() has no vertical advection at all
-        if self.get_config('drift:vertical_advection') is False:
-            return
-        self.P.vertical_advection(self.time_step.total_seconds(), self.get_config('drift:vertical_advection_at_surface'))
 
     def _compute_band_half_width(self, z):   # :177-186
         dz = self.get_config('biology:dz_rel') * np.abs(z)

@@ -121,37 +121,29 @@ class Leeway(OpenDriftSimulation):
         with its draws made BEFORE the base class draws the seeding radius (:327-346 before :386).  Extension: explicit
         per-element arrays downwind_slope=..., crosswind_slope=..., ... (no draws)."""
         explicit = {k: kwargs.pop(k) for k in list(kwargs) if k in self.aux_properties and k != 'jibe_probability'}
-        n_before = 0 if self._sched is None else len(self._sched['lon'])
-        jibe = kwargs.pop('jibe_probability', None)
         coefficient_arrays = [k for k in explicit if k != 'capsized']
         if object_type is not None or (leeway_coefficients is None and not coefficient_arrays):
             if leeway_coefficients is not None:
                 raise ValueError('object_type and leeway_coefficients are both given')
             leeway_coefficients = self._object_class(object_type)
-        props = None
         if leeway_coefficients is not None:
             lon_a = np.atleast_1d(lon).ravel()
             if kwargs.get('number') is not None:              # :297-302
-                number = kwargs['number']
+                drawn = kwargs['number']
             elif len(lon_a) > 1:
-                number = len(lon_a)
+                drawn = len(lon_a)
             else:
-                number = self.get_config('seed:number')
-            props = self._perturbed_coefficients(leeway_coefficients, number, explicit)
-        super().seed_elements(lon, lat, **kwargs)
+                drawn = self.get_config('seed:number')
+            props = self._perturbed_coefficients(leeway_coefficients, drawn, explicit)
+        else:
+            drawn = None
+            props = dict(dict(downwind_slope=1, crosswind_slope=1, downwind_offset=0, crosswind_offset=0, downwind_eps=0,
+                              crosswind_eps=0, orientation=1, capsized=0), **explicit)     # LeewayObj defaults (:50-131)
+        n_before = 0 if self._sched is None else len(self._sched['lon'])
+        super().seed_elements(lon, lat, **props, **kwargs)
         number = len(self._sched['lon']) - n_before
-        if props is not None and len(props['orientation']) != number:
-            raise ValueError('Leeway.seed_elements: %d elements were seeded, the coefficients were drawn for %d'
-                             % (number, len(props['orientation'])))
-        if props is None:
-            defaults = dict(downwind_slope=1, crosswind_slope=1, downwind_offset=0, crosswind_offset=0, downwind_eps=0,
-                            crosswind_eps=0, orientation=1, capsized=0)     # LeewayObj defaults (:50-131)
-            props = {k: np.asarray(explicit.get(k, v), dtype=np.float64) * np.ones(number) for k, v in defaults.items()}
-        if jibe is not None:
-            self._sched['jibe_probability'][n_before:] = np.float32(jibe)
-        for k, v in props.items():
-            v = np.asarray(v, dtype=np.float32)
-            self._sched[k] = v if n_before == 0 else np.concatenate([self._sched[k], v])
+        if drawn is not None and drawn != number:      # (a single draw would have been taken for every element)
+            raise ValueError('Leeway.seed_elements: %d elements were seeded, the coefficients were drawn for %d' % (number, drawn))
 
     @staticmethod
     def _perturbed_coefficients(c, number, explicit):

@@ -138,7 +138,7 @@ class OpenDriftSimulation(Configurable):
                                                 'level': CONFIG_LEVEL_BASIC, 'description': ''},
                 'environment:fallback:%s' % v: {'type': 'float', 'default': spec.get('fallback'), 'min': -1e12,
                                                 'max': 1e12, 'level': CONFIG_LEVEL_BASIC, 'description': ''}})
-        for prop, default in self.element_properties.items():
+        for prop, default in {**self.element_properties, **getattr(self, 'aux_defaults', {})}.items():
             self._add_config({'seed:%s' % prop: {'type': 'float', 'default': default, 'min': -1e12, 'max': 1e12,
                                                  'level': CONFIG_LEVEL_ESSENTIAL, 'description': ''}})
 
@@ -302,6 +302,19 @@ class OpenDriftSimulation(Configurable):
         return False
 
     # ------------------------------------------------------------------ seeding (:1033-1330)
+    def _seed_number(self, lon, time, number=None, number_per_point=None):
+        """How many elements seed_elements(lon, lat, time, number=..., number_per_point=...) schedules."""
+        nlon, ntime = np.size(lon), np.size(time)
+        if nlon <= 1:
+            return (ntime if ntime > 2 else self.get_config('seed:number')) if number is None else number
+        if number_per_point is not None:
+            if number is not None:
+                raise ValueError('Both number and number_per_point is provided')
+            number = number_per_point * nlon
+        if number is not None and number % nlon != 0:
+            raise ValueError('Lon and lat have length %s, but number is %s, which is not a multiple' % (nlon, number))
+        return max(number or 0, nlon)
+
     def seed_elements(self, lon, lat, time, radius=0, number=None, number_per_point=None,
                       radius_type='gaussian', **kwargs):
         self._require('Config', 'Ready')
@@ -312,22 +325,10 @@ class OpenDriftSimulation(Configurable):
             raise ValueError('Latitude must be between -90 and 90 degrees')
         if len(lon) != len(lat):
             raise ValueError('Lon and lat must have same lengths')
+        number = self._seed_number(lon, time, number, number_per_point)
         if len(lon) > 1:
-            if number_per_point is not None:
-                if number is not None:
-                    raise ValueError('Both number and number_per_point is provided')
-                number = number_per_point * len(lon)
-            if number is not None:
-                if number % len(lon) != 0:
-                    raise ValueError('Lon and lat have length %s, but number is %s, which is not a multiple'
-                                     % (len(lon), number))
-                npp = int(number / len(lon))
-                if npp > 1:
-                    lon, lat = np.repeat(lon, npp), np.repeat(lat, npp)
-            number = len(lon)
+            lon, lat = np.repeat(lon, int(number // len(lon))), np.repeat(lat, int(number // len(lon)))
         else:
-            if number is None:
-                number = len(time) if len(time) > 2 else self.get_config('seed:number')
             lon, lat = lon * np.ones(number), lat * np.ones(number)
         if len(time) != number and len(time) > 1:
             if len(time) == 2:
@@ -375,6 +376,17 @@ class OpenDriftSimulation(Configurable):
         for prop in self.element_properties:
             val = kwargs.pop(prop, None)
             props[prop] = np.float32(self.get_config('seed:%s' % prop) if val is None else val) * np.ones(number, np.float32)
+        for prop in getattr(self, 'aux_properties', []):   # model-specific float32 properties: scalars or one value per element
+            if prop in props:
+                continue
+            val = kwargs.pop(prop, None)
+            if val is None:
+                if 'seed:%s' % prop not in self._config:
+                    raise TypeError('%s.seed_elements: no value for the property %s' % (type(self).__name__, prop))
+                val = self.get_config('seed:%s' % prop)
+            if np.size(val) not in (1, number):
+                raise ValueError('%s has length %s, but %s elements were seeded' % (prop, np.size(val), number))
+            props[prop] = np.asarray(val, np.float32) * np.ones(number, np.float32)
         if kwargs:
             raise TypeError('Redundant arguments: %s' % list(kwargs))
         # LagrangianArray stores lon/lat/z as float32 at seeding (elements.py:71-88,156-158)
@@ -1234,6 +1246,24 @@ class OpenDriftSimulation(Configurable):
         raise NotImplementedError('Any trajectory model implementation must define an update method.')
 
     # ------------------------------------------------------------------ run (:1828-2340)
+    @classmethod
+    def _stock_methods(cls, names):
+        return issubclass(cls, OceanDrift) and cls._fuses_vertical_advection() and \
+            all(getattr(cls, m) is getattr(OceanDrift, m) for m in names)
+
+    @classmethod
+    def _stock_speculation_methods(cls):
+        """The method half of run()'s `speculate`: what runs between the status scan and the end of the step is the stock code."""
+        return cls._stock_methods(('vertical_mixing', 'update_terminal_velocity', '_advect_wind_then_stokes_drift', 'advect_wind',
+                                   'stokes_drift', '_with_seafloor_action', '_seafloor_action_in_update'))
+
+    @classmethod
+    def _stock_update(cls):
+        """run()'s `stock_update`: update() cannot register a status category on its own."""
+        return cls._stock_methods(('update', 'vertical_mixing', 'update_terminal_velocity', '_advect_wind_then_stokes_drift',
+                                   'advect_wind', 'stokes_drift', '_with_seafloor_action', '_seafloor_action_in_update',
+                                   'vertical_buoyancy'))
+
     def run(self, time_step=None, steps=None, time_step_output=None, duration=None, end_time=None,
             outfile=None, export_variables=None, export_buffer_length=100, stop_on_error=False):
         self._require('Ready')
@@ -1421,13 +1451,9 @@ class OpenDriftSimulation(Configurable):
         # stock update() makes nothing but that launch between the scan and the end of the step -- no mover that could move an
         # element first (the wind is calm everywhere and there is no Stokes drift: decided on the host), stock methods, reader
         # diffusivity, device RNG.  Between output times only: the result buffer records z as it is BEFORE update().
-        cls, OD = type(self), OceanDrift
         sx, sy = 'sea_surface_wave_stokes_drift_x_velocity', 'sea_surface_wave_stokes_drift_y_velocity'
         speculate = bool(
-            fused_lane and not os.environ.get('ODR_NO_SPECULATION') and self.rng == 'device' and isinstance(self, OD) and
-            all(getattr(cls, m) is getattr(OD, m) for m in ('vertical_mixing', 'vertical_advection', 'update_terminal_velocity',
-                                                           '_advect_wind_then_stokes_drift', 'advect_wind', 'stokes_drift',
-                                                           '_with_seafloor_action', '_seafloor_action_in_update')) and
+            fused_lane and not os.environ.get('ODR_NO_SPECULATION') and self.rng == 'device' and self._stock_speculation_methods() and
             self.get_config('drift:vertical_mixing') is True and
             self.get_config('vertical_mixing:diffusivitymodel') == 'environment' and
             ('x_wind' not in self.required_variables or self._calm_everywhere()) and
@@ -1436,11 +1462,7 @@ class OpenDriftSimulation(Configurable):
         # the step's collective may be finished BEHIND update() only when update() cannot register a status category on its own
         # (a subclass's vertical_mixing / update_terminal_velocity calling deactivate_elements would append it before the other
         # ranks' categories on a deferring rank and after them on a blocking one: ADVICE round 5): the stock methods only
-        stock_update = isinstance(self, OD) and all(
-            getattr(cls, m) is getattr(OD, m) for m in ('update', 'vertical_mixing', 'vertical_advection', 'update_terminal_velocity',
-                                                        '_advect_wind_then_stokes_drift', 'advect_wind', 'stokes_drift',
-                                                        '_with_seafloor_action', '_seafloor_action_in_update',
-                                                        'vertical_buoyancy'))
+        stock_update = self._stock_update()
         self._vmix_speculated = False
         self.ctx.sync()
         t_loop = [time.perf_counter(), None]      # main-loop wall time (the reference keeps 'main loop' timers, basemodel :2174)
@@ -2069,6 +2091,9 @@ class OceanDrift(OpenDriftSimulation):
     # environment variables whose value AT the element nothing in run() / OceanDrift.update reads (the mixing scheme takes the
     # diffusivity from the profiles, oceandrift.py:428-449; the element value is only exported): see run(), fused lane
     _export_only_variables = ('ocean_vertical_diffusivity', )
+    # vertical_mixing() folds the vertical advection into its launch: right when update() calls the stock vertical_advection()
+    # directly after it (_fuses_vertical_advection)
+    fuse_vertical_advection = True
     required_variables = {
         'x_sea_water_velocity': {'fallback': 0},
         'y_sea_water_velocity': {'fallback': 0},
@@ -2136,14 +2161,19 @@ class OceanDrift(OpenDriftSimulation):
         })
         self._set_config_default('drift:max_speed', 2)
 
+    @classmethod
+    def _fuses_vertical_advection(cls):
+        """The mixing launch may take the vertical advection with it: the class says so and runs the stock method (a subclass
+        that overrides vertical_advection switches the fusion off by doing so)."""
+        return cls.fuse_vertical_advection and cls.vertical_advection is OceanDrift.vertical_advection
+
     def vertical_mixing(self, _guarded=False):   # oceandrift.py:397-571
         """_guarded (run(), fused lane): the launch is enqueued BEHIND the fold of the step's status scan and BEFORE the host has
         read it -- it does nothing unless every element stays (Particles.vmix(guarded=True)); returns whether it was enqueued.
         update() then finds the step's mixing done (`_vmix_speculated`) and returns here at once."""
         if getattr(self, '_vmix_speculated', False) and not _guarded:
             self._vmix_speculated = False
-            self._vadv_fused = bool(self.get_config('drift:vertical_advection')) and \
-                type(self).vertical_advection is OceanDrift.vertical_advection
+            self._vadv_fused = bool(self.get_config('drift:vertical_advection')) and self._fuses_vertical_advection()
             return
         if self.get_config('drift:vertical_mixing') is False:
             return False
@@ -2155,7 +2185,7 @@ class OceanDrift(OpenDriftSimulation):
         # its block, _profile_level_cut -- golden c24c; whole columns for a reader that ignores the depth range asked, c24a)
         dt, dt_mix = self.time_step.total_seconds(), self.get_config('vertical_mixing:timestep')
         fuse = None
-        if self.get_config('drift:vertical_advection') and type(self).vertical_advection is OceanDrift.vertical_advection:
+        if self.get_config('drift:vertical_advection') and self._fuses_vertical_advection():
             fuse = bool(self.get_config('drift:vertical_advection_at_surface'))
             self._vadv_fused = True
         kw = dict(mix_at_surface=self.get_config('drift:vertical_mixing_at_surface'), fuse_vertical_advection=fuse)

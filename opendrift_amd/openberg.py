@@ -85,7 +85,7 @@ class OpenBerg(OceanDrift):
             'melting:lateral': b(True, 'If True, lateral melting is enabled'),
             'melting:basal': b(True, 'If True, basal melting is enabled')}, overwrite=True)      # (drift:stokes_drift is OceanDrift's too: off here)
         self._add_config({'seed:%s' % k: {'type': 'float', 'default': v, 'min': -1e12, 'max': 1e12, 'level': CONFIG_LEVEL_ESSENTIAL, 'description': ''}
-                          for k, v in list(self.aux_defaults.items()) + list(COEFFICIENTS.items())})
+                          for k, v in COEFFICIENTS.items()})
         self.coefficients = None      # fixed by the first seed_elements
         self.solver_attempts = []     # (attempts, rejected attempts) of every advect_iceberg
         self._lat_is_float32 = True   # set where run() starts
@@ -118,17 +118,8 @@ class OpenBerg(OceanDrift):
             k = [k for k in coef if coef[k] != self.coefficients[k]][0]
             raise NotImplementedError('%s differs from an earlier seed_elements call: the coefficients are scalars of the run '
                                       '(DESIGN.md section 7e)' % k)
-        given = {k: kwargs.pop(k, None) for k in self.aux_properties}
-        n_before = 0 if self._sched is None else len(self._sched['lon'])
         super().seed_elements(lon, lat, time, **kwargs)
         self.coefficients = coef
-        n_new = len(self._sched['lon']) - n_before
-        for k, v in given.items():
-            v = self.get_config('seed:%s' % k) if v is None else v
-            if np.size(v) not in (1, n_new):
-                raise ValueError('%s has length %s, but %s elements were seeded' % (k, np.size(v), n_new))
-            v = np.asarray(v, dtype=np.float32) * np.ones(n_new, np.float32)
-            self._sched[k] = v if n_before == 0 else np.concatenate([self._sched[k], v])
 
     def run(self, *args, **kwargs):
         # a run that starts from seeded elements starts from float32 latitudes again (as f32_first of OceanDrift.run)

@@ -150,16 +150,9 @@ class OpenOil(OceanDrift):
                 mu, sigma2 = self.get_config('seed:droplet_diameter_mu'), self.get_config('seed:droplet_diameter_sigma')**2
                 s2 = np.log(sigma2 / mu**2 + 1)
                 diameter = np.random.lognormal(np.log(mu) - s2 / 2, s2**0.5, number)
-        n_before = 0 if self._sched is None else len(self._sched['lon'])
-        super().seed_elements(lon, lat, time, **kwargs)
-        n_new = len(self._sched['lon']) - n_before
-        if diameter is not None and np.size(diameter) not in (1, n_new):
-            raise ValueError('diameter has length %s, but %s elements were seeded' % (np.size(diameter), n_new))
-        props = dict(diameter=0.0 if diameter is None else diameter, density=self.oiltype['density'],
-                     viscosity=self.oiltype['viscosity'], oil_film_thickness=oil_film_thickness, diameter_if_entrained=0.0)
-        for k, v in props.items():
-            v = np.asarray(v, dtype=np.float32) * np.ones(n_new, np.float32)
-            self._sched[k] = v if n_before == 0 else np.concatenate([self._sched[k], v])
+        super().seed_elements(lon, lat, time, diameter=0.0 if diameter is None else diameter, density=self.oiltype['density'],
+                              viscosity=self.oiltype['viscosity'], oil_film_thickness=oil_film_thickness, diameter_if_entrained=0.0,
+                              **kwargs)
 
     # ---- PhysicsMethods pieces that OpenOil evaluates differently from OceanDrift
     def _wave_modes(self):

@@ -25,10 +25,7 @@ eighteen.
 
 rng='numpy' consumes np.random as the reference does: random(n) once per mixing sub-step.
 """
-import numpy as np
-
 from . import _abi
-from .config import CONFIG_LEVEL_ESSENTIAL
 from .oceandrift import OceanDrift
 
 # required by the reference's class, read by nothing in it, and without a device variable id
@@ -40,6 +37,7 @@ class PelagicEggDrift(OceanDrift):
     """opendrift/models/pelagicegg.py:45-193 (see the module docstring: four required variables are accepted, not sampled)."""
     aux_properties = list(_abi.EGG_PROPERTIES)     # slot order of odr_particles_set_property
     aux_defaults = {'diameter': 0.0014, 'neutral_buoyancy_salinity': 31.25, 'density': 1028., 'hatched': 0.}   # :30-42 (NEA cod)
+    fuse_vertical_advection = False     # update(): the current advection lies between the mixing and the vertical advection
     required_variables = {   # pelagicegg.py:60-79
         'x_sea_water_velocity': {'fallback': 0},
         'y_sea_water_velocity': {'fallback': 0},
@@ -65,8 +63,6 @@ class PelagicEggDrift(OceanDrift):
         super().__init__(*args, **kwargs)       # (config keys for all eighteen variables)
         for v in UNSAMPLED_VARIABLES:
             self.required_variables.pop(v)
-        self._add_config({'seed:%s' % k: {'type': 'float', 'default': v, 'min': -1e12, 'max': 1e12, 'level': CONFIG_LEVEL_ESSENTIAL, 'description': ''}
-                          for k, v in self.aux_defaults.items()})
         self._set_config_default('general:coastline_action', 'previous')      # :92-98
         self._set_config_default('drift:vertical_mixing', True)
         self._set_config_default('drift:vertical_mixing_at_surface', True)
@@ -80,33 +76,12 @@ class PelagicEggDrift(OceanDrift):
                 raise TypeError('Please provide Reader object')
             super().add_reader(r, [v for v in (variables or r.variables) if v not in UNSAMPLED_VARIABLES], first)
 
-    def seed_elements(self, lon, lat, time=None, **kwargs):
-        """The egg properties as scalars or per-element arrays; defaults from seed:<name>."""
-        given = {k: kwargs.pop(k, None) for k in self.aux_properties}
-        n_before = 0 if self._sched is None else len(self._sched['lon'])
-        super().seed_elements(lon, lat, time, **kwargs)
-        n_new = len(self._sched['lon']) - n_before
-        for k, v in given.items():
-            v = self.get_config('seed:%s' % k) if v is None else v
-            if np.size(v) not in (1, n_new):
-                raise ValueError('%s has length %s, but %s elements were seeded' % (k, np.size(v), n_new))
-            v = np.asarray(v, dtype=np.float32) * np.ones(n_new, np.float32)
-            self._sched[k] = v if n_before == 0 else np.concatenate([self._sched[k], v])
-
     def update_terminal_velocity(self, Tprofiles=None, Sprofiles=None, z_index=None):   # :100-179
         if Tprofiles is not None or Sprofiles is not None:
             raise NotImplementedError('temperature / salinity profiles in update_terminal_velocity (DESIGN.md section 7b)')
         if self.num_elements_active() > 0:
             self.P.egg_terminal_velocity(self.aux_properties.index('diameter'),
                                          self.aux_properties.index('neutral_buoyancy_salinity'))
-
-    def vertical_advection(self):   # oceandrift.py:315-350
-        # A method of this class, so that OceanDrift.vertical_mixing does not fold the vertical advection into the mixing launch
-        # (it does when the stock method follows it directly): the current advection lies between the two here, and its
-        # Runge-Kutta stages sample at the depth the mixing left
-        if self.get_config('drift:vertical_advection') is False:
-            return
-        self.P.vertical_advection(self.time_step.total_seconds(), self.get_config('drift:vertical_advection_at_surface'))
 
     def update(self):   # :181-193
         self.update_terminal_velocity()

@@ -138,6 +138,7 @@ class RadionuclideDrift(OceanDrift):
     """opendrift/models/radionuclides.py:58-1044 (see the module docstring)."""
     aux_properties = list(_abi.RADIO_PROPERTIES)     # slot order of odr_particles_set_property
     aux_defaults = {'diameter': 0., 'neutral_buoyancy_salinity': 31.25, 'density': 2650., 'specie': 0}   # :31-43
+    fuse_vertical_advection = False     # update(): resuspension and the current advection lie between the mixing and the vertical advection
     required_variables = {   # :77-96
         'x_sea_water_velocity': {'fallback': None},
         'y_sea_water_velocity': {'fallback': None},
@@ -199,8 +200,7 @@ class RadionuclideDrift(OceanDrift):
             'radionuclide:output:depthintervals': {'type': 'str', 'default': '-25, -10., -5., -1.', 'min_length': 0, 'max_length': 60,
                                                    'level': E, 'description': 'Depth intervals for computation of concentration'},
         })
-        self._add_config({'seed:%s' % k: {'type': 'float', 'default': v, 'min': -1e12, 'max': 1e12, 'level': E, 'description': ''}
-                          for k, v in self.aux_defaults.items() if k != 'specie'})
+        del self._config['seed:specie']      # drawn or given in seed_elements, never a default of the run
         self._set_config_default('drift:vertical_mixing', True)      # :206-208
         self._set_config_default('drift:vertical_mixing_at_surface', True)
         self._set_config_default('drift:vertical_advection_at_surface', True)
@@ -346,20 +346,11 @@ class RadionuclideDrift(OceanDrift):
         is_particle = np.array(['particle' in name.lower() for name in self.name_species])
         particles = np.concatenate([np.flatnonzero(init_specie == k) for k in np.flatnonzero(is_particle)] + [np.empty(0, int)]).astype(int)
         init_diam = self.set_init_diameter(num_elements, particles, diameter, kwargs.pop('diameter_rng', None))
-        given = {k: kwargs.pop(k, None) for k in ('neutral_buoyancy_salinity', 'density')}
         n_before = 0 if self._sched is None else len(self._sched['lon'])
-        super().seed_elements(lon, lat, time, **kwargs)
+        super().seed_elements(lon, lat, time, specie=init_specie, diameter=init_diam, **kwargs)
         n_new = len(self._sched['lon']) - n_before
-        if n_new != num_elements:
+        if n_new != num_elements:      # (a single draw would have been taken for every element)
             raise ValueError('%s elements were seeded, but the species were drawn for %s' % (n_new, num_elements))
-        props = {'specie': init_specie.astype(np.float32), 'diameter': init_diam.astype(np.float32)}
-        for k, v in given.items():
-            v = self.get_config('seed:%s' % k) if v is None else v
-            if np.size(v) not in (1, n_new):
-                raise ValueError('%s has length %s, but %s elements were seeded' % (k, np.size(v), n_new))
-            props[k] = np.asarray(v, dtype=np.float32) * np.ones(n_new, np.float32)
-        for k in self.aux_properties:
-            self._sched[k] = props[k] if n_before == 0 else np.concatenate([self._sched[k], props[k]])
 
     # ------------------------------------------------------------------ the run
     def run(self, *args, **kwargs):
@@ -423,13 +414,6 @@ class RadionuclideDrift(OceanDrift):
             kw.update(diameter_noise=self._host_noise(n),
                       depth_noise=np.random.normal(0, self.get_config('radionuclide:sediment:resuspension_depth_uncert'), n))
         self.P.radio_resuspend(self._setup(), **kw)
-
-    def vertical_advection(self):   # oceandrift.py:315-350
-        # A method of this class, so that OceanDrift.vertical_mixing does not fold the vertical advection into the mixing launch:
-        # resuspension and the current advection lie between the two here
-        if self.get_config('drift:vertical_advection') is False:
-            return
-        self.P.vertical_advection(self.time_step.total_seconds(), self.get_config('drift:vertical_advection_at_surface'))
 
     def update(self):   # :1004-1038
         if self.num_elements_active() == 0:

@@ -29,8 +29,6 @@ or a non-zero constant / fallback raises NotImplementedError.
 rng='numpy' consumes np.random as the reference does: random(n) once per mixing sub-step.  A sharded run needs nothing new:
 settling and resuspension are per element, no global reduction.
 """
-import numpy as np
-
 from .config import CONFIG_LEVEL_ESSENTIAL
 from .oceandrift import OceanDrift
 
@@ -40,8 +38,8 @@ REFUSED_SEAFLOOR_ACTIONS = ('none', 'previous')
 
 class SedimentDrift(OceanDrift):
     """opendrift/models/sedimentdrift.py:39-126 (see the module docstring)."""
-    aux_properties = ['settled']      # slot order of odr_particles_set_property
-    aux_defaults = {'settled': 0.}    # :30-32
+    aux_properties = ['settled']      # slot order of odr_particles_set_property; seeded from seed:settled (:30-32)
+    fuse_vertical_advection = False     # update(): the vertical advection comes BEFORE the mixing
     element_properties = dict(OceanDrift.element_properties, terminal_velocity=-0.001)   # :33-35: 1 mm/s negative buoyancy
     required_variables = {   # sedimentdrift.py:45-61
         'x_sea_water_velocity': {'fallback': 0},
@@ -83,18 +81,6 @@ class SedimentDrift(OceanDrift):
                                           '(DESIGN.md section 7c)' % TM02)
         super().add_reader(readers, variables, first)
 
-    def seed_elements(self, lon, lat, time=None, **kwargs):
-        """`settled` as a scalar or a per-element array; default from seed:settled."""
-        v = kwargs.pop('settled', None)
-        n_before = 0 if self._sched is None else len(self._sched['lon'])
-        super().seed_elements(lon, lat, time, **kwargs)
-        n_new = len(self._sched['lon']) - n_before
-        v = self.get_config('seed:settled') if v is None else v
-        if np.size(v) not in (1, n_new):
-            raise ValueError('settled has length %s, but %s elements were seeded' % (np.size(v), n_new))
-        v = np.asarray(v, dtype=np.float32) * np.ones(n_new, np.float32)
-        self._sched['settled'] = v if n_before == 0 else np.concatenate([self._sched['settled'], v])
-
     def run(self, *args, **kwargs):
         action = self.get_config('general:seafloor_action', 'lift_to_seafloor')
         if action in REFUSED_SEAFLOOR_ACTIONS:      # (before anything is set up on the device)
@@ -108,13 +94,6 @@ class SedimentDrift(OceanDrift):
 
     def bottom_interaction(self, Zmin=None):   # :108-116
         """Nothing to do here: the settling is part of the device's sea-floor check (_seafloor_action_in_update)."""
-
-    def vertical_advection(self):   # oceandrift.py:315-350
-        # A method of this class, so that OceanDrift.vertical_mixing does not fold the vertical advection into the mixing launch
-        # (it does when the stock method follows it directly): the vertical advection comes BEFORE the mixing here
-        if self.get_config('drift:vertical_advection') is False:
-            return
-        self.P.vertical_advection(self.time_step.total_seconds(), self.get_config('drift:vertical_advection_at_surface'))
 
     def resuspension(self):   # :118-126
         if self.num_elements_active() > 0:

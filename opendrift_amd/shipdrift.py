@@ -248,9 +248,7 @@ class ShipDrift(OceanDrift):
         0 / 1, else by seed:orientation."""
         given = {k: kwargs.pop(k, None) for k in DIMENSIONS}
         orientation = kwargs.pop('orientation', None)
-        n_before = 0 if self._sched is None else len(self._sched['lon'])
-        super().seed_elements(lon, lat, time, **kwargs)
-        num = len(self._sched['lon']) - n_before
+        num = self._seed_number(lon, time, kwargs.get('number'), kwargs.get('number_per_point'))
         dim = {}
         for k, v in given.items():
             v = self.get_config('seed:%s' % k) if v is None else v
@@ -275,8 +273,7 @@ class ShipDrift(OceanDrift):
         props.update(wind_drag_coeff=Cf.astype(np.float32), water_drag_coeff=Cd.astype(np.float32),
                      orientation=np.asarray(orientation, dtype=np.float32) * np.ones(num, np.float32))
         props['ship_class'] = self._class_indices(*clipped_ratios(props['length'], props['draft'], props['beam']))
-        for k in self.aux_properties:
-            self._sched[k] = props[k] if n_before == 0 else np.concatenate([self._sched[k], props[k]])
+        super().seed_elements(lon, lat, time, **props, **kwargs)
 
     def _wave_modes(self):
         """(hs_mode, tp_mode, wave_dir_from_stokes) of this step's odr_ship_drift.  Wave height and period: the sampled variable

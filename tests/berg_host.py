@@ -1,16 +1,11 @@
 """TEST INFRASTRUCTURE: ctypes access to opendrift_amd/csrc/odr_berg.hip.h compiled for the host (g++ -ffp-contract=off,
 tests/hostshim in place of the HIP runtime header), see berg_host.cpp."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-OUT = os.path.join(ROOT, 'oracle', '_build', 'berg_host.so')
-SRC = [os.path.join(HERE, 'berg_host.cpp'), os.path.join(HERE, 'hostshim', 'hip', 'hip_runtime.h'),
-       os.path.join(ROOT, 'opendrift_amd', 'csrc', 'odr_berg.hip.h')]
+from host_build import f32, geod_host, host_lib
+
 BLOCK = 256       # ODR_BLOCK (opendrift_amd/csrc/odr_kernels.hip.h): the workgroup size the sums are ordered by
 ENV = ('x_sea_water_velocity', 'y_sea_water_velocity', 'sea_surface_wave_stokes_drift_x_velocity', 'sea_surface_wave_stokes_drift_y_velocity',
        'x_wind', 'y_wind', 'sea_floor_depth_below_sea_level', 'sea_surface_height', 'sea_surface_wave_significant_height',
@@ -19,37 +14,19 @@ COEF = dict(weight_coef=1.0, water_form_drag_coef=0.25, water_skin_drag_coef=0.0
             wave_drag_coef=0.3)      # the order of BergCoef, the defaults of IcebergObj
 SOLVE = {0: 'ok', 1: 'error norm not finite', 2: 'step too small', 3: 'too many attempts'}
 _fp, _dp, _ip = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32)
-_lib = None
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(OUT) or any(os.path.getmtime(OUT) < os.path.getmtime(s) for s in SRC):
-            os.makedirs(os.path.dirname(OUT), exist_ok=True)
-            subprocess.check_call(['g++', '-O1', '-std=c++17', '-ffp-contract=off', '-I', os.path.join(HERE, 'hostshim'),
-                                   '-shared', '-fPIC', '-o', OUT, SRC[0]])
-        _lib = C.CDLL(OUT)
-        _lib.bergh_sin.restype = C.c_double
-        _lib.bergh_sin.argtypes = [C.c_double]
-    return _lib
-
-
-_geod = None
+def _lib():
+    L = host_lib('berg_host', ('odr_berg.hip.h',))
+    L.bergh_sin.restype = C.c_double
+    L.bergh_sin.argtypes = [C.c_double]
+    return L
 
 
 def geod_move(lat, lon, east, north):
     """One move of csrc/odr_geodesic.hip.h (tests/geod_host.cpp, the host build tests/test_geod_host.py uses) from (lat, lon) by
     (east, north) metres: (lat2, lon2)."""
-    global _geod
-    if _geod is None:
-        out, src = os.path.join(ROOT, 'oracle', '_build', 'geod_host.so'), os.path.join(HERE, 'geod_host.cpp')
-        deps = [src, SRC[1], os.path.join(ROOT, 'opendrift_amd', 'csrc', 'odr_geodesic.hip.h')]
-        if not os.path.exists(out) or any(os.path.getmtime(out) < os.path.getmtime(s) for s in deps):
-            os.makedirs(os.path.dirname(out), exist_ok=True)
-            subprocess.check_call(['g++', '-O1', '-std=c++17', '-ffp-contract=off', '-w', '-shared', '-fPIC', '-I' + os.path.join(HERE, 'hostshim'),
-                                   '-o', out, src])
-        _geod = C.CDLL(out)
+    _geod = geod_host()
     a = [np.ascontiguousarray(v, np.float64) for v in (lat, lon, east, north)]
     series = np.empty(len(a[0]), np.int32)
     for full in (1, 0):      # the complete solution, replaced by the series move wherever that is valid (as geod_local_move)
@@ -63,27 +40,23 @@ def geod_move(lat, lon, east, north):
     return lat2, lon2
 
 
-def _f32(a, n):
-    return np.array(np.broadcast_to(np.asarray(a, np.float32), (n,)), dtype=np.float32, order='C')
-
-
 def sin(x):
-    return lib().bergh_sin(float(x))
+    return _lib().bergh_sin(float(x))
 
 
 def sincosf(x):
     """berg_sincosf_numpy of a float32 array: (sin, cos)."""
     x = np.ascontiguousarray(x, np.float32)
     s, c = np.empty_like(x), np.empty_like(x)
-    lib().bergh_sincosf(C.c_longlong(len(x)), *(a.ctypes.data_as(_fp) for a in (x, s, c)))
+    _lib().bergh_sincosf(C.c_longlong(len(x)), *(a.ctypes.data_as(_fp) for a in (x, s, c)))
     return s, c
 
 
 def roll_over(sail, draft, length, width):
     """roll_over of every element: float32 copies of (sail, draft, length, width) after the call."""
     n = len(sail)
-    s, d, L, W = (_f32(a, n) for a in (sail, draft, length, width))
-    lib().bergh_roll_over(C.c_longlong(n), *(a.ctypes.data_as(_fp) for a in (s, d, L, W)))
+    s, d, L, W = (f32(a, n) for a in (sail, draft, length, width))
+    _lib().bergh_roll_over(C.c_longlong(n), *(a.ctypes.data_as(_fp) for a in (s, d, L, W)))
     return s, d, L, W
 
 
@@ -92,10 +65,10 @@ def advect(env, lat, sail, draft, length, width, moving, dt, wave_from_direction
     """advect_iceberg up to update_positions.  env: {variable name: float32 array}.  Returns a dict: V0x, V0y, Vx, Vy (float64),
     iceb_x_velocity, iceb_y_velocity (float32), grounded, moving, attempts, rejected, status (a key of SOLVE)."""
     n = len(lat)
-    e = [_f32(env[k], n) for k in ENV]
+    e = [f32(env[k], n) for k in ENV]
     envp = (_fp * len(ENV))(*(a.ctypes.data_as(_fp) for a in e))
     lat = np.array(lat, dtype=np.float64, order='C')
-    s, d, L, W = (_f32(a, n) for a in (sail, draft, length, width))
+    s, d, L, W = (f32(a, n) for a in (sail, draft, length, width))
     moving = np.array(moving, dtype=np.int32, order='C')
     k = dict(COEF, **coef)
     # IcebergObj declares the coefficients float32: the reference's float64 arrays hold float32 values (0.8 is 0.800000011920929)
@@ -105,7 +78,7 @@ def advect(env, lat, sail, draft, length, width, moving, dt, wave_from_direction
     xv, yv = np.zeros(n, np.float32), np.zeros(n, np.float32)
     grounded = np.zeros(n, np.int8)
     stat = np.zeros(2, np.int32)
-    rc = lib().bergh_advect(C.c_longlong(n), envp, lat.ctypes.data_as(_dp), *(a.ctypes.data_as(_fp) for a in (s, d, L, W)),
+    rc = _lib().bergh_advect(C.c_longlong(n), envp, lat.ctypes.data_as(_dp), *(a.ctypes.data_as(_fp) for a in (s, d, L, W)),
                             moving.ctypes.data_as(_ip), coefs.ctypes.data_as(_dp), C.c_double(wave_from_direction), C.c_double(sea_ice_thickness),
                             flags.ctypes.data_as(_ip), C.c_double(dt), C.c_int(block), *(out[name].ctypes.data_as(_dp) for name in ('V0x', 'V0y', 'Vx', 'Vy')),
                             xv.ctypes.data_as(_fp), yv.ctypes.data_as(_fp), grounded.ctypes.data_as(C.POINTER(C.c_byte)), stat.ctypes.data_as(_ip))

@@ -2,36 +2,23 @@
 the host (g++ -ffp-contract=off, tests/hostshim in place of the HIP runtime header), see density_host.cpp; the NumPy restatement of
 get_density_array's contract that the tests compare with; and the error bound of a weighted map."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-OUT = os.path.join(ROOT, 'oracle', '_build', 'density_host.so')
-SRC = [os.path.join(HERE, 'density_host.cpp'), os.path.join(HERE, 'hostshim', 'hip', 'hip_runtime.h'),
-       os.path.join(ROOT, 'opendrift_amd', 'csrc', 'odr_density.hip.h')]
+from host_build import host_lib
+
 _fp, _dp, _ip = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int)
-_lib = None
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(OUT) or any(os.path.getmtime(OUT) < os.path.getmtime(s) for s in SRC):
-            os.makedirs(os.path.dirname(OUT), exist_ok=True)
-            subprocess.check_call(['g++', '-O1', '-std=c++17', '-ffp-contract=off', '-I', os.path.join(HERE, 'hostshim'),
-                                   '-shared', '-fPIC', '-o', OUT, SRC[0]])
-        _lib = C.CDLL(OUT)
-    return _lib
+def _lib():
+    return host_lib('density_host', ('odr_density.hip.h',))
 
 
 def bins(v, edges):
     """The header's bin of every float64 value (-1: dropped)."""
     v, edges = np.ascontiguousarray(v, np.float64), np.ascontiguousarray(edges, np.float64)
     out = np.empty(len(v), np.int32)
-    lib().densh_bin(C.c_longlong(len(v)), v.ctypes.data_as(_dp), C.c_int(len(edges)), edges.ctypes.data_as(_dp), out.ctypes.data_as(_ip))
+    _lib().densh_bin(C.c_longlong(len(v)), v.ctypes.data_as(_dp), C.c_int(len(edges)), edges.ctypes.data_as(_dp), out.ctypes.data_as(_ip))
     return out
 
 
@@ -39,7 +26,7 @@ def classes(z, status, stranded_code):
     """Bit 0: counts in H, bit 1: in H_submerged, bit 2: in H_stranded."""
     z, status = np.ascontiguousarray(z, np.float32), np.ascontiguousarray(status, np.float32)
     out = np.empty(len(z), np.int32)
-    lib().densh_classes(C.c_longlong(len(z)), z.ctypes.data_as(_fp), status.ctypes.data_as(_fp), C.c_int(stranded_code), out.ctypes.data_as(_ip))
+    _lib().densh_classes(C.c_longlong(len(z)), z.ctypes.data_as(_fp), status.ctypes.data_as(_fp), C.c_int(stranded_code), out.ctypes.data_as(_ip))
     return out
 
 
@@ -50,7 +37,7 @@ def density_map(lon, lat, z, status, lon_edges, lat_edges, weight=None, stranded
     ntraj, nt = arrs[0].shape
     le, la = np.ascontiguousarray(lon_edges, np.float64), np.ascontiguousarray(lat_edges, np.float64)
     out = [np.zeros((nt, len(le) - 1, len(la) - 1)) for _ in range(3)]
-    lib().densh_map(C.c_longlong(ntraj), C.c_int(nt), *(a.ctypes.data_as(_fp) for a in arrs), w.ctypes.data_as(_fp) if w is not None else None,
+    _lib().densh_map(C.c_longlong(ntraj), C.c_int(nt), *(a.ctypes.data_as(_fp) for a in arrs), w.ctypes.data_as(_fp) if w is not None else None,
                     C.c_int(stranded_code), C.c_int(len(le)), le.ctypes.data_as(_dp), C.c_int(len(la)), la.ctypes.data_as(_dp),
                     *(o.ctypes.data_as(_dp) for o in out))
     return tuple(out)

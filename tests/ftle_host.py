@@ -2,18 +2,12 @@
 the host (g++ -ffp-contract=off, tests/hostshim in place of the HIP runtime header), see ftle_host.cpp; the NumPy restatement of
 physics_methods.ftle that the GPU tests compare with; the error measure and the measured bounds of the FTLE tests."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-OUT = os.path.join(ROOT, 'oracle', '_build', 'ftle_host.so')
-SRC = [os.path.join(HERE, 'ftle_host.cpp'), os.path.join(HERE, 'hostshim', 'hip', 'hip_runtime.h'),
-       os.path.join(ROOT, 'opendrift_amd', 'csrc', 'odr_ftle.hip.h')]
+from host_build import host_lib
+
 _fp, _dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
-_lib = None
 
 # max |host build - reference| / (1 / |T| + |reference|) over every finite cell of tests/golden/c33_ftle.npz: measured 8.71e-08 over
 # the fields of (a) and 1.04e-07 over the maps of (b) on the CPU the golden was written on (tools/gen_golden_ftle.py prints them);
@@ -30,15 +24,8 @@ PROJECTION_MEASURED = 1.20e-15
 PROJECTION_BOUND = 4 * PROJECTION_MEASURED
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(OUT) or any(os.path.getmtime(OUT) < os.path.getmtime(s) for s in SRC):
-            os.makedirs(os.path.dirname(OUT), exist_ok=True)
-            subprocess.check_call(['g++', '-O1', '-std=c++17', '-ffp-contract=off', '-I', os.path.join(HERE, 'hostshim'),
-                                   '-shared', '-fPIC', '-o', OUT, SRC[0]])
-        _lib = C.CDLL(OUT)
-    return _lib
+def _lib():
+    return host_lib('ftle_host', ('odr_ftle.hip.h',))
 
 
 def gradient(f):
@@ -46,7 +33,7 @@ def gradient(f):
     f = np.ascontiguousarray(f, np.float64)
     ny, nx = f.shape
     g0, g1 = np.empty_like(f), np.empty_like(f)
-    lib().ftleh_gradient(C.c_int(nx), C.c_int(ny), f.ctypes.data_as(_dp), g0.ctypes.data_as(_dp), g1.ctypes.data_as(_dp))
+    _lib().ftleh_gradient(C.c_int(nx), C.c_int(ny), f.ctypes.data_as(_dp), g0.ctypes.data_as(_dp), g1.ctypes.data_as(_dp))
     return [g0, g1]
 
 
@@ -56,7 +43,7 @@ def ftle_map(dX, dY, delta, duration_seconds):
     assert dX.ndim == 2 and dX.shape == dY.shape
     ny, nx = dX.shape
     out = np.empty((ny, nx), np.float32)
-    lib().ftleh_map(C.c_int(nx), C.c_int(ny), dX.ctypes.data_as(_dp), dY.ctypes.data_as(_dp), C.c_double(delta),
+    _lib().ftleh_map(C.c_int(nx), C.c_int(ny), dX.ctypes.data_as(_dp), dY.ctypes.data_as(_dp), C.c_double(delta),
                     C.c_double(duration_seconds), out.ctypes.data_as(_fp))
     return out
 

@@ -2,16 +2,11 @@
 the host (g++ -ffp-contract=off, tests/hostshim in place of the HIP runtime header), see geodinv_host.cpp; and the metric that turns
 an error of (azi1, s12) into metres at point 2."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-OUT = os.path.join(ROOT, 'oracle', '_build', 'geodinv_host.so')
-SRC = [os.path.join(HERE, 'geodinv_host.cpp'), os.path.join(HERE, 'hostshim', 'hip', 'hip_runtime.h'),
-       os.path.join(ROOT, 'opendrift_amd', 'csrc', 'odr_geodinv.hip.h'), os.path.join(ROOT, 'opendrift_amd', 'csrc', 'odr_geodesic.hip.h')]
+from host_build import host_lib
+
 _fp, _dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
 
 # Bounds: 4 x the host build's measured maximum (DESIGN.md sections 7e, 8i), all far inside the 1e-6 m pin of the oracle's own inverse.
@@ -21,18 +16,10 @@ _fp, _dp = C.POINTER(C.c_float), C.POINTER(C.c_double)
 KAT_S12_BOUND_M = 4 * 3.73e-9
 KAT_LANDING_BOUND_M = 4 * 3.83e-9
 C34_DISTANCE_BOUND_M = 4 * 2.68e-9
-_lib = None
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(OUT) or any(os.path.getmtime(OUT) < os.path.getmtime(s) for s in SRC):
-            os.makedirs(os.path.dirname(OUT), exist_ok=True)
-            subprocess.check_call(['g++', '-O1', '-std=c++17', '-ffp-contract=off', '-I', os.path.join(HERE, 'hostshim'),
-                                   '-shared', '-fPIC', '-o', OUT, SRC[0]])
-        _lib = C.CDLL(OUT)
-    return _lib
+def _lib():
+    return host_lib('geodinv_host', ('odr_geodinv.hip.h', 'odr_geodesic.hip.h'))
 
 
 def inverse(lon1, lat1, lon2, lat2):
@@ -41,7 +28,7 @@ def inverse(lon1, lat1, lon2, lat2):
                                                                             for v in (lon1, lat1, lon2, lat2)))]
     n = a[0].size
     out = [np.empty(a[0].shape) for _ in range(3)]
-    lib().geodinvh_inverse(C.c_longlong(n), *(v.ctypes.data_as(_dp) for v in a), *(o.ctypes.data_as(_dp) for o in out))
+    _lib().geodinvh_inverse(C.c_longlong(n), *(v.ctypes.data_as(_dp) for v in a), *(o.ctypes.data_as(_dp) for o in out))
     return tuple(out)
 
 
@@ -52,7 +39,7 @@ def trajectory_lengths(lon, lat, dt, segments=True):
     total = np.empty(ntraj)
     dist = np.empty((nt - 1, ntraj)) if segments else None
     speed = np.empty((nt - 1, ntraj)) if segments else None
-    lib().geodinvh_trajectory_lengths(C.c_longlong(ntraj), C.c_int(nt), lon.ctypes.data_as(_fp), lat.ctypes.data_as(_fp), C.c_double(dt),
+    _lib().geodinvh_trajectory_lengths(C.c_longlong(ntraj), C.c_int(nt), lon.ctypes.data_as(_fp), lat.ctypes.data_as(_fp), C.c_double(dt),
                                       total.ctypes.data_as(_dp), *(None if o is None else o.ctypes.data_as(_dp) for o in (dist, speed)))
     return (total, dist, speed) if segments else total
 

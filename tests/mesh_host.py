@@ -1,27 +1,17 @@
 """TEST INFRASTRUCTURE: ctypes access to opendrift_amd/csrc/odr_mesh.h compiled for the host (g++), see mesh_host.cpp."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-OUT = os.path.join(ROOT, 'oracle', '_build', 'mesh_host.so')
-SRC = [os.path.join(HERE, 'mesh_host.cpp'), os.path.join(ROOT, 'opendrift_amd', 'csrc', 'odr_mesh.h')]
+from host_build import host_lib
+
 _dp = C.POINTER(C.c_double)
-_lib = None
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(OUT) or any(os.path.getmtime(OUT) < os.path.getmtime(s) for s in SRC):
-            os.makedirs(os.path.dirname(OUT), exist_ok=True)
-            subprocess.check_call(['g++', '-O2', '-std=c++17', '-shared', '-fPIC', '-o', OUT, SRC[0]])
-        _lib = C.CDLL(OUT)
-        _lib.mesh_build.restype = C.c_void_p
-    return _lib
+def _lib():
+    L = host_lib('mesh_host', ('odr_mesh.h',), flags=('-O2',), shim=False)
+    L.mesh_build.restype = C.c_void_p
+    return L
 
 
 class HostMesh:
@@ -29,7 +19,7 @@ class HostMesh:
         lo = np.ascontiguousarray(lon2d, dtype=np.float64)
         la = np.ascontiguousarray(lat2d, dtype=np.float64)
         fl, nt, err = C.c_longlong(), C.c_longlong(), C.create_string_buffer(256)
-        h = lib().mesh_build(lo.ctypes.data_as(_dp), la.ctypes.data_as(_dp), lo.shape[0], lo.shape[1], C.byref(fl),
+        h = _lib().mesh_build(lo.ctypes.data_as(_dp), la.ctypes.data_as(_dp), lo.shape[0], lo.shape[1], C.byref(fl),
                              C.byref(nt), err, 256)
         if not h:
             raise ValueError(err.value.decode())
@@ -38,20 +28,20 @@ class HostMesh:
     def triangles(self):
         v = np.empty((self.ntri, 3), np.int32)
         n = np.empty((self.ntri, 3), np.int32)
-        lib().mesh_tris(self.h, v.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p))
+        _lib().mesh_tris(self.h, v.ctypes.data_as(C.c_void_p), n.ctypes.data_as(C.c_void_p))
         return v, n
 
     def locate(self, lon, lat):
         lon = np.ascontiguousarray(lon, dtype=np.float64)
         lat = np.ascontiguousarray(lat, dtype=np.float64)
         x, y = np.empty(len(lon)), np.empty(len(lon))
-        lib().mesh_locate(self.h, C.c_longlong(len(lon)), lon.ctypes.data_as(_dp), lat.ctypes.data_as(_dp),
+        _lib().mesh_locate(self.h, C.c_longlong(len(lon)), lon.ctypes.data_as(_dp), lat.ctypes.data_as(_dp),
                           x.ctypes.data_as(_dp), y.ctypes.data_as(_dp))
         return x, y
 
     def __del__(self):
         if getattr(self, 'h', None):
-            lib().mesh_free(self.h)
+            _lib().mesh_free(self.h)
             self.h = None
 
 

@@ -3,18 +3,14 @@
 see it (setup members from its stored configuration, one step's inputs, draws and expected outputs)."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
+from host_build import f32, f64, host_lib
+
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-OUT = os.path.join(ROOT, 'oracle', '_build', 'radio_host.so')
-SRC = [os.path.join(HERE, 'radio_host.cpp'), os.path.join(HERE, 'hostshim', 'hip', 'hip_runtime.h')] + \
-    [os.path.join(ROOT, 'opendrift_amd', 'csrc', f) for f in ('odr_radio.hip.h', 'odr_seawater.hip.h')]
 GOLDEN = os.path.join(HERE, 'golden', 'c30_radionuclides.npz')
 _fp, _dp, _ip, _lp = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
-_lib = None
 SPECIES = {'lmm': 'LMM', 'lmmcation': 'LMMcation', 'lmmanion': 'LMManion', 'polymer': 'Polymer', 'particle_rev': 'Particle reversible',
            'sediment_rev': 'Sediment reversible', 'particle_slow': 'Particle slowly reversible', 'sediment_slow': 'Sediment slowly reversible',
            'particle_irrev': 'Particle irreversible', 'sediment_irrev': 'Sediment irreversible'}
@@ -26,15 +22,8 @@ CONFIG = {'layer_thick': 'radionuclide:sediment:layer_thick', 'particle_diameter
           'resuspension_critvel': 'radionuclide:sediment:resuspension_critvel'}
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(OUT) or any(os.path.getmtime(OUT) < os.path.getmtime(s) for s in SRC):
-            os.makedirs(os.path.dirname(OUT), exist_ok=True)
-            subprocess.check_call(['g++', '-O1', '-std=c++17', '-ffp-contract=off', '-I', os.path.join(HERE, 'hostshim'),
-                                   '-shared', '-fPIC', '-o', OUT, SRC[0]])
-        _lib = C.CDLL(OUT)
-    return _lib
+def _lib():
+    return host_lib('radio_host', ('odr_radio.hip.h', 'odr_seawater.hip.h'))
 
 
 def golden_setup(G, case):
@@ -62,23 +51,15 @@ def _table(m):
     return np.ascontiguousarray(t)
 
 
-def _f(a, n):
-    return np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32), (n,)))
-
-
-def _d(a, n):
-    return np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float64), (n,)))
-
-
 def speciation(m, dt, specie, diameter, moving, z, sal, depth, conc3, u1, u2, diameter_noise, depth_noise, noise_is_final=True):
     """One odr_radio_speciation launch on the host: returns dict(specie, diameter, moving, z, counts[7, 7], bad)."""
     n = len(specie)
     sp, di, mv, zz = np.array(specie, np.float32), np.array(diameter, np.float32), np.array(moving, np.int32), np.array(z, np.float64)
     counts = np.zeros(50, np.int64)
     st, tb = _setup_vector(m, dt), _table(m)
-    ins = [_f(sal, n), _f(depth, n), _f(conc3, n)]
-    dr = [_d(a, n) for a in (u1, u2, diameter_noise, depth_noise)]
-    lib().radioh_speciation(C.c_longlong(n), st.ctypes.data_as(_dp), tb.ctypes.data_as(_dp), sp.ctypes.data_as(_fp), di.ctypes.data_as(_fp),
+    ins = [f32(sal, n), f32(depth, n), f32(conc3, n)]
+    dr = [f64(a, n) for a in (u1, u2, diameter_noise, depth_noise)]
+    _lib().radioh_speciation(C.c_longlong(n), st.ctypes.data_as(_dp), tb.ctypes.data_as(_dp), sp.ctypes.data_as(_fp), di.ctypes.data_as(_fp),
                             mv.ctypes.data_as(_ip), zz.ctypes.data_as(_dp), *[a.ctypes.data_as(_fp) for a in ins],
                             *[a.ctypes.data_as(_dp) for a in dr], C.c_int(int(noise_is_final)), counts.ctypes.data_as(_lp))
     return dict(specie=sp, diameter=di, moving=mv, z=zz, counts=counts[:49].reshape(7, 7)[:m['nspecies'], :m['nspecies']].copy(), bad=int(counts[49]))
@@ -89,8 +70,8 @@ def probabilities(m, dt, specie, z, sal, depth, conc3):
     n = len(specie)
     p, ps = np.zeros((n, 7)), np.zeros(n)
     st, tb = _setup_vector(m, dt), _table(m)
-    a = [_f(specie, n), _d(z, n), _f(sal, n), _f(depth, n), _f(conc3, n)]
-    lib().radioh_probabilities(C.c_longlong(n), st.ctypes.data_as(_dp), tb.ctypes.data_as(_dp), a[0].ctypes.data_as(_fp),
+    a = [f32(specie, n), f64(z, n), f32(sal, n), f32(depth, n), f32(conc3, n)]
+    _lib().radioh_probabilities(C.c_longlong(n), st.ctypes.data_as(_dp), tb.ctypes.data_as(_dp), a[0].ctypes.data_as(_fp),
                                a[1].ctypes.data_as(_dp), a[2].ctypes.data_as(_fp), a[3].ctypes.data_as(_fp), a[4].ctypes.data_as(_fp),
                                p.ctypes.data_as(_dp), ps.ctypes.data_as(_dp))
     return p, ps
@@ -98,10 +79,10 @@ def probabilities(m, dt, specie, z, sal, depth, conc3):
 
 def terminal_velocity(temperature, salinity, diameter, density, moving):
     n = len(temperature)
-    a = [_f(x, n) for x in (temperature, salinity, diameter, density)]
+    a = [f32(x, n) for x in (temperature, salinity, diameter, density)]
     mv = np.ascontiguousarray(np.broadcast_to(np.asarray(moving, np.int32), (n,)))
     w = np.empty(n, np.float32)
-    lib().radioh_terminal_velocity(C.c_longlong(n), *[x.ctypes.data_as(_fp) for x in a], mv.ctypes.data_as(_ip), w.ctypes.data_as(_fp))
+    _lib().radioh_terminal_velocity(C.c_longlong(n), *[x.ctypes.data_as(_fp) for x in a], mv.ctypes.data_as(_ip), w.ctypes.data_as(_fp))
     return w
 
 
@@ -111,9 +92,9 @@ def resuspend(m, specie, diameter, moving, z, u, v, depth, diameter_noise, depth
     sp, di, mv, zz = np.array(specie, np.float32), np.array(diameter, np.float32), np.array(moving, np.int32), np.array(z, np.float64)
     counts = np.zeros(50, np.int64)
     st = _setup_vector(m, 0.0)
-    ins = [_f(u, n), _f(v, n), _f(depth, n)]
-    dr = [_d(a, n) for a in (diameter_noise, depth_noise)]
-    lib().radioh_resuspend(C.c_longlong(n), st.ctypes.data_as(_dp), sp.ctypes.data_as(_fp), di.ctypes.data_as(_fp), mv.ctypes.data_as(_ip),
+    ins = [f32(u, n), f32(v, n), f32(depth, n)]
+    dr = [f64(a, n) for a in (diameter_noise, depth_noise)]
+    _lib().radioh_resuspend(C.c_longlong(n), st.ctypes.data_as(_dp), sp.ctypes.data_as(_fp), di.ctypes.data_as(_fp), mv.ctypes.data_as(_ip),
                            zz.ctypes.data_as(_dp), *[a.ctypes.data_as(_fp) for a in ins], *[a.ctypes.data_as(_dp) for a in dr],
                            C.c_int(int(noise_is_final)), counts.ctypes.data_as(_lp))
     return dict(specie=sp, diameter=di, moving=mv, z=zz, counts=counts[:49].reshape(7, 7)[:m['nspecies'], :m['nspecies']].copy(), bad=int(counts[49]))

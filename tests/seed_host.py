@@ -2,17 +2,11 @@
 -ffp-contract=off, tests/hostshim in place of the HIP runtime header), see seed_host.cpp; the NumPy restatement of matplotlib's
 crossing rule; the point sets and rings the tests share; and HostContext, which stands in for the model's device context."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-OUT = os.path.join(ROOT, 'oracle', '_build', 'seed_host.so')
-CSRC = os.path.join(ROOT, 'opendrift_amd', 'csrc')
-SRC = [os.path.join(HERE, 'seed_host.cpp'), os.path.join(HERE, 'hostshim', 'hip', 'hip_runtime.h'), os.path.join(CSRC, 'odr_seed.hip.h'),
-       os.path.join(CSRC, 'odr_geodinv.hip.h'), os.path.join(CSRC, 'odr_geodesic.hip.h')]
+from host_build import host_lib
+
 _dp, _bp = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
 
 # Bounds: 4 x the host build's measured maximum over every case of tests/golden/c35_seed_geometry.npz (DESIGN.md section 8j).
@@ -21,25 +15,17 @@ _dp, _bp = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
 # evaluation rounded to float64.
 C35_LON_BOUND_DEG = 4 * 2.85e-14
 C35_LAT_BOUND_DEG = 4 * 7.64e-14
-_lib = None
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(OUT) or any(os.path.getmtime(OUT) < os.path.getmtime(s) for s in SRC):
-            os.makedirs(os.path.dirname(OUT), exist_ok=True)
-            subprocess.check_call(['g++', '-O1', '-std=c++17', '-ffp-contract=off', '-I', os.path.join(HERE, 'hostshim'),
-                                   '-shared', '-fPIC', '-o', OUT, SRC[0]])
-        _lib = C.CDLL(OUT)
-    return _lib
+def _lib():
+    return host_lib('seed_host', ('odr_seed.hip.h', 'odr_geodinv.hip.h', 'odr_geodesic.hip.h'))
 
 
 def points_in_polygon(x, y, vx, vy):
     """The signature of opendrift_amd.device.Context.points_in_polygon, computed by the host build of the header."""
     x, y, vx, vy = (np.ascontiguousarray(a, np.float64).ravel() for a in (x, y, vx, vy))
     inside = np.zeros(len(x), np.uint8)
-    lib().seedh_points_in_polygon(C.c_longlong(len(x)), x.ctypes.data_as(_dp), y.ctypes.data_as(_dp), C.c_int(len(vx)),
+    _lib().seedh_points_in_polygon(C.c_longlong(len(x)), x.ctypes.data_as(_dp), y.ctypes.data_as(_dp), C.c_int(len(vx)),
                                   vx.ctypes.data_as(_dp), vy.ctypes.data_as(_dp), inside.ctypes.data_as(_bp))
     return inside.astype(bool)
 
@@ -55,7 +41,7 @@ def points_within_polygon(lons, lats, number, info=False, mask=False):
     n_inside, nx, ny = C.c_longlong(), C.c_int(), C.c_int()
 
     def call(m):
-        rc = lib().seedh_polygon_points(C.c_int(len(lons)), lons.ctypes.data_as(_dp), lats.ctypes.data_as(_dp), C.c_longlong(number),
+        rc = _lib().seedh_polygon_points(C.c_int(len(lons)), lons.ctypes.data_as(_dp), lats.ctypes.data_as(_dp), C.c_longlong(number),
                                         lon.ctypes.data_as(_dp), lat.ctypes.data_as(_dp), C.byref(n_inside), C.byref(nx), C.byref(ny),
                                         None if m is None else m.ctypes.data_as(_bp))
         if rc:
@@ -72,7 +58,7 @@ def points_within_polygon(lons, lats, number, info=False, mask=False):
 def albers(lat1, lat2, lat0, lon0, a, b, forward=True):
     a, b = (np.ascontiguousarray(v, np.float64).ravel() for v in (a, b))
     u, v = np.empty(len(a)), np.empty(len(a))
-    rc = lib().seedh_albers(C.c_double(lat1), C.c_double(lat2), C.c_double(lat0), C.c_double(lon0), C.c_longlong(len(a)),
+    rc = _lib().seedh_albers(C.c_double(lat1), C.c_double(lat2), C.c_double(lat0), C.c_double(lon0), C.c_longlong(len(a)),
                             a.ctypes.data_as(_dp), b.ctypes.data_as(_dp), u.ctypes.data_as(_dp), v.ctypes.data_as(_dp), C.c_int(int(forward)))
     if rc:
         raise ValueError('no Albers cone')

@@ -2,18 +2,13 @@
 tests/hostshim in place of the HIP runtime header), see ship_host.cpp; and ShipDrift.update of the host build end to end, with the
 two moves made by the host build of the geodesic (tests/geod_host.cpp)."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
+from host_build import f32, host_lib
+
 import berg_host
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
-OUT = os.path.join(ROOT, 'oracle', '_build', 'ship_host.so')
-SRC = [os.path.join(HERE, 'ship_host.cpp'), os.path.join(HERE, 'hostshim', 'hip', 'hip_runtime.h'),
-       os.path.join(ROOT, 'opendrift_amd', 'csrc', 'odr_ship.hip.h')]
 TM02 = 'sea_surface_wave_mean_period_from_variance_spectral_density_second_frequency_moment'
 ENV = ('x_sea_water_velocity', 'y_sea_water_velocity', 'x_wind', 'y_wind', 'sea_surface_wave_stokes_drift_x_velocity',
        'sea_surface_wave_stokes_drift_y_velocity', 'sea_surface_wave_significant_height', TM02)      # the order of ShipEnv
@@ -21,29 +16,17 @@ PROPS = ('length', 'height', 'draft', 'beam', 'wind_drag_coeff', 'water_drag_coe
 F32 = ('bl', 'dl', 'Tm', 'Hs', 'F_wind_x', 'F_wind_y', 'beta1')                                      # ShipForces
 F64 = ('F_wave_b', 'beta2_b', 'F_wave', 'beta2', 'wave_dir', 'F_total', 'uw_tot', 'uw_dir', 'velocity_u', 'velocity_v')
 _fp, _dp, _ip = C.POINTER(C.c_float), C.POINTER(C.c_double), C.POINTER(C.c_int32)
-_lib = None
 
 
-def lib():
-    global _lib
-    if _lib is None:
-        if not os.path.exists(OUT) or any(os.path.getmtime(OUT) < os.path.getmtime(s) for s in SRC):
-            os.makedirs(os.path.dirname(OUT), exist_ok=True)
-            subprocess.check_call(['g++', '-O1', '-std=c++17', '-ffp-contract=off', '-I', os.path.join(HERE, 'hostshim'),
-                                   '-shared', '-fPIC', '-o', OUT, SRC[0]])
-        _lib = C.CDLL(OUT)
-    return _lib
-
-
-def _f32(a, n):
-    return np.array(np.broadcast_to(np.asarray(a, np.float32), (n,)), dtype=np.float32, order='C')
+def _lib():
+    return host_lib('ship_host', ('odr_ship.hip.h',))
 
 
 def ratios(length, draft, beam):
     n = len(length)
-    a = [_f32(v, n) for v in (length, draft, beam)]
+    a = [f32(v, n) for v in (length, draft, beam)]
     bl, dl = np.empty(n, np.float32), np.empty(n, np.float32)
-    lib().shiph_ratios(C.c_longlong(n), *(v.ctypes.data_as(_fp) for v in a + [bl, dl]))
+    _lib().shiph_ratios(C.c_longlong(n), *(v.ctypes.data_as(_fp) for v in a + [bl, dl]))
     return bl, dl
 
 
@@ -51,14 +34,14 @@ def forces(env, props, orientation, cls, table, hs_mode, tp_mode, wave_dir_from_
     """ship_forces of every element.  env / props: {name: float32 array} (ENV, PROPS); table [n_classes][49][2].  Returns
     {name: array} for F32 + F64."""
     n = len(cls)
-    e = [_f32(env[k], n) for k in ENV]
-    p = [_f32(props[k], n) for k in PROPS]
+    e = [f32(env[k], n) for k in ENV]
+    p = [f32(props[k], n) for k in PROPS]
     table = np.ascontiguousarray(table, np.float64)
-    assert table.shape[1:] == (lib().shiph_rows(), 2) and 0 <= np.min(cls) and np.max(cls) < len(table)
+    assert table.shape[1:] == (_lib().shiph_rows(), 2) and 0 <= np.min(cls) and np.max(cls) < len(table)
     ori, cls = (np.array(a, dtype=np.int32, order='C') for a in (orientation, cls))
     out = {k: np.zeros(n, np.float32) for k in F32}
     out.update({k: np.zeros(n, np.float64) for k in F64})
-    lib().shiph_forces(C.c_longlong(n), (_fp * 8)(*(a.ctypes.data_as(_fp) for a in e)), (_fp * 6)(*(a.ctypes.data_as(_fp) for a in p)),
+    _lib().shiph_forces(C.c_longlong(n), (_fp * 8)(*(a.ctypes.data_as(_fp) for a in e)), (_fp * 6)(*(a.ctypes.data_as(_fp) for a in p)),
                        ori.ctypes.data_as(_ip), cls.ctypes.data_as(_ip), table.ctypes.data_as(_dp), C.c_int(hs_mode), C.c_int(tp_mode),
                        C.c_int(int(wave_dir_from_stokes)), (_fp * 7)(*(out[k].ctypes.data_as(_fp) for k in F32)),
                        (_dp * 10)(*(out[k].ctypes.data_as(_dp) for k in F64)))

@@ -5,8 +5,7 @@ import os
 
 import pytest
 
-from test_layout_spec_resources import READELF
-from test_ship_kernel_resources import kernel_resources
+from code_objects import READELF, kernel_resources
 
 pytestmark = pytest.mark.skipif(not os.path.exists(READELF), reason='needs the ROCm LLVM tools')
 

@@ -11,28 +11,17 @@ libm / mpmath and the oracle's complete geodesic (oracle/geodesic.c, itself pinn
 No GPU: the arithmetic is the same source the kernels compile (the hardware's reciprocal seeds replaced by exact operations, FMA
 contraction off); tests/test_gpu_parity.py and tests/test_gpu_movers.py hold the device build to the same bounds."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+from host_build import geod_host
 from oracle import oracle as orc
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 
 @pytest.fixture(scope='module')
 def gh():
-    out = os.path.join(ROOT, 'oracle', '_build', 'geod_host.so')
-    src = os.path.join(HERE, 'geod_host.cpp')
-    deps = [src, os.path.join(HERE, 'hostshim', 'hip', 'hip_runtime.h'), os.path.join(ROOT, 'opendrift_amd', 'csrc', 'odr_geodesic.hip.h')]
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    if not os.path.exists(out) or any(os.path.getmtime(d) > os.path.getmtime(out) for d in deps):
-        subprocess.check_call(['g++', '-O1', '-std=c++17', '-ffp-contract=off', '-w', '-shared', '-fPIC', '-I' + os.path.join(HERE, 'hostshim'),
-                               '-o', out, src])
-    return C.CDLL(out)
+    return geod_host()
 
 
 def _p(a):

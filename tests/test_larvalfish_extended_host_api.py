@@ -174,7 +174,7 @@ def test_run_takes_the_call_by_call_lane():
     from opendrift_amd.oceandrift import OceanDrift
     from opendrift_amd.larvalfish_extended import LarvalFishExtended
     assert LarvalFishExtended.update is not OceanDrift.update
-    assert LarvalFishExtended.vertical_advection is not OceanDrift.vertical_advection      # (the mixing launch must not take it in)
+    assert not LarvalFishExtended._fuses_vertical_advection()      # (the mixing launch must not take it in)
     assert LarvalFishExtended.vertical_mixing is OceanDrift.vertical_mixing and LarvalFishExtended.stokes_drift is OceanDrift.stokes_drift
     assert LarvalFishExtended.advect_ocean_current is OceanDrift.advect_ocean_current
     assert getattr(LarvalFishExtended, 'leeway_lane_update', None) is None
@@ -209,4 +209,5 @@ def test_abi_entries_are_declared_and_bound():
     assert _abi.NVAR == 26
     for cite in ('larvalfish_extended.py:292-318', 'larvalfish_extended.py:206-290', 'physics_methods.py:977-979'):
         assert cite in src
-    assert 'odr_larvalx.hip' in open(os.path.join(ROOT, 'opendrift_amd', 'build.py')).read()
+    from opendrift_amd import build
+    assert 'odr_larvalx.hip' in build.UNITS

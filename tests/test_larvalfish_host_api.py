@@ -136,7 +136,7 @@ def test_run_takes_the_call_by_call_lane():
     from opendrift_amd.larvalfish import LarvalFish
     assert LarvalFish.update is not OceanDrift.update
     assert LarvalFish.update_terminal_velocity is not OceanDrift.update_terminal_velocity
-    assert LarvalFish.vertical_advection is not OceanDrift.vertical_advection      # (the mixing launch must not take it in)
+    assert not LarvalFish._fuses_vertical_advection()      # (the mixing launch must not take it in)
     assert LarvalFish.vertical_mixing is OceanDrift.vertical_mixing and LarvalFish.stokes_drift is OceanDrift.stokes_drift
     assert LarvalFish.advect_ocean_current is OceanDrift.advect_ocean_current
     assert getattr(LarvalFish, 'leeway_lane_update', None) is None

@@ -87,13 +87,13 @@ def test_tsprofiles_is_refused_by_name():
 
 def test_run_takes_the_call_by_call_lane():
     """run() chooses its lane by the methods a class overrides (oceandrift.py, run()): update() is the model's own, so neither
-    the fused OceanDrift launch nor the speculated mixing launch (which needs the fused lane) is taken; vertical_advection is
-    the model's own, so the mixing launch does not take the vertical advection in."""
+    the fused OceanDrift launch nor the speculated mixing launch (which needs the fused lane) is taken; the class
+    does not fuse (fuse_vertical_advection), so the mixing launch does not take the vertical advection in."""
     from opendrift_amd.oceandrift import OceanDrift
     from opendrift_amd.pelagicegg import PelagicEggDrift
     assert PelagicEggDrift.update is not OceanDrift.update
     assert PelagicEggDrift.update_terminal_velocity is not OceanDrift.update_terminal_velocity
-    assert PelagicEggDrift.vertical_advection is not OceanDrift.vertical_advection
+    assert not PelagicEggDrift._fuses_vertical_advection()
     assert PelagicEggDrift.vertical_mixing is OceanDrift.vertical_mixing and PelagicEggDrift.advect_ocean_current is OceanDrift.advect_ocean_current
     assert getattr(PelagicEggDrift, 'leeway_lane_update', None) is None
 

@@ -241,7 +241,7 @@ def test_run_takes_the_call_by_call_lane():
     from opendrift_amd import RadionuclideDrift
     from opendrift_amd.oceandrift import OceanDrift
     assert RadionuclideDrift.update is not OceanDrift.update
-    assert RadionuclideDrift.vertical_advection is not OceanDrift.vertical_advection
+    assert not RadionuclideDrift._fuses_vertical_advection()
     assert RadionuclideDrift._with_seafloor_action is not OceanDrift._with_seafloor_action
     assert RadionuclideDrift.vertical_mixing is OceanDrift.vertical_mixing
     assert RadionuclideDrift.interact_with_seafloor is OceanDrift.interact_with_seafloor

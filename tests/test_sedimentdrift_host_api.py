@@ -114,11 +114,11 @@ def test_the_settle_action_is_handed_to_the_device_for_lift_only():
 def test_run_takes_the_call_by_call_lane():
     """run() chooses its lane by the methods a class overrides (oceandrift.py, run()): update() is the model's own, so neither
     the fused OceanDrift launch nor the speculated mixing launch (which needs the fused lane and the stock sea-floor hook) is
-    taken; vertical_advection is the model's own, so the mixing launch does not take the vertical advection in."""
+    taken; the class does not fuse (fuse_vertical_advection), so the mixing launch does not take the vertical advection in."""
     from opendrift_amd.oceandrift import OceanDrift
     from opendrift_amd.sedimentdrift import SedimentDrift
     assert SedimentDrift.update is not OceanDrift.update
-    assert SedimentDrift.vertical_advection is not OceanDrift.vertical_advection
+    assert not SedimentDrift._fuses_vertical_advection()
     assert SedimentDrift._seafloor_action_in_update is not OceanDrift._seafloor_action_in_update
     assert SedimentDrift.vertical_mixing is OceanDrift.vertical_mixing and SedimentDrift.interact_with_seafloor is OceanDrift.interact_with_seafloor
     assert getattr(SedimentDrift, 'leeway_lane_update', None) is None

@@ -2,30 +2,12 @@
 section 7f has the register count of the build it was written with; the test prints the present one).  Reads the metadata of the
 library's gfx950 code object, so that an edit that makes the loop spill, or stages something in LDS, fails here."""
 import os
-import re
-import subprocess
-import tempfile
 
 import pytest
 
-from test_layout_spec_resources import READELF, _code_objects
+from code_objects import READELF, kernel_resources
 
 KERNEL = 'k_ship_driftILb0E'      # k_ship_drift<false>: the launch of a run (<true> also reports the intermediates, for the tests)
-
-
-def kernel_resources(lib, name):
-    found = []
-    with tempfile.TemporaryDirectory() as d:
-        for k, co in enumerate(_code_objects(lib)):
-            path = os.path.join(d, 'co%d.o' % k)
-            open(path, 'wb').write(co)
-            notes = subprocess.run([READELF, '--notes', path], capture_output=True, text=True).stdout
-            for block in re.split(r'\n\s+- \.', notes):
-                m = re.search(r'(?:^|\n)\s*\.?name:\s+(\S+)', block)
-                if m and name in m.group(1) and not m.group(1).endswith('.kd'):
-                    found.append({k: int(re.search(r'%s:\s+(\d+)' % k, block).group(1))
-                                  for k in ('private_segment_fixed_size', 'group_segment_fixed_size', 'vgpr_count', 'sgpr_count')})
-    return found
 
 
 @pytest.mark.skipif(not os.path.exists(READELF), reason='needs the ROCm LLVM tools')
