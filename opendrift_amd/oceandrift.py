@@ -998,9 +998,15 @@ class OpenDriftSimulation(Configurable):
 
     def _ensemble_current(self):
         """The current comes (also) from a reader that hands it out as a list of ensemble members."""
-        return any(
-            b.sid is not None and self.ctx._grids.get(b.sid, {}).get('members') and
-            ('x_sea_water_velocity' in b.variables or 'y_sea_water_velocity' in b.variables) for b in self.readers.values())
+        return any('x_sea_water_velocity' in b.variables or 'y_sea_water_velocity' in b.variables for b in self._ensemble_readers())
+
+    def _ensemble_readers(self):
+        """The bound readers that hand their data out as a list of ensemble members."""
+        return [b for b in self.readers.values() if b.sid is not None and self.ctx._grids.get(b.sid, {}).get('members')]
+
+    def _grid_sid(self):
+        """Source id of the first bound grid reader, or None."""
+        return next((b.sid for b in self.readers.values() if b.is_grid() and b.sid is not None), None)
 
     def _sample_host_readers(self, names, P=None, time=None):
         """Readers evaluated on the host (user-defined ContinuousReaders): where such a reader comes BEFORE the device
@@ -1259,18 +1265,102 @@ class OpenDriftSimulation(Configurable):
 
     @classmethod
     def _stock_update(cls):
-        """run()'s `stock_update`: update() cannot register a status category on its own."""
+        """run()'s `stock_update`: the step's collective may be finished BEHIND update() only when update() cannot register a status
+        category on its own (a subclass's vertical_mixing / update_terminal_velocity calling deactivate_elements would append it
+        before the other ranks' categories on a deferring rank and after them on a blocking one: ADVICE round 5): the stock
+        methods only."""
         return cls._stock_methods(('update', 'vertical_mixing', 'update_terminal_velocity', '_advect_wind_then_stokes_drift',
                                    'advect_wind', 'stokes_drift', '_with_seafloor_action', '_seafloor_action_in_update',
                                    'vertical_buoyancy'))
 
-    def run(self, time_step=None, steps=None, time_step_output=None, duration=None, end_time=None,
-            outfile=None, export_variables=None, export_buffer_length=100, stop_on_error=False):
-        self._require('Ready')
-        if self._sched is None:
-            raise ValueError('Please seed elements before starting a run.')
-        if outfile is not None:
-            raise NotImplementedError('netCDF export is host-side I/O outside the hot path')
+    def _speculates(self, lane):
+        """The mixing launch of the step enqueued before the host has read the status scan (vertical_mixing(_guarded=True)): when the
+        stock update() makes nothing but that launch between the scan and the end of the step -- no mover that could move an
+        element first (the wind is calm everywhere and there is no Stokes drift: decided on the host), stock methods, reader
+        diffusivity, device RNG.  Between output times only: the result buffer records z as it is BEFORE update()."""
+        sx, sy = 'sea_surface_wave_stokes_drift_x_velocity', 'sea_surface_wave_stokes_drift_y_velocity'
+        return bool(
+            lane == 'fused' and not os.environ.get('ODR_NO_SPECULATION') and self.rng == 'device' and self._stock_speculation_methods() and
+            self.get_config('drift:vertical_mixing') is True and
+            self.get_config('vertical_mixing:diffusivitymodel') == 'environment' and
+            ('x_wind' not in self.required_variables or self._calm_everywhere()) and
+            (sx not in self.required_variables or self.get_config('drift:stokes_drift') is False or
+             (self._identically_zero(sx) and self._identically_zero(sy))))
+
+    def _one_launch_lanes_open(self):
+        """What the two one-launch lanes of run() ask alike: the stock loop body, and nothing in it that a launch cannot honour."""
+        return (not os.environ.get('ODR_RUN_UNFUSED') and
+                all(getattr(type(self), m) is getattr(OpenDriftSimulation, m) for m in (
+                    'get_environment', 'interact_with_coastline', 'interact_with_seafloor', 'deactivate_outside',
+                    'deactivate_elements')) and
+                self.get_config('drift:max_age_seconds') is None and
+                not self.get_config('general:coastline_approximation_precision') and
+                not self._host_bindings() and
+                # report_missing_variables comes BEFORE deactivate_outside in the loop (:2251-2253) but sits inside the
+                # launch: an element both outside the domain and without data must end as 'missing_data'
+                not (any(self.get_config('drift:deactivate_%s_of' % k) is not None for k in ('west', 'east', 'south', 'north'))
+                     and self._can_be_missing(list(self.required_variables))))
+
+    def _run_lane(self):
+        """The lane run() takes, 'fused' | 'leeway' | 'call_by_call': decided by what the class overrides, the configuration and
+        the bound readers -- a configured model answers without a device."""
+        cls = type(self)
+        if not self._one_launch_lanes_open():
+            return 'call_by_call'
+        # fused lane: the stock loop body and the stock OceanDrift.update order (current advection first), no
+        # retirement between coastline and advection.  Uncertainties: with the device RNG (streams keyed by element
+        # ID) they are added inside the launch; np.random draws are sized by the elements present at each call, which
+        # the fused launch cannot honour -> call-by-call lane
+        if (getattr(cls, 'update', None) is OceanDrift.update and
+                cls.advect_ocean_current is OpenDriftSimulation.advect_ocean_current and
+                (self.rng == 'device' or not (any(self._current_uncertainty()) or self.get_config('drift:wind_uncertainty'))) and
+                not self._config.get('drift:water_column_stretching', {}).get('value') and
+                self._config.get('drift:truncate_ocean_model_below_m', {}).get('value') is None and
+                self.get_config('general:seafloor_action', 'lift_to_seafloor') in ('lift_to_seafloor', 'none') and
+                'x_sea_water_velocity' in self.required_variables and 'y_sea_water_velocity' in self.required_variables and
+                not (self._ensemble_current() and self.get_config('drift:advection_scheme') != 'euler')):
+            return 'fused'
+        # Leeway lane: the loop body between two compactions + Leeway.update (leeway, current, jibes) in ONE launch
+        # (odr_env_coast_leeway; what bench.py's C5 line times).  Stock methods, device RNG (the jibe draws are keyed by
+        # element ID), no capsizing (its draws are sized by the elements that can capsize: call-by-call lane), nothing
+        # the launch cannot honour -- as for the OceanDrift lane above.
+        lw_update = getattr(cls, 'leeway_lane_update', None)
+        if (lw_update is not None and getattr(cls, 'update', None) is lw_update and
+                cls.stokes_drift is OpenDriftSimulation.stokes_drift and
+                self.rng == 'device' and not self.get_config('processes:capsizing') and
+                not self.get_config('drift:current_uncertainty_uniform') and
+                all(v in self.required_variables for v in ('x_wind', 'y_wind', 'x_sea_water_velocity', 'y_sea_water_velocity')) and
+                'sea_floor_depth_below_sea_level' not in self.required_variables):
+            return 'leeway'
+        return 'call_by_call'
+
+    def _sort_interval(self, lane):
+        """Re-sort interval in steps: what bench.py's bare sequences were tuned to (a re-sort costs ~1.7 step-kernel launches at
+        10 M elements; the layout decays with the distance travelled: 3-D current + mixing 24 steps, Leeway 48, the rest 16)."""
+        if self.sort_every is not None:
+            return self.sort_every
+        return 48 if lane == 'leeway' else (24 if lane == 'fused' and 'upward_sea_water_velocity' in self.required_variables else 16)
+
+    def _unread_variables(self, lane, recorded):
+        """Variables nothing reads between this step's sample and the next one are not sampled in the fused lane (the sample
+        of `ocean_vertical_diffusivity` AT the element is only ever exported: the mixing scheme works on the profiles,
+        oceandrift.py:428-449).  They are sampled when the result buffer holds them (`recorded`) and in the last step of the run,
+        so that `o.environment` and `o.result` come out as the reference's."""
+        stock_readers_of_it = isinstance(self, OceanDrift) and all(
+            getattr(type(self), m) is getattr(OceanDrift, m) for m in ('vertical_mixing', 'update_terminal_velocity', 'update'))
+        if lane != 'fused' or not stock_readers_of_it or self._ensemble_readers():
+            return []      # (ensemble data: the member numbering goes with the main-loop call as the reference makes it)
+        return [v for v in getattr(self, '_export_only_variables', ()) if v in self.required_variables and
+                v not in recorded and not self._can_be_missing([v])]
+
+    @staticmethod
+    def _age_in_launch(recorded):
+        """increase_age_and_retire comes after state_to_buffer in the loop: inside the fused launch only when the result
+        buffer does not hold age_seconds (it would see the age one step ahead)."""
+        return 'age_seconds' not in recorded
+
+    def _time_arguments(self, time_step, steps, time_step_output, duration, end_time):
+        """run()'s time arguments (basemodel/__init__.py:1939-2010) -> (steps, calculation steps per output step)."""
         if sum(x is not None for x in (steps, duration, end_time)) > 1:
             raise ValueError('Only one of "steps", "duration" and "end_time" may be provided simultaneously')
         if time_step is None:
@@ -1286,7 +1376,7 @@ class OpenDriftSimulation(Configurable):
                 time_step_output = timedelta(seconds=time_step_output)
             if time_step_output.days >= 0 and time_step.days < 0:
                 time_step_output = -time_step_output
-        self.time_step_output = time_step_output      # (basemodel/__init__.py:1939-1958)
+        self.time_step_output = time_step_output
         ratio = time_step_output.total_seconds() / time_step.total_seconds()
         if ratio < 1:
             raise ValueError('Output time step must be equal or larger than calculation time step.')
@@ -1315,17 +1405,11 @@ class OpenDriftSimulation(Configurable):
             duration = np.ceil(ratio_duration_output) * time_step_output
         steps = int(round(duration.total_seconds() / time_step.total_seconds()))
         self.expected_steps_calculation = steps
-        out_every = max(1, int(round(ratio)))
-        # skip_if conditionals of required_variables (:1899-1906)
-        for vn, var in list(self.required_variables.items()):
-            if 'skip_if' in var:
-                key, op, val = var['skip_if']
-                cur = self.get_config(key)
-                if {'is': cur is val, '==': cur == val, '!=': cur != val}[op]:
-                    self.required_variables.pop(vn)
-        self.time = self.start_time
+        return steps, max(1, int(round(ratio)))
+
+    def _set_extents(self, steps):
         # the lon / lat box the elements can reach (:2017-2035): readers are prepared for it
-        max_distance = self.get_config('drift:max_speed') * steps * abs(time_step.total_seconds())
+        max_distance = self.get_config('drift:max_speed') * steps * abs(self.time_step.total_seconds())
         dlat = max_distance / 111000.
         dlon = dlat / np.cos(np.radians(np.mean(self._sched['lat'])))
         ext = np.array([max(-360, self._sched['lon'].min() - dlon), max(-89, self._sched['lat'].min() - dlat),
@@ -1335,33 +1419,30 @@ class OpenDriftSimulation(Configurable):
         self.simulation_extent = ext
         # the window the reader blocks are cut to (DeviceReaderBinding.set_extent): what can be covered between two looks
         # at the elements' box on top of it (_check_reader_windows)
-        mlat = self.get_config('drift:max_speed') * self.WINDOW_CHECK_EVERY * abs(time_step.total_seconds()) / 111000.
+        mlat = self.get_config('drift:max_speed') * self.WINDOW_CHECK_EVERY * abs(self.time_step.total_seconds()) / 111000.
         mlon = mlat / np.cos(np.radians(np.mean(self._sched['lat'])))
         self._block_extent = np.array([max(-360, ext[0] - mlon), max(-89, ext[1] - mlat), min(360, ext[2] + mlon), min(89, ext[3] + mlat)])
-        self._all_at_start = bool((self._sched['t_epoch'] == _epoch(self.start_time)).all())
-        self._finalize_environment(self.start_time, self.start_time + time_step)
-        # Move point seeded on land to ocean (:2150-2158)
-        if self.get_config('seed:ocean_only') is True and 'land_binary_mask' in self.required_variables:
-            self._sched['lon'], self._sched['lat'], _ = self.closest_ocean_points(self._sched['lon'], self._sched['lat'])
+
+    def _shard_schedule(self, steps):
+        """-> this rank's contiguous range (lo_id, hi_id) of element IDs; the others are never released here."""
         n_total = self.num_elements_total()
         lo_id, hi_id = 0, n_total
         self._n_global = n_total
         self._g_release = self._g_release_cum = None
         self._g_active_carry = self._below_active = 0
         self._timing_collectives, self._timing_collective_s, self._step_red = 0, 0.0, None
-        if self._world > 1:     # this rank's contiguous range of element IDs; the others are never released here
+        if self._world > 1:
             from . import distributed as D
             lo_id, hi_id = D.shard_range(n_total, self._rank, self._world)
             # the release schedule of ALL elements as a histogram over the steps (what _global_counts needs), then the
             # schedule itself cut down to this rank's range: the per-step host work is O(N / ranks) from here on
-            te, dts = self._sched['t_epoch'], time_step.total_seconds()
-            t_start = _epoch(self.start_time)
+            te, dts = self._sched['t_epoch'], self.time_step.total_seconds()
             if self._all_at_start:
                 k = np.zeros(n_total, np.int64)
             else:
                 # the step an element is released in, by the comparisons release_elements() makes on the same epoch values:
                 # forward t0 <= t < t1, backward t0 >= t > t1, with t0 / t1 the epochs of start + i time_step
-                edges = np.array([_epoch(self.start_time + i * time_step) for i in range(steps + 1)])
+                edges = np.array([_epoch(self.start_time + i * self.time_step) for i in range(steps + 1)])
                 sgn = 1.0 if dts > 0 else -1.0
                 k = np.searchsorted(sgn * edges, sgn * te, side='right').astype(np.int64) - 1
             ok = (k >= 0) & (k < steps)
@@ -1374,6 +1455,46 @@ class OpenDriftSimulation(Configurable):
                     delattr(self, attr)
             self._all_at_start = False if n_total == 0 else self._all_at_start
         self._shard = (lo_id, hi_id)
+        return lo_id, hi_id
+
+    def _run_timing(self, t_start, t_steady, t_end, phases):
+        """o.timing: `t_steady` is the clock after the first step (None: the run had one step), `phases` the phase clock's table."""
+        ahead = {'hits': 0, 'misses': 0, 'worker_s': 0.0}
+        for b in self.readers.values():
+            for k, closed in zip(ahead, getattr(b, '_ahead_stats', (0, 0, 0.0))):
+                ahead[k] += closed + getattr(getattr(b, '_ahead', None), k, 0)
+        per_step = max(1, self.steps_calculation - 1)
+        return {'main_loop_s': t_end - t_start, 'steps': self.steps_calculation,
+                'collectives': self._timing_collectives, 'collective_s': self._timing_collective_s,
+                'reader_level_stall_s': sum(getattr(b, 'stall_s', 0.0) for b in self.readers.values()),
+                # rank 0 of a sharded run: levels its worker thread had read ahead / read inline, and the time the worker spent reading
+                'reader_thread': ahead,
+                'steady_ms_per_step': (1e3 * (t_end - t_steady) / per_step) if t_steady else None,
+                'host_phases_ms_per_step': {k: (round(1e3 * v[0] / per_step, 4), round(1e3 * v[1], 3)) for k, v in phases.items()}}
+
+    def run(self, time_step=None, steps=None, time_step_output=None, duration=None, end_time=None,
+            outfile=None, export_variables=None, export_buffer_length=100, stop_on_error=False):
+        self._require('Ready')
+        if self._sched is None:
+            raise ValueError('Please seed elements before starting a run.')
+        if outfile is not None:
+            raise NotImplementedError('netCDF export is host-side I/O outside the hot path')
+        steps, out_every = self._time_arguments(time_step, steps, time_step_output, duration, end_time)
+        # skip_if conditionals of required_variables (:1899-1906)
+        for vn, var in list(self.required_variables.items()):
+            if 'skip_if' in var:
+                key, op, val = var['skip_if']
+                cur = self.get_config(key)
+                if {'is': cur is val, '==': cur == val, '!=': cur != val}[op]:
+                    self.required_variables.pop(vn)
+        self.time = self.start_time
+        self._set_extents(steps)
+        self._all_at_start = bool((self._sched['t_epoch'] == _epoch(self.start_time)).all())
+        self._finalize_environment(self.start_time, self.start_time + self.time_step)
+        # Move point seeded on land to ocean (:2150-2158)
+        if self.get_config('seed:ocean_only') is True and 'land_binary_mask' in self.required_variables:
+            self._sched['lon'], self._sched['lat'], _ = self.closest_ocean_points(self._sched['lon'], self._sched['lat'])
+        lo_id, hi_id = self._shard_schedule(steps)
         self._resolve_seafloor_seeds(0, hi_id - lo_id)
         self.P = self.ctx.particles(max(1, hi_id - lo_id))
         self.mode = 'Run'
@@ -1386,101 +1507,21 @@ class OpenDriftSimulation(Configurable):
         self._hist = _ResultBuffer(self.ctx, max(1, hi_id - lo_id), nout, min(nout, max(1, int(export_buffer_length))), hvars,
                                    id_base=lo_id)
         times = []
-        grid_sid = next((b.sid for b in self.readers.values() if b.is_grid() and b.sid is not None), None)
-        # fused lane: the stock loop body and the stock OceanDrift.update order (current advection first), no
-        # retirement between coastline and advection.  Uncertainties: with the device RNG (streams keyed by element
-        # ID) they are added inside the launch; np.random draws are sized by the elements present at each call, which
-        # the fused launch cannot honour -> call-by-call lane
-        B = OpenDriftSimulation
-        fused_lane = (not os.environ.get('ODR_RUN_UNFUSED') and getattr(type(self), 'update', None) is OceanDrift.update and
-                      all(getattr(type(self), m) is getattr(B, m) for m in (
-                          'advect_ocean_current', 'get_environment', 'interact_with_coastline', 'interact_with_seafloor',
-                          'deactivate_outside', 'deactivate_elements')) and
-                      (self.rng == 'device' or not (any(self._current_uncertainty()) or self.get_config('drift:wind_uncertainty'))) and
-                      self.get_config('drift:max_age_seconds') is None and
-                      not self._config.get('drift:water_column_stretching', {}).get('value') and
-                      self._config.get('drift:truncate_ocean_model_below_m', {}).get('value') is None and
-                      self.get_config('general:seafloor_action', 'lift_to_seafloor') in ('lift_to_seafloor', 'none') and
-                      not self.get_config('general:coastline_approximation_precision') and
-                      'x_sea_water_velocity' in self.required_variables and 'y_sea_water_velocity' in self.required_variables and
-                      not self._host_bindings() and
-                      not (self._ensemble_current() and self.get_config('drift:advection_scheme') != 'euler') and
-                      # report_missing_variables comes BEFORE deactivate_outside in the loop (:2251-2253) but sits inside the
-                      # launch: an element both outside the domain and without data must end as 'missing_data'
-                      not (any(self.get_config('drift:deactivate_%s_of' % k) is not None for k in ('west', 'east', 'south', 'north'))
-                           and self._can_be_missing(list(self.required_variables))))
+        lane = self._run_lane()
         # the movers' global tests (calm, no Stokes drift, zero diffusivity, nothing at the surface) come out of the fused launch
         # instead of out of a pass over the arrays before the first mover (odr_ctx_set_step_reduce; a sharded run combines
         # its reductions over the ranks in the step's collective instead)
-        self.ctx.set_step_reduce(fused_lane and self._world == 1, self.get_config('drift:wind_drift_depth', 0.1) or 0.0,
+        self.ctx.set_step_reduce(lane == 'fused' and self._world == 1, self.get_config('drift:wind_drift_depth', 0.1) or 0.0,
                                  bool(self.get_config('drift:relative_wind')))
-        # Leeway lane: the loop body between two compactions + Leeway.update (leeway, current, jibes) in ONE launch
-        # (odr_env_coast_leeway; what bench.py's C5 line times).  Stock methods, device RNG (the jibe draws are keyed by
-        # element ID), no capsizing (its draws are sized by the elements that can capsize: call-by-call lane), nothing
-        # the launch cannot honour -- as for the OceanDrift lane above.
-        lw_update = getattr(type(self), 'leeway_lane_update', None)
-        leeway_lane = (not os.environ.get('ODR_RUN_UNFUSED') and lw_update is not None and getattr(type(self), 'update', None) is lw_update and
-                       all(getattr(type(self), m) is getattr(B, m) for m in (
-                           'get_environment', 'interact_with_coastline', 'interact_with_seafloor', 'deactivate_outside',
-                           'deactivate_elements', 'stokes_drift')) and
-                       self.rng == 'device' and not self.get_config('processes:capsizing') and
-                       not self.get_config('drift:current_uncertainty_uniform') and
-                       self.get_config('drift:max_age_seconds') is None and
-                       not self.get_config('general:coastline_approximation_precision') and
-                       all(v in self.required_variables for v in ('x_wind', 'y_wind', 'x_sea_water_velocity', 'y_sea_water_velocity')) and
-                       'sea_floor_depth_below_sea_level' not in self.required_variables and
-                       not self._host_bindings() and
-                       not (any(self.get_config('drift:deactivate_%s_of' % k) is not None for k in ('west', 'east', 'south', 'north'))
-                            and self._can_be_missing(list(self.required_variables))))
-        # re-sort interval: what bench.py's bare sequences were tuned to (a re-sort costs ~1.7 step-kernel launches at 10 M
-        # elements; the layout decays with the distance travelled: 3-D current + mixing 24 steps, Leeway 48, the rest 16)
-        sort_every = self.sort_every
-        if sort_every is None:
-            sort_every = 48 if leeway_lane else (24 if fused_lane and 'upward_sea_water_velocity' in self.required_variables else 16)
-        # Variables nothing reads between this step's sample and the next one are not sampled in the fused lane (the sample
-        # of `ocean_vertical_diffusivity` AT the element is only ever exported: the mixing scheme works on the profiles,
-        # oceandrift.py:428-449).  They are sampled when the result buffer holds them and in the last step of the run, so
-        # that `o.environment` and `o.result` come out as the reference's.
-        stock_readers_of_it = isinstance(self, OceanDrift) and all(
-            getattr(type(self), m) is getattr(OceanDrift, m) for m in ('vertical_mixing', 'update_terminal_velocity', 'update'))
-        unread = [v for v in getattr(self, '_export_only_variables', ()) if v in self.required_variables and
-                  v not in self._hist.variables and not self._can_be_missing([v])] if fused_lane and stock_readers_of_it else []
-        if any(b.sid is not None and self.ctx._grids.get(b.sid, {}).get('members') for b in self.readers.values()):
-            unread = []      # (ensemble data: the member numbering goes with the main-loop call as the reference makes it)
-        # The mixing launch of the step enqueued before the host has read the status scan (vertical_mixing(_guarded=True)): when the
-        # stock update() makes nothing but that launch between the scan and the end of the step -- no mover that could move an
-        # element first (the wind is calm everywhere and there is no Stokes drift: decided on the host), stock methods, reader
-        # diffusivity, device RNG.  Between output times only: the result buffer records z as it is BEFORE update().
-        sx, sy = 'sea_surface_wave_stokes_drift_x_velocity', 'sea_surface_wave_stokes_drift_y_velocity'
-        speculate = bool(
-            fused_lane and not os.environ.get('ODR_NO_SPECULATION') and self.rng == 'device' and self._stock_speculation_methods() and
-            self.get_config('drift:vertical_mixing') is True and
-            self.get_config('vertical_mixing:diffusivitymodel') == 'environment' and
-            ('x_wind' not in self.required_variables or self._calm_everywhere()) and
-            (sx not in self.required_variables or self.get_config('drift:stokes_drift') is False or
-             (self._identically_zero(sx) and self._identically_zero(sy))))
-        # the step's collective may be finished BEHIND update() only when update() cannot register a status category on its own
-        # (a subclass's vertical_mixing / update_terminal_velocity calling deactivate_elements would append it before the other
-        # ranks' categories on a deferring rank and after them on a blocking one: ADVICE round 5): the stock methods only
-        stock_update = self._stock_update()
+        sort_every = self._sort_interval(lane)
+        clock = _PhaseClock()
+        # what the step of a lane is handed besides its number: what was decided once for all steps
+        plan = SimpleNamespace(steps=steps, out_every=out_every, times=times, clock=clock,
+                               unread=self._unread_variables(lane, self._hist.variables), speculate=self._speculates(lane),
+                               stock_update=self._stock_update(), age_in_launch=self._age_in_launch(self._hist.variables))
         self._vmix_speculated = False
         self.ctx.sync()
-        t_loop = [time.perf_counter(), None]      # main-loop wall time (the reference keeps 'main loop' timers, basemodel :2174)
-        # increase_age_and_retire comes after state_to_buffer in the loop: inside the fused launch only when the result
-        # buffer does not hold age_seconds (it would see the age one step ahead)
-        age_in_launch = 'age_seconds' not in self._hist.variables
-        # host time of the loop body by phase, steps 1.. (the reference keeps `timers` of its main loop, basemodel :2174):
-        # [seconds, longest single step] -- 'status read' is where the host waits for the device
-        phases = {}
-        pc = time.perf_counter
-
-        def lap(name, t_from):
-            t = pc()
-            if i > 0:
-                e = phases.setdefault(name, [0.0, 0.0])
-                e[0] += t - t_from
-                e[1] = max(e[1], t - t_from)
-            return t
+        t_start, t_steady = time.perf_counter(), None   # main-loop wall time (the reference keeps 'main loop' timers, basemodel :2174)
         # Until the first update_positions of a run the reference's elements.lon / lat are float32 ARRAYS (elements.py:71-88):
         # its first get_environment modulates the longitudes in float32 (variables.py:259-280, :914).  The main-loop sample of
         # the steps up to the first one that moves elements does the same (odr_ctx_set_position_class); the Runge-Kutta stage
@@ -1492,170 +1533,40 @@ class OpenDriftSimulation(Configurable):
                     self.ctx.set_position_class(True)
                 if i == 1:
                     self.ctx.sync()
-                    t_loop[1] = time.perf_counter()   # after the first step: seeding, first uploads and sort are behind
-                t_ph = pc()
+                    t_steady = time.perf_counter()   # after the first step: seeding, first uploads and sort are behind
+                clock.start(record=i > 0)
                 self.release_elements()
                 g_active, g_sched = self._global_counts(i)
-                t_ph = lap('release', t_ph)
+                clock.lap('release')
                 if g_active == 0 and g_sched > 0:
                     self._state_to_buffer(i, out_every, times)   # (:2208)
                     self.steps_calculation += 1
                     self.time = self.time + self.time_step
                     continue
                 self._ensure_reader_levels(self.time, self.time + self.time_step)
-                t_ph = lap('reader levels', t_ph)
+                clock.lap('reader levels')
                 # device layout maintenance: re-sort by grid cell every sort_every steps and whenever a
                 # release added a sizeable share of new (unsorted) elements
                 n_act = self.num_elements_active()
-                if grid_sid is None:       # (gone after a failed re-cut of a reader's window: it may be back)
-                    grid_sid = next((b.sid for b in self.readers.values() if b.is_grid() and b.sid is not None), None)
-                if self.rng == 'device' and grid_sid is not None and sort_every and n_act > 65536 and \
-                        (i % sort_every == 0 or self.newly_seeded * 20 > n_act):
+                if self.rng == 'device' and sort_every and n_act > 65536 and (i % sort_every == 0 or self.newly_seeded * 20 > n_act):
                     # (the source id of a reader changes when its window is re-cut, and is gone when the re-cut failed)
-                    grid_sid = next((b.sid for b in self.readers.values() if b.is_grid() and b.sid is not None), None)
+                    grid_sid = self._grid_sid()
                     if grid_sid is not None:
                         self.P.sort_by_cell(grid_sid, keep_environment=False)   # the step's sample follows
-                t_ph = lap('layout', t_ph)
-                one_collective, deferred = False, None
+                clock.lap('layout')
                 # ensemble data in a sharded run: the stage calls of advect_ocean_current take the member by the rank among
                 # the elements that are STILL active after this step's coastline / seafloor deactivations on ALL ranks --
                 # known only from the step's collective, which the call-by-call lane makes between the two
-                ens_sharded = self._world > 1 and any(
-                    b.sid is not None and self.ctx._grids.get(b.sid, {}).get('members') for b in self.readers.values())
-                if fused_lane and not ens_sharded:
-                    # ONE launch for get_environment + coastline + seafloor + update_previous_state +
-                    # advect_ocean_current (odr_env_coast_advect).  deactivate_outside only reads positions and goes
-                    # first; the result buffer is written afterwards from the saved pre-advection position.
-                    self.deactivate_outside()
-                    names = [v for v in self.required_variables if i == steps - 1 or v not in unread]
-                    action = self.get_config('general:coastline_action')
-                    floor = ('sea_floor_depth_below_sea_level' in self.priority_list and
-                             self.get_config('general:seafloor_action', 'lift_to_seafloor') == 'lift_to_seafloor')
-                    std, ustd = self._current_uncertainty()
-                    noisy = std > 0 or ustd > 0
-                    if noisy:
-                        self.P.set_advect_noise(std, ustd, step=self.steps_calculation)
-                    self.P.env_coast_advect(
-                        names, _epoch(self.time), self.get_config('drift:advection_scheme'), self.time_step.total_seconds(),
-                        coastline=action if 'land_binary_mask' in names else 'none',
-                        stranded_code=self._status_code('stranded') if action == 'stranding' else 1,
-                        seeded_on_land_code=(self._status_code('seeded_on_land') if action == 'previous' and self._newly_any
-                                             else 0),
-                        store_previous=True, count=False, seafloor=floor,
-                        missing_code=self._status_code('missing_data') if self._can_be_missing(names) else 0,
-                        main_noise=noisy, age_dt=self.time_step.total_seconds() if age_in_launch else 0.0)
-                    self._sampled = names
-                    self._add_uncertainty(names, current=False)     # the wind's share
-                    t_ph = lap('step launch', t_ph)
-                    # ONE host read per step: how many elements stay + which new deactivation reasons occurred
-                    self._vmix_speculated = False
-                    want_red = self._needs_reductions()
-                    early = None
-                    if speculate and i % out_every != 0 and self.P.scan_status_begin():
-                        if self._world > 1 and stock_update and not want_red and not os.environ.get('ODR_SYNC_COLLECTIVE'):
-                            from . import distributed as D
-                            if D.backend() == 'rccl':     # the step's ONE collective leaves behind the fold, ahead of the host's read
-                                early = self._step_summary(None, None, False, start_only=True, from_scan=True)
-                        launched = self.vertical_mixing(_guarded=True)      # (does nothing unless every element stays)
-                        kept, flags = self.P.scan_status_end()
-                        self._vmix_speculated = bool(launched) and kept == len(self.P)
-                    else:
-                        kept, flags = self.P.scan_status()
-                    t_ph = lap('status read', t_ph)
-                    all_stay = kept == len(self.P)      # nothing to backfill, nothing to compact on this rank
-                    if early is not None and flags == 0:
-                        deferred = (early, self._pending_status, kept)
-                        self._pending_status = []
-                    elif early is not None:      # a reason of this rank waits for its category: the collective is finished now
-                        kept, flags = self._step_summary(None, None, False, handle=early)
-                        self._resolve_status(flags)
-                    elif self._world > 1 and stock_update and not want_red and flags == 0 and not os.environ.get('ODR_SYNC_COLLECTIVE'):
-                        # sharded: nothing this rank does before the end of update() depends on the other ranks (no mover
-                        # consults all-rank maxima, no element here carries a reason that waits for its category) -- the
-                        # step's ONE collective is started here and finished behind the launches of update()
-                        deferred = (self._step_summary(kept, flags, False, start_only=True), self._pending_status, kept)
-                        self._pending_status = []       # (as _resolve_status leaves it: update() registers its own reasons anew)
-                    else:
-                        kept, flags = self._step_summary(kept, flags, want_red)   # the step's ONE collective
-                        self._resolve_status(flags)
-                    self._state_to_buffer(i, out_every, times, from_previous=True, all_stay=all_stay)
-                    if not age_in_launch:
-                        self.P.increase_age(self.time_step.total_seconds())
-                    self.P.compact_apply()
-                    self._advected = True
-                elif leeway_lane and not ens_sharded:
-                    self.deactivate_outside()
-                    names = list(self.required_variables)
-                    action = self.get_config('general:coastline_action')
-                    # the launch jibes before the step's record is taken; the loop records first (basemodel/__init__.py:2276,
-                    # :2293): at output steps the record reads the two properties a jibe changes from a copy taken here
-                    jibed = [k for k, nm in enumerate(getattr(self, 'aux_properties', []))
-                             if nm in ('crosswind_slope', 'orientation') and nm in self._hist.variables]
-                    snap = bool(jibed) and i % out_every == 0
-                    if snap:
-                        for k in jibed:
-                            self.P.snapshot_property(k)
-                    _, split = self.P.env_coast_leeway(
-                        names, _epoch(self.time), self.time_step.total_seconds(), self.get_config('capsizing:leeway_fraction'),
-                        coastline=action if 'land_binary_mask' in names else 'none',
-                        stranded_code=self._status_code('stranded') if action == 'stranding' else 1,
-                        seeded_on_land_code=(self._status_code('seeded_on_land') if action == 'previous' and self._newly_any
-                                             else 0),
-                        store_previous=True, current_uncertainty=self.get_config('drift:current_uncertainty') or 0.0,
-                        wind_uncertainty=self.get_config('drift:wind_uncertainty') or 0.0, step=self.steps_calculation,
-                        split='return', count=False,
-                        missing_code=self._status_code('missing_data') if self._can_be_missing(names) else 0)
-                    self._sampled = names
-                    t_ph = lap('step launch', t_ph)
-                    kept, flags = self.P.scan_status()
-                    t_ph = lap('status read', t_ph)
-                    all_stay = kept == len(self.P)
-                    kept, flags = self._step_summary(kept, flags, self._needs_reductions())   # the step's ONE collective
-                    self._resolve_status(flags)
-                    self._state_to_buffer(i, out_every, times, from_previous=3 if snap else 1, all_stay=all_stay)
-                    self.P.increase_age(self.time_step.total_seconds())
-                    self.P.compact_apply()
-                    # wind, current and land mask from more than one reader: the library sampled, perturbed and applied the
-                    # coastline; Leeway.update makes its own call on the compacted set
-                    self._leeway_in_launch = not split
+                ens_sharded = self._world > 1 and bool(self._ensemble_readers())
+                if lane == 'call_by_call' or ens_sharded:
+                    deferred, one_collective = self._step_call_by_call(i, plan, ens_sharded)
+                elif lane == 'fused':
+                    deferred, one_collective = self._step_fused(i, plan)
                 else:
-                    self.get_environment()
-                    self.report_missing_variables()
-                    self.deactivate_outside()
-                    self.interact_with_coastline()
-                    self.interact_with_seafloor()
-                    max_age = self.get_config('drift:max_age_seconds')
-                    one_collective = self._world > 1 and not max_age
-                    if one_collective:      # sharded: the step's ONE collective, as in the fused lane
-                        kept, flags = self.P.scan_status()
-                        kept, flags = self._step_summary(kept, flags, self._needs_reductions())
-                        self.P.set_rank_offset(self._below_active)     # (ensemble members of the stage calls, see above)
-                        self._resolve_status(flags)
-                    else:
-                        self._resolve_status()
-                    self._state_to_buffer(i, out_every, times)
-                    self.P.increase_age(self.time_step.total_seconds(), max_age or 0.0,
-                                        self._status_code('retired') if max_age else 0)
-                    if one_collective:
-                        self.P.compact_apply()
-                    else:
-                        self._resolve_status()
-                        self.P.compact()
-                        if ens_sharded:
-                            # (drift:max_age_seconds: the retirements come after the point the step's one collective is made
-                            # at) the stage calls of update() number the elements present NOW on all ranks: the elements the
-                            # lower ranks kept, from a collective of its own
-                            from . import distributed as D
-                            rows = D.allgather_vector([float(len(self.P))])
-                            self._timing_collectives += 1
-                            self._below_active = int(round(rows[:self._rank, 0].sum()))
-                            self.P.set_rank_offset(self._below_active)
-                    self.P.store_previous()
-                    if hasattr(self, '_store_environment_previous'):
-                        self._store_environment_previous()
+                    deferred, one_collective = self._step_leeway(i, plan)
                 if deferred is not None:
                     g_active = max(1, deferred[2])      # (decided for good when the collective is finished, below)
-                elif self._world > 1 and (((fused_lane or leeway_lane) and not ens_sharded) or one_collective):
+                elif self._world > 1 and one_collective:
                     g_active = self._g_active           # from this step's collective
                 elif self._world > 1:
                     newly = self._newly_any
@@ -1663,7 +1574,7 @@ class OpenDriftSimulation(Configurable):
                     self._newly_any = newly
                 else:
                     g_active = self._g_active = self.num_elements_active()
-                t_ph = lap('bookkeeping', t_ph)
+                clock.lap('bookkeeping')
                 if f32_first:
                     self.ctx.set_position_class(False)
                     f32_first = not g_active > 0
@@ -1671,21 +1582,20 @@ class OpenDriftSimulation(Configurable):
                     if g_active > 0:
                         self.update()
                         self._flush_elements()      # what a model's update() wrote into self.elements goes to the device
-                    elif g_sched == 0:
-                        raise ValueError('No more active or scheduled elements, quitting.')
                 finally:
                     if deferred is not None:    # an open collective is finished whatever update() did: the ranks stay in step
                         g_kept, g_flags = self._step_summary(None, None, False, handle=deferred[0])
                 if deferred is not None:
                     self._resolve_status(g_flags, pending=deferred[1])
-                    if g_kept == 0 and g_sched == 0:
-                        raise ValueError('No more active or scheduled elements, quitting.')
+                    g_active = g_kept
+                if g_active == 0 and g_sched == 0:
+                    raise ValueError('No more active or scheduled elements, quitting.')
                 self._advected = False
                 self.horizontal_diffusion()
                 self._step_release()
                 self.time = self.time + self.time_step
                 self.steps_calculation += 1
-                t_ph = lap('update', t_ph)
+                clock.lap('update')
             except Exception as e:
                 self.ctx.set_position_class(False)
                 if stop_on_error or self.steps_calculation <= 1:
@@ -1694,18 +1604,7 @@ class OpenDriftSimulation(Configurable):
                 break
         self.ctx.set_position_class(False)
         self.ctx.sync()
-        t_end = time.perf_counter()
-        self.timing = {'main_loop_s': t_end - t_loop[0], 'steps': self.steps_calculation,
-                       'collectives': self._timing_collectives, 'collective_s': self._timing_collective_s,
-                       'reader_level_stall_s': sum(getattr(b, 'stall_s', 0.0) for b in self.readers.values()),
-                       # rank 0 of a sharded run: levels its worker thread had read ahead / read inline, and the time the worker spent reading
-                       'reader_thread': dict(zip(('hits', 'misses', 'worker_s'), map(sum, zip(*([(0, 0, 0.0)] + [
-                           tuple(x + getattr(getattr(b, '_ahead', None), k, 0) for x, k in zip(getattr(b, '_ahead_stats', (0, 0, 0.0)),
-                                                                                              ('hits', 'misses', 'worker_s')))
-                           for b in self.readers.values()]))))),
-                       'steady_ms_per_step': (1e3 * (t_end - t_loop[1]) / max(1, self.steps_calculation - 1)) if t_loop[1] else None,
-                       'host_phases_ms_per_step': {k: (round(1e3 * v[0] / max(1, self.steps_calculation - 1), 4), round(1e3 * v[1], 3))
-                                                   for k, v in phases.items()}}
+        self.timing = self._run_timing(t_start, t_steady, time.perf_counter(), clock.phases)
         for b in self.readers.values():      # no read of the user's Reader is in flight when run() returns
             if hasattr(b, 'close_read_ahead'):
                 b.close_read_ahead()
@@ -1716,6 +1615,140 @@ class OpenDriftSimulation(Configurable):
         self.result = dict(time=times, **self._hist.finish(len(times)))
         self.result_minmax = self._hist.minmax
         return self.result
+
+    # ---- a step of run() in each lane -> (the open collective to finish behind update() or None, the step's ONE collective was made)
+    def _one_launch_codes(self, names):
+        """What the two one-launch calls are told alike: the coastline action and the status numbers they may assign."""
+        action = self.get_config('general:coastline_action')
+        return dict(coastline=action if 'land_binary_mask' in names else 'none',
+                    stranded_code=self._status_code('stranded') if action == 'stranding' else 1,
+                    seeded_on_land_code=self._status_code('seeded_on_land') if action == 'previous' and self._newly_any else 0,
+                    missing_code=self._status_code('missing_data') if self._can_be_missing(names) else 0)
+
+    def _step_fused(self, i, plan):
+        # ONE launch for get_environment + coastline + seafloor + update_previous_state +
+        # advect_ocean_current (odr_env_coast_advect).  deactivate_outside only reads positions and goes
+        # first; the result buffer is written afterwards from the saved pre-advection position.
+        self.deactivate_outside()
+        names = [v for v in self.required_variables if i == plan.steps - 1 or v not in plan.unread]
+        floor = ('sea_floor_depth_below_sea_level' in self.priority_list and
+                 self.get_config('general:seafloor_action', 'lift_to_seafloor') == 'lift_to_seafloor')
+        std, ustd = self._current_uncertainty()
+        noisy = std > 0 or ustd > 0
+        if noisy:
+            self.P.set_advect_noise(std, ustd, step=self.steps_calculation)
+        self.P.env_coast_advect(
+            names, _epoch(self.time), self.get_config('drift:advection_scheme'), self.time_step.total_seconds(),
+            store_previous=True, count=False, seafloor=floor, main_noise=noisy,
+            age_dt=self.time_step.total_seconds() if plan.age_in_launch else 0.0, **self._one_launch_codes(names))
+        self._sampled = names
+        self._add_uncertainty(names, current=False)     # the wind's share
+        plan.clock.lap('step launch')
+        # ONE host read per step: how many elements stay + which new deactivation reasons occurred
+        self._vmix_speculated = False
+        want_red = self._needs_reductions()
+        early = deferred = None
+        if plan.speculate and i % plan.out_every != 0 and self.P.scan_status_begin():
+            if self._world > 1 and plan.stock_update and not want_red and not os.environ.get('ODR_SYNC_COLLECTIVE'):
+                from . import distributed as D
+                if D.backend() == 'rccl':     # the step's ONE collective leaves behind the fold, ahead of the host's read
+                    early = self._step_summary(None, None, False, start_only=True, from_scan=True)
+            launched = self.vertical_mixing(_guarded=True)      # (does nothing unless every element stays)
+            kept, flags = self.P.scan_status_end()
+            self._vmix_speculated = bool(launched) and kept == len(self.P)
+        else:
+            kept, flags = self.P.scan_status()
+        plan.clock.lap('status read')
+        all_stay = kept == len(self.P)      # nothing to backfill, nothing to compact on this rank
+        if early is not None and flags == 0:
+            deferred = (early, self._pending_status, kept)
+            self._pending_status = []
+        elif early is not None:      # a reason of this rank waits for its category: the collective is finished now
+            kept, flags = self._step_summary(None, None, False, handle=early)
+            self._resolve_status(flags)
+        elif self._world > 1 and plan.stock_update and not want_red and flags == 0 and not os.environ.get('ODR_SYNC_COLLECTIVE'):
+            # sharded: nothing this rank does before the end of update() depends on the other ranks (no mover
+            # consults all-rank maxima, no element here carries a reason that waits for its category) -- the
+            # step's ONE collective is started here and finished behind the launches of update()
+            deferred = (self._step_summary(kept, flags, False, start_only=True), self._pending_status, kept)
+            self._pending_status = []       # (as _resolve_status leaves it: update() registers its own reasons anew)
+        else:
+            kept, flags = self._step_summary(kept, flags, want_red)   # the step's ONE collective
+            self._resolve_status(flags)
+        self._state_to_buffer(i, plan.out_every, plan.times, from_previous=True, all_stay=all_stay)
+        if not plan.age_in_launch:
+            self.P.increase_age(self.time_step.total_seconds())
+        self.P.compact_apply()
+        self._advected = True
+        return deferred, True
+
+    def _step_leeway(self, i, plan):
+        self.deactivate_outside()
+        names = list(self.required_variables)
+        # the launch jibes before the step's record is taken; the loop records first (basemodel/__init__.py:2276,
+        # :2293): at output steps the record reads the two properties a jibe changes from a copy taken here
+        jibed = [k for k, nm in enumerate(getattr(self, 'aux_properties', []))
+                 if nm in ('crosswind_slope', 'orientation') and nm in self._hist.variables]
+        snap = bool(jibed) and i % plan.out_every == 0
+        if snap:
+            for k in jibed:
+                self.P.snapshot_property(k)
+        _, split = self.P.env_coast_leeway(
+            names, _epoch(self.time), self.time_step.total_seconds(), self.get_config('capsizing:leeway_fraction'),
+            store_previous=True, current_uncertainty=self.get_config('drift:current_uncertainty') or 0.0,
+            wind_uncertainty=self.get_config('drift:wind_uncertainty') or 0.0, step=self.steps_calculation,
+            split='return', count=False, **self._one_launch_codes(names))
+        self._sampled = names
+        plan.clock.lap('step launch')
+        kept, flags = self.P.scan_status()
+        plan.clock.lap('status read')
+        all_stay = kept == len(self.P)
+        kept, flags = self._step_summary(kept, flags, self._needs_reductions())   # the step's ONE collective
+        self._resolve_status(flags)
+        self._state_to_buffer(i, plan.out_every, plan.times, from_previous=3 if snap else 1, all_stay=all_stay)
+        self.P.increase_age(self.time_step.total_seconds())
+        self.P.compact_apply()
+        # wind, current and land mask from more than one reader: the library sampled, perturbed and applied the
+        # coastline; Leeway.update makes its own call on the compacted set
+        self._leeway_in_launch = not split
+        return None, True
+
+    def _step_call_by_call(self, i, plan, ens_sharded):
+        self.get_environment()
+        self.report_missing_variables()
+        self.deactivate_outside()
+        self.interact_with_coastline()
+        self.interact_with_seafloor()
+        max_age = self.get_config('drift:max_age_seconds')
+        one_collective = self._world > 1 and not max_age
+        if one_collective:      # sharded: the step's ONE collective, as in the fused lane
+            kept, flags = self.P.scan_status()
+            kept, flags = self._step_summary(kept, flags, self._needs_reductions())
+            self.P.set_rank_offset(self._below_active)     # (ensemble members of the stage calls, see run())
+            self._resolve_status(flags)
+        else:
+            self._resolve_status()
+        self._state_to_buffer(i, plan.out_every, plan.times)
+        self.P.increase_age(self.time_step.total_seconds(), max_age or 0.0,
+                            self._status_code('retired') if max_age else 0)
+        if one_collective:
+            self.P.compact_apply()
+        else:
+            self._resolve_status()
+            self.P.compact()
+            if ens_sharded:
+                # (drift:max_age_seconds: the retirements come after the point the step's one collective is made
+                # at) the stage calls of update() number the elements present NOW on all ranks: the elements the
+                # lower ranks kept, from a collective of its own
+                from . import distributed as D
+                rows = D.allgather_vector([float(len(self.P))])
+                self._timing_collectives += 1
+                self._below_active = int(round(rows[:self._rank, 0].sum()))
+                self.P.set_rank_offset(self._below_active)
+        self.P.store_previous()
+        if hasattr(self, '_store_environment_previous'):
+            self._store_environment_previous()
+        return None, one_collective
 
     def get_density_array(self, pixelsize_m, weight=None, bins=None):
         """basemodel/__init__.py:4091-4146: (H, H_submerged, H_stranded, lon_array, lat_array), the number of elements -- or, with
@@ -1996,6 +2029,26 @@ class ElementsView:
                 P.set_property(slot, np.ascontiguousarray(cur[name][inv]))
         for k in changed:
             orig[k] = cur[k].copy()
+
+
+class _PhaseClock:
+    """Host time of run()'s loop body by phase (the reference keeps `timers` of its main loop, basemodel :2174): phases[name] =
+    [seconds, longest single step] -- 'status read' is where the host waits for the device.  The first step of a run
+    (seeding, first uploads, sort) is clocked and not recorded."""
+
+    def __init__(self):
+        self.phases, self.record, self.t = {}, False, 0.0
+
+    def start(self, record):
+        self.record, self.t = record, time.perf_counter()
+
+    def lap(self, name):
+        t = time.perf_counter()
+        if self.record:
+            e = self.phases.setdefault(name, [0.0, 0.0])
+            e[0] += t - self.t
+            e[1] = max(e[1], t - self.t)
+        self.t = t
 
 
 class _ResultBuffer:

@@ -218,6 +218,30 @@ def test_mixing_launch_enqueued_ahead_of_the_status_read_changes_nothing(monkeyp
             assert held < 6 and np.isnan(ra['lon'][:, -1]).sum() > 20     # steps that lose elements fail their guard and mix after the compaction
 
 
+def test_timing_of_a_fused_run_with_the_re_sort_armed():
+    """o.timing after a fused-lane run above the 65 536 elements that arm the re-sort: its keys and the seven phases of the loop body."""
+    g = golden('c3_grid3d_rk4_vmix.npz')
+    names = ['x_sea_water_velocity', 'y_sea_water_velocity', 'upward_sea_water_velocity',
+             'ocean_vertical_diffusivity', 'sea_floor_depth_below_sea_level', 'land_binary_mask']
+    o = OceanDrift(loglevel=50, seed=11)
+    o.add_reader(_grid_reader(g, names, z=g['g_z']))
+    o.set_config('drift:advection_scheme', 'runge-kutta4')
+    o.set_config('drift:vertical_mixing', True)
+    o.set_config('general:coastline_action', 'previous')
+    n = 70000
+    rng = np.random.default_rng(3)
+    o.seed_elements(lon=rng.uniform(1, 8, n), lat=rng.uniform(60.5, 65.5, n), z=-rng.uniform(0, 40, n), time=T0)
+    assert o._run_lane() == 'fused'
+    o.run(time_step=600, steps=9, time_step_output=1800)
+    assert set(o.timing) == {'main_loop_s', 'steps', 'collectives', 'collective_s', 'reader_level_stall_s', 'reader_thread',
+                             'steady_ms_per_step', 'host_phases_ms_per_step'}
+    assert set(o.timing['host_phases_ms_per_step']) == {'release', 'reader levels', 'layout', 'step launch', 'status read',
+                                                        'bookkeeping', 'update'}
+    assert all(len(v) == 2 and v[1] >= 0 for v in o.timing['host_phases_ms_per_step'].values())
+    assert set(o.timing['reader_thread']) == {'hits', 'misses', 'worker_s'} and o.timing['steady_ms_per_step'] > 0
+    assert o._sampled and o.steps_calculation == 9 and o.timing['steps'] == 9
+
+
 def test_openoil_advection_equals_reference_path():
     """OpenOil.update with weathering off = advect_oil (openoil.py:1179-1239): on the C4-shaped case the
     reference's OceanDrift-equivalent golden vectors apply."""

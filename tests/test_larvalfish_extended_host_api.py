@@ -178,6 +178,7 @@ def test_run_takes_the_call_by_call_lane():
     assert LarvalFishExtended.vertical_mixing is OceanDrift.vertical_mixing and LarvalFishExtended.stokes_drift is OceanDrift.stokes_drift
     assert LarvalFishExtended.advect_ocean_current is OceanDrift.advect_ocean_current
     assert getattr(LarvalFishExtended, 'leeway_lane_update', None) is None
+    assert LarvalFishExtended(loglevel=50)._run_lane() == 'call_by_call'
 
 
 def test_solar_elevation_is_a_method_of_the_base_model_and_its_time_scalars():

@@ -140,6 +140,7 @@ def test_run_takes_the_call_by_call_lane():
     assert LarvalFish.vertical_mixing is OceanDrift.vertical_mixing and LarvalFish.stokes_drift is OceanDrift.stokes_drift
     assert LarvalFish.advect_ocean_current is OceanDrift.advect_ocean_current
     assert getattr(LarvalFish, 'leeway_lane_update', None) is None
+    assert LarvalFish(loglevel=50)._run_lane() == 'call_by_call'
 
 
 def test_abi_entries_are_declared_and_bound():

@@ -96,6 +96,7 @@ def test_run_takes_the_call_by_call_lane():
     assert not PelagicEggDrift._fuses_vertical_advection()
     assert PelagicEggDrift.vertical_mixing is OceanDrift.vertical_mixing and PelagicEggDrift.advect_ocean_current is OceanDrift.advect_ocean_current
     assert getattr(PelagicEggDrift, 'leeway_lane_update', None) is None
+    assert PelagicEggDrift(loglevel=50)._run_lane() == 'call_by_call'
 
 
 def test_abi_entry_is_declared_and_bound():

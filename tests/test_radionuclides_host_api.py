@@ -245,6 +245,7 @@ def test_run_takes_the_call_by_call_lane():
     assert RadionuclideDrift._with_seafloor_action is not OceanDrift._with_seafloor_action
     assert RadionuclideDrift.vertical_mixing is OceanDrift.vertical_mixing
     assert RadionuclideDrift.interact_with_seafloor is OceanDrift.interact_with_seafloor
+    assert RadionuclideDrift(loglevel=50)._run_lane() == 'call_by_call'
 
 
 def test_abi_entries_are_declared_and_bound():

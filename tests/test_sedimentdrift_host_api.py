@@ -122,6 +122,7 @@ def test_run_takes_the_call_by_call_lane():
     assert SedimentDrift._seafloor_action_in_update is not OceanDrift._seafloor_action_in_update
     assert SedimentDrift.vertical_mixing is OceanDrift.vertical_mixing and SedimentDrift.interact_with_seafloor is OceanDrift.interact_with_seafloor
     assert getattr(SedimentDrift, 'leeway_lane_update', None) is None
+    assert SedimentDrift(loglevel=50)._run_lane() == 'call_by_call'
 
 
 def test_abi_entries_are_declared_and_bound():
