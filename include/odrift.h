@@ -947,6 +947,46 @@ int odr_polygon_points(odr_ctx *ctx, int32_t m, const double *lons, const double
 /* device time [ms] of the kernel launches of this process's last odr_polygon_points (tools/bench_seed.py); 0 when it launched none */
 int odr_polygon_points_last_kernel_ms(odr_ctx *ctx, float *ms);
 
+/* ---------------------------------------------------------------- unstructured (triangular-mesh) readers
+ * The reference's UnstructuredReader (readers/basereader/unstructured.py, readers/reader_netCDF_CF_unstructured.py): the value
+ * at the nearest node (node variables) or nearest face centre (face variables), at the nearest sigma layer or level of that
+ * column, at the nearest time level -- no interpolation anywhere (csrc/odr_umesh.hip.h).
+ * odr_umesh_create: x, y [n_nodes] and xc, yc [n_faces] (n_faces may be 0) host float64 in the mesh's own coordinates (proj; NULL:
+ * geographic).  One exact search index each is built on the host, once.  siglay [n_siglay][n_nodes], siglev [n_siglay + 1][n_nodes],
+ * h [n_nodes], siglay_center / siglev_center / h_center the same over the faces: host float32, each may be NULL (n_siglay 0: all).
+ * Coverage is the bounding box of the nodes.  ODR_ERR_INVALID: no node, a position that is not finite, sigma arrays without
+ * their depth array or without n_siglay, ODR_PROJ_OB_TRAN / ODR_PROJ_CURVILINEAR.  odr_umesh_destroy waits for the context's stream. */
+typedef struct odr_umesh odr_umesh;
+int odr_umesh_create(odr_ctx *ctx, const odr_proj_desc *proj, int32_t n_nodes, const double *x, const double *y, int32_t n_faces,
+                     const double *xc, const double *yc, int32_t n_siglay, const float *siglay, const float *siglev,
+                     const float *siglay_center, const float *siglev_center, const float *h, const float *h_center, odr_umesh **out);
+int odr_umesh_destroy(odr_ctx *ctx, odr_umesh *mesh);
+/* Variable var_id (ODR_VAR_*) of the time level t_epoch becomes resident in `slot` (0 .. 2): data is host float32, [points] with
+ * n_levels 0 or [n_levels][points], points = n_faces (on_faces != 0) or n_nodes.  n_levels == n_siglay: the variable sits on the
+ * layers, n_siglay + 1: on the levels -- decided by the count, as the reference decides by the array's shape.  Synchronous.
+ * ODR_ERR_INVALID: a slot outside 0 .. 2, another level count, a level count without the matching sigma and depth arrays of the
+ * mesh, a face variable on a mesh without faces. */
+int odr_umesh_set_level(odr_ctx *ctx, odr_umesh *mesh, int32_t slot, double t_epoch, int32_t var_id, int on_faces, int32_t n_levels,
+                        const float *data);
+/* For every element of the particle set, in ONE launch: lonlat2xy; the coverage test; the nearest node and / or face (one search
+ * each, however many variables share it); per variable the sigma index argmin(|sigma * h - z|) (float32 product, float64
+ * difference, first minimum) and the float32 value of the level in `slot`; x / y vector pairs (both components in var_ids)
+ * rotated from the mesh's CRS to east / north unless it is geographic; then the merge into the element's environment slot: a
+ * finite value is taken when first_flags[k] != 0 or the slot holds nothing finite.  Elements outside the box keep what they
+ * have; a variable that was never sampled starts as NaN.  nvars: 1 .. 8.  Enqueued on the context's stream.
+ * ODR_ERR_INVALID: a slot outside 0 .. 2, nvars outside 1 .. 8, a variable id given twice; ODR_ERR_STATE: the level in `slot`
+ * does not hold one of the variables. */
+int odr_umesh_sample(odr_ctx *ctx, odr_particles *p, odr_umesh *mesh, int32_t slot, int32_t nvars, const int32_t *var_ids,
+                     const int32_t *first_flags);
+/* The bare query (tests, tools/bench_umesh.py): idx_out[i] = index of the node (on_faces 0) or face centre nearest to (x[i], y[i]),
+ * mesh coordinates, host float64; squared distances are dx * dx + dy * dy in float64 without contraction; exact.  -1 for a point
+ * that is not finite.  A point far outside the box of the mesh is answered exactly too, but visits a large share of the tree
+ * (every point is about as far away); odr_umesh_sample never searches for one.  Synchronous. */
+int odr_umesh_nearest(odr_ctx *ctx, odr_umesh *mesh, int on_faces, int64_t n, const double *x, const double *y, int32_t *idx_out);
+/* device time [ms] of the launches of this process's last odr_umesh_nearest, or of the launch of its last odr_umesh_sample if
+ * that came later (waits for it) */
+int odr_umesh_last_kernel_ms(odr_ctx *ctx, float *ms);
+
 /* ---------------------------------------------------------------- ROMS sigma grid
  * The sigma -> z regridding reader_ROMS_native.get_variables applies to every 4-D variable of a block
  * (reader_ROMS_native.py:512-538,617-684) with roppy (readers/roppy/depth.py): sdepth (:31-113, rho points,

@@ -236,7 +236,14 @@ _SIGNATURES = {
     'odr_points_in_polygon': [_vp, C.c_int64, _dp, _dp, C.c_int32, _dp, _dp, _P(C.c_uint8)],
     'odr_polygon_points': [_vp, C.c_int32, _dp, _dp, C.c_int64, _dp, _dp, _P(C.c_int64), _P(C.c_int32), _P(C.c_int32)],
     'odr_polygon_points_last_kernel_ms': [_vp, _fp],
+    'odr_umesh_create': [_vp, _P(ProjDesc), C.c_int32, _dp, _dp, C.c_int32, _dp, _dp, C.c_int32] + [_fp] * 6 + [_P(_vp)],
+    'odr_umesh_destroy': [_vp, _vp],
+    'odr_umesh_set_level': [_vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_int, C.c_int32, _fp],
+    'odr_umesh_sample': [_vp, _vp, _vp, C.c_int32, C.c_int32, _ip, _ip],
+    'odr_umesh_nearest': [_vp, _vp, C.c_int, C.c_int64, _dp, _dp, _ip],
+    'odr_umesh_last_kernel_ms': [_vp, _fp],
 }
+UMESH_MAX_VARIABLES, UMESH_LEVELS = 8, 3      # odr_umesh_sample, odr_umesh_set_level
 EXPORTS = sorted(list(_SIGNATURES) + ['odr_last_error', 'odr_version'])
 
 _lib = None

@@ -568,6 +568,15 @@ class Context:
         check(self.lib.odr_polygon_points_last_kernel_ms(self.h, C.byref(ms)))
         return ms.value
 
+    def umesh(self, x, y, xc=None, yc=None, proj=None, **sigma):
+        """The device image of a triangular mesh (odr_umesh_create): UMesh."""
+        return UMesh(self, x, y, xc, yc, proj=proj, **sigma)
+
+    def umesh_last_kernel_ms(self):
+        ms = C.c_float()
+        check(self.lib.odr_umesh_last_kernel_ms(self.h, C.byref(ms)))
+        return ms.value
+
     def particles(self, capacity):
         return Particles(self, capacity)
 
@@ -687,6 +696,15 @@ class Particles:
     def env_upload(self, variable, values):
         a, p = _f(values, len(self))
         check(self.lib.odr_env_upload(self.ctx.h, self.h, self.ctx._vid(variable), p))
+
+    def umesh_sample(self, mesh, slot, variables, first):
+        """The variables of the mesh's resident level `slot` at every element, merged into the environment slots in one launch
+        (odr_umesh_sample): a finite value is taken where first[k] or where the slot holds nothing finite."""
+        ids, pi = _i([self.ctx._vid(v) for v in variables])
+        if len(first) != len(ids):
+            raise ValueError('%d variables and %d first flags' % (len(ids), len(first)))
+        fl, pf = _i([int(bool(f)) for f in first])
+        check(self.lib.odr_umesh_sample(self.ctx.h, self.h, mesh.ptr, int(slot), len(ids), pi, pf))
 
     def env_add_noise(self, var_x, var_y, std, step=0, normals=None, uniform=False):
         """drift:current_uncertainty / wind_uncertainty (normal) or drift:current_uncertainty_uniform (uniform=True) on
@@ -1347,7 +1365,7 @@ def _touching(fn):
     return wrapper
 
 
-for _name in ('append', 'upload', 'env_sample', 'env_upload', 'env_add_noise', 'advect', 'env_coast_advect',
+for _name in ('append', 'upload', 'env_sample', 'umesh_sample', 'env_upload', 'env_add_noise', 'advect', 'env_coast_advect',
               'update_positions', 'advect_wind', 'stokes_drift', 'advect_sea_ice', 'set_property', 'leeway_capsize', 'leeway', 'hdiffusion', 'movers',
               'vmix', 'vmix_analytic', 'vmix_oil', 'vertical_advection', 'vertical_buoyancy', 'coastline', 'coastline_crossing',
               'increase_age', 'deactivate_missing', 'remap_status', 'seafloor', 'deactivate', 'deactivate_outside', 'compact',
@@ -1394,6 +1412,68 @@ class ShipTable:
     def close(self):
         if self.ptr and self.ctx.h:
             self.ctx.lib.odr_ship_table_destroy(self.ctx.h, self.ptr)
+        self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class UMesh:
+    """Device image of a triangular mesh (odr_umesh_create / _destroy): the search indices over the nodes and the face centres,
+    the box of the nodes, the sigma and depth arrays, and up to three resident time levels."""
+    SIGMA = ('siglay', 'siglev', 'siglay_center', 'siglev_center', 'h', 'h_center')
+
+    def __init__(self, ctx, x, y, xc=None, yc=None, proj=None, **sigma):
+        unknown = set(sigma) - set(self.SIGMA)
+        if unknown:
+            raise TypeError('unknown mesh arrays %s' % sorted(unknown))
+        (x, px), (y, py) = _d(np.ravel(x)), _d(np.ravel(y))
+        (xc, pxc), (yc, pyc) = _d(np.ravel([] if xc is None else xc)), _d(np.ravel([] if yc is None else yc))
+        if len(x) != len(y) or len(xc) != len(yc):
+            raise ValueError('%d x and %d y node coordinates, %d xc and %d yc face centres' % (len(x), len(y), len(xc), len(yc)))
+        self.n_nodes, self.n_faces = len(x), len(xc)
+        a = {k: (None if sigma.get(k) is None else np.ascontiguousarray(sigma[k], dtype=np.float32)) for k in self.SIGMA}
+        lays = [a[k].shape[0] for k in ('siglay', 'siglay_center') if a[k] is not None and a[k].ndim == 2]
+        levs = [a[k].shape[0] - 1 for k in ('siglev', 'siglev_center') if a[k] is not None and a[k].ndim == 2]
+        if len(set(lays + levs)) > 1:
+            raise ValueError('the sigma arrays disagree on the number of layers: %s layers, %s levels' % (lays, [k + 1 for k in levs]))
+        self.n_siglay = (lays + levs + [0])[0]
+        for k in self.SIGMA:      # the library reads whole arrays: their lengths are checked here
+            npts = self.n_faces if k.endswith('center') else self.n_nodes
+            rows = () if k.startswith('h') else ((self.n_siglay + (1 if 'siglev' in k else 0)),)
+            if a[k] is not None and a[k].shape != rows + (npts,):
+                raise ValueError('%s of shape %s, expected %s' % (k, a[k].shape, rows + (npts,)))
+        pd = proj_desc(proj)
+        self.ctx, self.ptr = ctx, C.c_void_p()
+        check(ctx.lib.odr_umesh_create(ctx.h, None if pd is None else C.byref(pd), self.n_nodes, px, py, self.n_faces,
+                                       pxc if self.n_faces else None, pyc if self.n_faces else None, self.n_siglay,
+                                       *[None if a[k] is None else a[k].ctypes.data_as(_fp) for k in self.SIGMA], C.byref(self.ptr)))
+
+    def set_level(self, slot, t_epoch, variable, data, on_faces):
+        """One variable of one time level becomes resident in `slot`: data [points] or [levels, points] float32."""
+        data = np.ascontiguousarray(data, dtype=np.float32)
+        npts = self.n_faces if on_faces else self.n_nodes
+        if data.ndim not in (1, 2) or data.shape[-1] != npts:
+            raise ValueError('%s of shape %s on a mesh of %d %s' % (variable, data.shape, npts, 'faces' if on_faces else 'nodes'))
+        check(self.ctx.lib.odr_umesh_set_level(self.ctx.h, self.ptr, int(slot), float(t_epoch), self.ctx._vid(variable), int(bool(on_faces)),
+                                               data.shape[0] if data.ndim == 2 else 0, data.ctypes.data_as(_fp)))
+
+    def nearest(self, x, y, on_faces=False):
+        """Index of the node (or face centre) nearest to each (x, y) in mesh coordinates (odr_umesh_nearest): int32, -1 for a
+        point that is not finite."""
+        (x, px), (y, py) = _d(np.ravel(x)), _d(np.ravel(y))
+        if len(x) != len(y):
+            raise ValueError('%d x and %d y' % (len(x), len(y)))
+        out = np.empty(len(x), np.int32)
+        check(self.ctx.lib.odr_umesh_nearest(self.ctx.h, self.ptr, int(bool(on_faces)), len(x), px, py, out.ctypes.data_as(_ip)))
+        return out
+
+    def close(self):
+        if self.ptr and self.ctx.h:
+            self.ctx.lib.odr_umesh_destroy(self.ctx.h, self.ptr)
         self.ptr = C.c_void_p()
 
     def __del__(self):

@@ -28,7 +28,7 @@ import numpy as np
 from . import _abi, projection
 from .config import Configurable, CONFIG_LEVEL_BASIC, CONFIG_LEVEL_ADVANCED, CONFIG_LEVEL_ESSENTIAL
 from .device import Context
-from .readers import BaseReader, ConstantReader, DeviceReaderBinding, ReaderLevelsError, _epoch
+from .readers import BaseReader, ConstantReader, ContinuousReader, DeviceReaderBinding, ReaderLevelsError, _epoch
 
 logger = logging.getLogger('opendrift_amd')
 
@@ -994,7 +994,15 @@ class OpenDriftSimulation(Configurable):
         return clipped()
 
     def _host_bindings(self):
-        return [(n, b) for n, b in self.readers.items() if getattr(b, 'host_eval', False)]
+        """The bindings outside the device's own priority lists: readers evaluated on the host (user-defined ContinuousReaders)
+        and unstructured meshes, which the device samples in a launch of their own (odr_umesh_sample)."""
+        return [(n, b) for n, b in self.readers.items() if getattr(b, 'host_eval', False) or getattr(b, 'mesh', None) is not None]
+
+    def _unbound_off_list_readers(self):
+        """Readers added but not bound yet (no device context so far) that will be among _host_bindings()."""
+        return [n for n, (r, _) in self._readers_host.items() if n not in self.readers and n not in self.discarded_readers and
+                (getattr(r, 'device_kind', None) == 'umesh' or
+                 (getattr(r, 'device_kind', None) is None and isinstance(r, ContinuousReader)))]
 
     def _ensemble_current(self):
         """The current comes (also) from a reader that hands it out as a list of ensemble members."""
@@ -1018,11 +1026,18 @@ class OpenDriftSimulation(Configurable):
         time = self.time if time is None else time
         if not hb or len(P) == 0:
             return
-        d = P.download()
+        d = None
         for name, b in hb:
             vs = [v for v in b.variables if v in names and name in self.priority_list.get(v, [])]
             if not vs:
                 continue
+            if getattr(b, 'mesh', None) is not None:      # the same rule in one launch: the positions stay on the device
+                try:
+                    b.sample_mesh(P, vs, [self.priority_list[v][0] == name for v in vs], time)
+                except Exception as e:
+                    self._reader_failed(name, b, e)
+                continue
+            d = P.download() if d is None else d
             try:
                 vals = b.evaluate_on_host(vs, time, d['lon'], d['lat'], d['z'], element_ID=d['ID'])
             except Exception as e:      # the reference catches every exception of a reader call (environment.py:640-668)
@@ -1295,7 +1310,7 @@ class OpenDriftSimulation(Configurable):
                     'deactivate_elements')) and
                 self.get_config('drift:max_age_seconds') is None and
                 not self.get_config('general:coastline_approximation_precision') and
-                not self._host_bindings() and
+                not self._host_bindings() and not self._unbound_off_list_readers() and
                 # report_missing_variables comes BEFORE deactivate_outside in the loop (:2251-2253) but sits inside the
                 # launch: an element both outside the domain and without data must end as 'missing_data'
                 not (any(self.get_config('drift:deactivate_%s_of' % k) is not None for k in ('west', 'east', 'south', 'north'))
@@ -1479,6 +1494,9 @@ class OpenDriftSimulation(Configurable):
             raise ValueError('Please seed elements before starting a run.')
         if outfile is not None:
             raise NotImplementedError('netCDF export is host-side I/O outside the hot path')
+        if self._world > 1 and any(getattr(r, 'device_kind', None) == 'umesh' for r, _ in self._readers_host.values()):
+            raise NotImplementedError('an UnstructuredReader in a sharded run: its time levels are not broadcast to the ranks '
+                                      '(DESIGN.md section 8k)')
         steps, out_every = self._time_arguments(time_step, steps, time_step_output, duration, end_time)
         # skip_if conditionals of required_variables (:1899-1906)
         for vn, var in list(self.required_variables.items()):

@@ -20,7 +20,7 @@ import threading
 
 import numpy as np
 
-from . import projection
+from . import _abi, projection
 
 
 def _epoch(t):
@@ -483,6 +483,197 @@ class SigmaGridReader(StructuredReader):
         return out
 
 
+class UnstructuredReader(BaseReader):
+    """In-memory reader on a triangular mesh, the reference's UnstructuredReader family (basereader/unstructured.py,
+    reader_netCDF_CF_unstructured.py; FVCOM-style output): node variables at the nearest node, face variables at the nearest
+    face centre, 3-D ones at the nearest sigma layer or level of that column, all at the nearest time level.  Nothing is
+    interpolated.
+
+    x, y [N] / xc, yc [E]: node / face-centre coordinates in the mesh's CRS (`proj4`).  node_arrays / face_arrays: {variable:
+    [nt, N] | [nt, L, N] | [N]} (over E for faces); a [nt, L, .] array is on the layers when L == len(siglay), on the levels when
+    L == len(siglev) -- decided by the count, as the reference decides by shp[1].  siglay [L, N], siglev [L + 1, N], h [N] and
+    their *_center / h_center twins over the faces are kept as float32, which is what model files hold: float64 input is ROUNDED
+    to float32 here, so that sigma * h is the float32 product the reference forms.
+
+    On the device (`device_kind = 'umesh'`) the whole get_variables -- projection, search, sigma rule, gather, rotation of vector
+    pairs, merge by priority -- is one launch per call (odr_umesh_sample).  `get_variables` below answers on the
+    host with scipy's cKDTree, as the reference does; it needs no device.
+
+    Two deviations from the reference, on purpose: a 2-D variable is the value at the nearest node / face at the
+    nearest time (the reference's 2-D branch returns a slab of the array without picking per element or per time), and any
+    array with a level axis is 3-D (the reference asks for a dimension literally named 'siglev' on nodes)."""
+    device_kind = 'umesh'
+
+    def __init__(self, x, y, xc, yc, times, node_arrays, face_arrays, siglay=None, siglev=None, siglay_center=None, siglev_center=None,
+                 h=None, h_center=None, proj4='+proj=latlong', name='unstructured_reader'):
+        self.proj4, self.name = proj4, name
+        pd = projection.parse_proj4(proj4)        # NotImplementedError: not on the device path
+        if pd.get('kind') == 'ob_tran':
+            raise NotImplementedError('a mesh on a rotated pole (+proj=ob_tran) is not on the device path')
+        self.x, self.y = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (x, y))
+        self.xc, self.yc = (np.ascontiguousarray(a if a is not None else [], dtype=np.float64).ravel() for a in (xc, yc))
+        if len(self.x) != len(self.y) or len(self.xc) != len(self.yc) or len(self.x) == 0:
+            raise ValueError('%d x and %d y node coordinates, %d xc and %d yc face centres' % (len(self.x), len(self.y), len(self.xc), len(self.yc)))
+        if not (np.isfinite(self.x).all() and np.isfinite(self.y).all() and np.isfinite(self.xc).all() and np.isfinite(self.yc).all()):
+            raise ValueError('a mesh coordinate is not finite')
+        N, E = len(self.x), len(self.xc)
+        self.xmin, self.xmax, self.ymin, self.ymax = float(self.x.min()), float(self.x.max()), float(self.y.min()), float(self.y.max())
+        self.times = None if times is None else list(times)
+        if self.times:
+            if any(b <= a for a, b in zip(self.times, self.times[1:])):
+                raise ValueError('times must increase')
+            self.start_time, self.end_time = self.times[0], self.times[-1]
+
+        def f32(a, npts, what):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape[-1] != npts:
+                raise ValueError('%s has %d points, the mesh %d' % (what, a.shape[-1], npts))
+            return a
+        self.siglay, self.siglev, self.h = f32(siglay, N, 'siglay'), f32(siglev, N, 'siglev'), f32(h, N, 'h')
+        self.siglay_center, self.siglev_center, self.h_center = f32(siglay_center, E, 'siglay_center'), \
+            f32(siglev_center, E, 'siglev_center'), f32(h_center, E, 'h_center')
+        lays = [a.shape[0] for a in (self.siglay, self.siglay_center) if a is not None]
+        levs = [a.shape[0] - 1 for a in (self.siglev, self.siglev_center) if a is not None]
+        if len(set(lays + levs)) > 1:
+            raise ValueError('the sigma arrays disagree on the number of layers: %s layers, %s levels' % (lays, [k + 1 for k in levs]))
+        self.n_siglay = (lays + levs + [0])[0]
+        self.node_arrays, self.face_arrays = {}, {}
+        nt = len(self.times) if self.times else 1
+        for arrays, mine, npts, sig, depth, where in ((node_arrays or {}, self.node_arrays, N, (self.siglay, self.siglev), self.h, 'node'),
+                                                      (face_arrays or {}, self.face_arrays, E, (self.siglay_center, self.siglev_center),
+                                                       self.h_center, 'face')):
+            for v, a in arrays.items():
+                a = np.ascontiguousarray(a, dtype=np.float32)
+                if a.ndim not in (1, 2, 3) or a.shape[-1] != npts or (a.ndim > 1 and a.shape[0] != nt):
+                    raise ValueError('%s variable %s of shape %s: expected [%d], [%d, %d] or [%d, levels, %d]' % (where, v, a.shape, npts, nt, npts, nt, npts))
+                if a.ndim == 3:
+                    L = a.shape[1]
+                    s = sig[0] if L == self.n_siglay else sig[1] if L == self.n_siglay + 1 else None
+                    if not self.n_siglay or s is None or depth is None:
+                        raise ValueError('%s variable %s has %d levels: the reader needs the matching sigma array (%d layers) and the depth '
+                                         '%s' % (where, v, L, self.n_siglay, 'h' if where == 'node' else 'h_center'))
+                mine[v] = a
+        both = set(self.node_arrays) & set(self.face_arrays)
+        if both:
+            raise ValueError('%s given on nodes and on faces' % sorted(both))
+        self.variables = list(self.node_arrays) + list(self.face_arrays)
+        self._trees = {}
+        super().__init__()
+
+    # ---- time: the `times` branch of variables.py:417-430
+    def nearest_time(self, time):
+        """(nearest_time, time_before, time_after, indx_nearest, indx_before, indx_after); midway between two levels: the later."""
+        if not self.times:
+            return None, None, None, 0, 0, 0
+        if len(self.times) == 1:
+            return self.times[0], self.times[0], None, 0, 0, 0
+        import bisect
+        ib = max(0, bisect.bisect_left(self.times, time) - 1)
+        if ib + 1 < len(self.times) and self.times[ib + 1] == time:
+            ib += 1
+        ia = min(ib + 1, len(self.times) - 1)
+        k = ib if (time - self.times[ib]) < (self.times[ia] - time) else ia
+        return self.times[k], self.times[ib], self.times[ia], k, ib, ia
+
+    def placement(self, variable):
+        """(array, on_faces, number of levels or 0) of a variable; ValueError when the reader has neither."""
+        if variable in self.node_arrays:
+            a, on_faces = self.node_arrays[variable], False
+        elif variable in self.face_arrays:
+            a, on_faces = self.face_arrays[variable], True
+        else:
+            raise ValueError('Variable not available: %s\nAvailable parameters are: %s' % (variable, self.variables))
+        return a, on_faces, (a.shape[1] if a.ndim == 3 else 0)
+
+    def level(self, variable, k):
+        """The array of time level k: [points] or [levels, points]."""
+        a = self.placement(variable)[0]
+        return a if a.ndim == 1 else a[k]
+
+    def _tree(self, on_faces):
+        if on_faces not in self._trees:
+            from scipy.spatial import cKDTree
+            self._trees[on_faces] = cKDTree(np.c_[self.xc, self.yc] if on_faces else np.c_[self.x, self.y])
+        return self._trees[on_faces]
+
+    def nearest_node(self, x, y):
+        return self._tree(False).query(np.c_[x, y], k=1)[1]
+
+    def nearest_face(self, x, y):
+        return self._tree(True).query(np.c_[x, y], k=1)[1]
+
+    def sigma_index(self, variable, idx, z):
+        """argmin(|sigma[:, idx] * h[idx] - z|), the first minimum (__nearest_node_sigma__ / __nearest_face_sigma__)."""
+        _, on_faces, L = self.placement(variable)
+        lay = L == self.n_siglay
+        sigma = (self.siglay_center if lay else self.siglev_center) if on_faces else (self.siglay if lay else self.siglev)
+        depths = sigma[:, idx] * (self.h_center if on_faces else self.h)[idx]
+        return np.argmin(np.abs(depths - np.atleast_2d(np.asarray(z, dtype=np.float64))), axis=0)
+
+    def get_variables(self, requested_variables, time=None, x=None, y=None, z=None):
+        """{variable: float32 values at the nearest node / face, sigma layer / level and time level} for positions x, y in the
+        mesh's coordinates and depths z -- for every position, covered or not (the caller masks, as the reference's does)."""
+        if isinstance(requested_variables, str):
+            requested_variables = [requested_variables]
+        x, y = np.atleast_1d(np.asarray(x, dtype=np.float64)), np.atleast_1d(np.asarray(y, dtype=np.float64))
+        z = np.zeros(len(x)) if z is None else np.broadcast_to(np.asarray(z, dtype=np.float64), x.shape)
+        if time is None:
+            time = self.start_time
+        if self.times and not self.covers_time(time):
+            raise ValueError('Requested time (%s) is outside the time coverage (%s - %s) of %s' % (time, self.start_time, self.end_time, self.name))
+        k = self.nearest_time(time)[3]
+        out, found = {}, {}
+        for v in requested_variables:
+            a, on_faces, L = self.placement(v)
+            if on_faces not in found:
+                found[on_faces] = self.nearest_face(x, y) if on_faces else self.nearest_node(x, y)
+            idx = found[on_faces]
+            lev = self.level(v, k)
+            out[v] = lev[self.sigma_index(v, idx, z), idx] if L else lev[idx]
+        return out
+
+    def rotation_angle(self, x, y):
+        """rot_angle_rad of rotate_vectors (variables.py:59-109) at mesh positions: minus the WGS84 azimuth of the 10 m line along +y."""
+        lo1, la1 = self.xy2lonlat(x, y)
+        lo2, la2 = self.xy2lonlat(x, np.asarray(y) + 10.0)
+        return -np.radians(wgs84_forward_azimuth(lo1, la1, lo2, la2))
+
+    def modulate_longitude(self, lon):      # variables.py:259-280, for a geographic mesh
+        lon = np.asarray(lon, dtype=np.float64)
+        return np.mod(lon + 180, 360) - 180 if self.xmin < 0 else np.mod(lon, 360)
+
+    def get_variables_interpolated(self, variables, time, lon, lat, z, rotate=True):
+        """What the device launch gives an element with an empty slot, on the host: NaN outside the box of the nodes or outside
+        the time coverage, vector pairs rotated to east / north unless the mesh is geographic."""
+        lon, lat = np.atleast_1d(np.asarray(lon, dtype=np.float64)), np.atleast_1d(np.asarray(lat, dtype=np.float64))
+        n = len(lon)
+        out = {v: np.full(n, np.nan, np.float32) for v in variables}
+        for v in variables:
+            self.placement(v)
+        if self.times and not self.covers_time(time):
+            return out
+        geographic = projection.parse_proj4(self.proj4).get('kind', 'latlong') == 'latlong'
+        x, y = (self.modulate_longitude(lon), lat) if geographic else self.lonlat2xy(lon, lat)
+        x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+        with np.errstate(invalid='ignore'):
+            ok = np.isfinite(x + y) & (x >= self.xmin) & (x <= self.xmax) & (y >= self.ymin) & (y <= self.ymax)
+        if not ok.any():
+            return out
+        zz = np.broadcast_to(np.asarray(z, dtype=np.float64), (n,))[ok]
+        res = self.get_variables(list(variables), time, x[ok], y[ok], zz)
+        if rotate and not geographic:
+            for vx, vy in VECTOR_PAIRS_XY:
+                if vx in res and vy in res:
+                    rot = self.rotation_angle(x[ok], y[ok])
+                    u, w = res[vx], res[vy]
+                    res[vx], res[vy] = u * np.cos(rot) - w * np.sin(rot), u * np.sin(rot) + w * np.cos(rot)
+        for v in variables:
+            out[v][ok] = res[v]
+        return out
+
+
 def _dev(a):
     """a block array as Context.upload_block_device wants it: the device pointer of a CUDA tensor, else the host array"""
     return int(a.data_ptr()) if hasattr(a, 'is_cuda') and a.is_cuda else a
@@ -591,6 +782,7 @@ class DeviceReaderBinding:
         self.stall_s = 0.0             # host time spent waiting for a level that was due (run().timing reports the sum)
         self._dist_pre = {}            # sharded run: time index -> (tensors, works) of a level whose broadcast is under way
         self._ahead, self._ahead_last = None, None   # sharded run, rank 0: the next level read on a worker thread (ReadAhead)
+        self.mesh = None               # device.UMesh of an UnstructuredReader
         kind = getattr(reader, 'device_kind', None)
         # a ContinuousReader the device has no closed form for (a user's analytic or point-wise reader,
         # basereader/continuous.py:20-46): evaluated on the host at the element positions, values uploaded
@@ -606,9 +798,16 @@ class DeviceReaderBinding:
         elif kind == 'oscillating':
             self.sid = ctx.add_oscillating(reader.variables[0], reader.amplitude, reader.period_seconds,
                                            _epoch(reader.zero_time))
+        elif kind == 'umesh':
+            # an unstructured mesh is no source of the device's priority-list walk (sid stays None: _bind_variables and
+            # set_extent leave it alone); the model samples it in a launch of its own behind that walk (sample_mesh)
+            self.sid = None
+            self.mesh = ctx.umesh(reader.x, reader.y, reader.xc, reader.yc, proj=projection.parse_proj4(reader.proj4),
+                                  **{k: getattr(reader, k) for k in ('siglay', 'siglev', 'siglay_center', 'siglev_center', 'h', 'h_center')})
+            self.mesh_slots = {}     # time index -> slot of the mesh (at most three resident)
         else:
             self.sid = None  # created with the first block (the grid comes with it)
-        if kind and reader.start_time is not None:
+        if kind and kind != 'umesh' and reader.start_time is not None:
             ctx.set_time_coverage(self.sid, _epoch(reader.start_time), _epoch(reader.end_time), reader.always_valid)
 
     def _static_ids(self):
@@ -734,6 +933,8 @@ class DeviceReaderBinding:
         step samples THIS reader at (default: t0, the middle and t1 -- a Runge-Kutta-4 step of a reader that holds the
         current; the model passes [t0] for Euler and for readers the stages do not sample)."""
         r = self.reader
+        if self.mesh is not None:
+            return self._ensure_mesh_levels(times if times is not None else (t0, t0 + (t1 - t0) / 2, t1))
         if extent is None:
             extent = getattr(self, 'extent', None)
         if not self.is_grid():
@@ -798,6 +999,44 @@ class DeviceReaderBinding:
                         self.ctx.drop_block(self.sid, self.slots.pop(k_old))
                 if len(self.slots) + len(self.staged) < self.NSLOTS:
                     self._upload(kn, extent, None, asynchronous=True)
+
+    def _ensure_mesh_levels(self, times):
+        """The time levels NEAREST to the given instants become resident on the mesh: at most three distinct ones, uploaded
+        synchronously, every variable of the binding."""
+        r = self.reader
+        need = sorted({r.nearest_time(t)[3] for t in times if r.covers_time(t)})
+        for k in [k for k in self.mesh_slots if k not in need]:
+            self.mesh_slots.pop(k)
+        free = [s for s in range(_abi.UMESH_LEVELS) if s not in self.mesh_slots.values()]
+        for k in need:
+            if k in self.mesh_slots:
+                continue
+            if not free:
+                raise ReaderLevelsError('reader %s: one model time step needs %d time levels resident, at most %d fit'
+                                        % (r.name, len(need), _abi.UMESH_LEVELS))
+            slot = free.pop(0)
+            t = _epoch(r.times[k]) if r.times else 0.0
+            for v in self.variables:
+                self.mesh.set_level(slot, t, v, r.level(v, k), r.placement(v)[1])
+            self.mesh_slots[k] = slot
+
+    def sample_mesh(self, P, variables, first, time):
+        """The mesh's values for the particle set P at `time`, merged into its environment slots by priority (first[k]: the mesh
+        heads the list of variable k) -- on the device, in launches of at most eight variables.  The slot is chosen here by the
+        reference's nearest-time rule; outside the reader's time coverage nothing is sampled (environment.py:640-668)."""
+        r = self.reader
+        if not r.covers_time(time):
+            return
+        k = r.nearest_time(time)[3]
+        if k not in self.mesh_slots:
+            self._ensure_mesh_levels([time])
+        # a vector pair stays in one launch: its components are rotated together
+        pairs = [p for p in VECTOR_PAIRS_XY if p[0] in variables and p[1] in variables]
+        ordered = [v for p in pairs for v in p] + [v for v in variables if not any(v in p for p in pairs)]
+        flag = dict(zip(variables, first))
+        for o in range(0, len(ordered), _abi.UMESH_MAX_VARIABLES):
+            vs = ordered[o:o + _abi.UMESH_MAX_VARIABLES]
+            P.umesh_sample(self.mesh, self.mesh_slots[k], vs, [flag[v] for v in vs])
 
     def _read_and_broadcast(self, k, x, y, async_op):
         """Sharded run: rank 0 reads time level k, every rank receives it.  A reader failure on rank 0 reaches every rank as
