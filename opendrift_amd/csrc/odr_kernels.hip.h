@@ -2818,11 +2818,20 @@ __global__ __launch_bounds__(1024) void k_scan_add(unsigned *a, long long n, con
   if (i < n) a[i] += boff[blockIdx.x];
 }
 
+// Every 32-bit array a particle set can carry: id status moving, the four float properties, one sampled environment variable
+// per NVAR, the property slots.  all_arrays (odrift.hip) refuses a set that would need more (the bound was a literal 40 once:
+// a set with all nine slots and 25 or more sampled variables wrote past the arrays, and the kernels read dead32[] out of the
+// arguments behind the struct).
+constexpr int NAUX = 9;
+constexpr int CMP_MAX32 = 3 + 4 + NVAR + NAUX;
+static_assert(sizeof(PView::env) / sizeof(float *) == NVAR && sizeof(PView::aux) / sizeof(float *) == NAUX,
+              "CmpArrays holds one entry per environment variable and per property slot of PView");
 struct CmpArrays {
   int n64, n32;
   const double *src64[8]; double *dst64[8]; double *dead64[8];  // lon lat z plon plat slon slat
-  const int *src32[40];   int *dst32[40];   int *dead32[40];
+  const int *src32[CMP_MAX32];   int *dst32[CMP_MAX32];   int *dead32[CMP_MAX32];
 };
+static_assert(sizeof(CmpArrays) <= 2048, "CmpArrays travels by value in the kernel arguments");
 
 __global__ __launch_bounds__(BLOCK) void k_cmp_scatter(const int *status, long long n,
                                                        const unsigned *boff, CmpArrays A,

@@ -2181,8 +2181,14 @@ static int ensure_alt(odr_particles *p) {
 
 // with_env = false: without the environment and the sample position (slon / slat), which the next environment sample
 // rewrites for every element -- a re-sort at the top of a step moves 68 instead of ~130 bytes per particle
-static void all_arrays(odr_particles *p, CmpArrays &A, bool with_env = true) {
+static int all_arrays(odr_particles *p, CmpArrays &A, bool with_env = true) {
+  static_assert(sizeof(p->env) / sizeof(p->env[0]) == NVAR && sizeof(p->aux) / sizeof(p->aux[0]) == NAUX,
+                "CMP_MAX32 counts the environment variables and property slots of a particle set");
   memset(&A, 0, sizeof A);
+  int want = 3 + 4;           // refuse before writing: a count beyond the capacity must never reach the arrays
+  if (with_env) for (int k = 0; k < NVAR; ++k) want += p->env[k] ? 1 : 0;
+  for (int k = 0; k < NAUX; ++k) want += p->aux[k] ? 1 : 0;
+  if (want > CMP_MAX32) return fail(ODR_ERR_STATE, "the particle set carries %d 32-bit arrays, the kernels take %d", want, CMP_MAX32);
   const int n64 = with_env ? 7 : 5;
   for (int k = 0; k < n64; ++k) {
     A.src64[k] = p->d64[k]; A.dst64[k] = p->alt64[k];
@@ -2195,9 +2201,10 @@ static void all_arrays(odr_particles *p, CmpArrays &A, bool with_env = true) {
   if (with_env)
     for (int k = 0; k < NVAR; ++k)
       if (p->env[k]) { A.src32[m] = (const int *)p->env[k]; A.dst32[m] = (int *)p->altenv[k]; ++m; }
-  for (int k = 0; k < 9; ++k)
+  for (int k = 0; k < NAUX; ++k)
     if (p->aux[k]) { A.src32[m] = (const int *)p->aux[k]; A.dst32[m] = (int *)p->altaux[k]; ++m; }
   A.n32 = m;
+  return 0;
 }
 
 static void swap_sets(odr_particles *p, bool with_env = true) {
@@ -2306,10 +2313,10 @@ int odr_compact_apply(odr_ctx *c, odr_particles *p, int64_t *n_active) {
   if (kept == p->n) { if (n_active) *n_active = p->n; return 0; }  // "No elements to deactivate"
   int rc = ensure_alt(p);  // (allocates the deactivated store)
   if (rc) return rc;
+  CmpArrays A;
+  if ((rc = all_arrays(p, A))) return rc;
   // exclusive scan of the per-block counts of the last odr_scan_status (only now that something is to be removed)
   hipLaunchKernelGGL(k_cmp_scan, dim3(1), dim3(1024), 0, c->stream, p->bcount, (long long)nb, c->counter + 3);
-  CmpArrays A;
-  all_arrays(p, A);
   long long removed = p->n - kept;
   if (getenv("ODR_ORDERED_COMPACT")) {  // order-preserving variant: rewrites every array
     hipLaunchKernelGGL(k_cmp_scatter, dim3(nb), dim3(BLOCK), 0, c->stream, p->i32[1], p->n, p->bcount, A, p->ndead);
@@ -2358,6 +2365,8 @@ int odr_sort_particles_ex(odr_ctx *c, odr_particles *p, int32_t sid, int keep_en
   int rc = flush_world(c);
   if (rc) return rc;
   if ((rc = ensure_alt(p))) return rc;
+  CmpArrays A;
+  if ((rc = all_arrays(p, A, with_env))) return rc;
   const DevSource &s = c->hw.src[sid];
   int slot = s.level_slot[0];
   const DevBlock &b = s.slot[slot];
@@ -2403,8 +2412,6 @@ int odr_sort_particles_ex(odr_ctx *c, odr_particles *p, int32_t sid, int keep_en
     hipLaunchKernelGGL(k_wg_fill, dim3((nt1 + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, c->stream, hist, ntiles, 64u * (unsigned)zb, wg_nw, p->wg_tab, (unsigned)cap);
     p->wg_grid = cap; p->wg_n = p->n; p->wg_sid = sid; p->wg_src_gen = c->src_gen[sid]; p->wg_valid = true;
   }
-  CmpArrays A;
-  all_arrays(p, A, with_env);
   hipLaunchKernelGGL(k_gather_perm, dim3(nblk(p->n)), dim3(BLOCK), 0, c->stream, perm, p->n, A);
   HIPCHK(hipGetLastError());
   swap_sets(p, with_env);     // host pointers only: everything after this call is ordered behind the gather on the stream

@@ -20,6 +20,7 @@ import gc
 import numpy as np
 import pytest
 
+from bookkeeping_model import cell_keys, sort_bins
 from conftest import _gpu_tests_selected
 from scenarios import Scenario
 from oracle import oracle as orc
@@ -63,11 +64,6 @@ def is_small(ny, nx, rec):
 
 def one_pass_preparation(ny, var_nz):
     return ny < 65536 and sum(var_nz.values()) < 65536
-
-
-def sort_bins(ny, nx):
-    """Histogram bins of sort_by_cell: 8x8-cell tiles of 64 cells, plus one for elements outside the grid."""
-    return ((nx + 7) // 8) * ((ny + 7) // 8) * 64 + 1
 
 
 def fast_read_address(node, byte_in_record, rec):
@@ -484,17 +480,9 @@ def test_fused_step_same_bits_as_generic_kernels(case, monkeypatch):
 
 # ------------------------------------------------------------------ 5. sort by cell
 def _cell_keys(c, lon, lat):
-    """sort_key of the host (k_sort_hist): 8x8-cell tiles, row-major cells inside; outside the grid: the last bin."""
-    ny, nx = c['ny'], c['nx']
-    x, y = c['f']['x'], c['f']['y']
-    lon = np.mod(lon, 360.0)                         # (lon_mode 2: the grid's longitudes are all >= 0)
-    xi = (lon - float(x[0])) / float(x[-1] - x[0]) * (nx - 1)
-    yi = (lat - float(y[0])) / float(y[-1] - y[0]) * (ny - 1)
-    inside = (xi >= 0) & (xi <= nx - 1) & (yi >= 0) & (yi <= ny - 1)
-    ix, iy = np.where(inside, xi, 0).astype(np.int64), np.where(inside, yi, 0).astype(np.int64)
-    ntx = (nx + 7) // 8
-    key = ((iy >> 3) * ntx + (ix >> 3)) * 64 + (iy & 7) * 8 + (ix & 7)
-    return np.where(inside, key, sort_bins(ny, nx) - 1)
+    """sort_key of the host (k_sort_hist); lon_mode 2: the grid's longitudes are all >= 0"""
+    assert (len(c['f']['y']), len(c['f']['x'])) == (c['ny'], c['nx'])
+    return cell_keys(c['f']['x'], c['f']['y'], lon, lat, lon_mode=2)
 
 
 @_params(A_ONLY)
