@@ -987,6 +987,36 @@ int odr_umesh_nearest(odr_ctx *ctx, odr_umesh *mesh, int on_faces, int64_t n, co
  * that came later (waits for it) */
 int odr_umesh_last_kernel_ms(odr_ctx *ctx, float *ms);
 
+/* ---------------------------------------------------------------- coastline polygons (shape reader)
+ * The reference's reader_shape.Reader (readers/reader_shape.py): land_binary_mask = shapely.contains_xy(unary_union(polys), x, y),
+ * here an exact crossing-number test behind a uniform grid whose cost per point is the local density of edges
+ * (csrc/odr_shape.hip.h).
+ * odr_shape_create (Reader.__init__, reader_shape.py:82-104): the edges of all rings of all polygons, host float64 in the
+ * reader's own coordinates (proj; NULL: geographic), poly[k] in 0 .. n_poly - 1 the polygon edge k belongs to (exterior ring
+ * and holes alike); closed rings, no edge of zero length.  nx, ny: the grid, 0 = automatic (about two cells per edge).  invert:
+ * the mask is 1 - contains (:106-110).  The grid and its lists are built on the host, once; offsets are 64-bit.  Coverage is the
+ * box of the vertices.  ODR_ERR_INVALID: no edge, a vertex that is not finite, an edge of zero length, a polygon id out of
+ * range, more than 2^28 cells, ODR_PROJ_OB_TRAN / ODR_PROJ_CURVILINEAR.  odr_shape_destroy waits for the context's stream. */
+typedef struct odr_shape odr_shape;
+int odr_shape_create(odr_ctx *ctx, const odr_proj_desc *proj, int64_t n_edges, const double *x1, const double *y1, const double *x2,
+                     const double *y2, const int32_t *poly, int32_t n_poly, int32_t nx, int32_t ny, int invert, odr_shape **out);
+int odr_shape_destroy(odr_ctx *ctx, odr_shape *shape);
+/* Reader.get_variables behind get_variables_interpolated (reader_shape.py:112-130; basereader/variables.py:860-914, covers_positions_xy
+ * :229-257) for every element of the particle set, in ONE launch: lonlat2xy, the coverage box, the list walk of the element's
+ * cell, invert, and the merge into the land_binary_mask slot: the value is taken when first != 0 or the slot holds nothing
+ * finite.  Elements outside the box keep what they have; a slot that was never sampled starts as NaN.  Enqueued on the
+ * context's stream. */
+int odr_shape_sample(odr_ctx *ctx, odr_particles *p, odr_shape *shape, int first);
+/* The bare query (Reader._on_land, reader_shape.py:106-110; tests, tools/bench_shape.py): out[i] = 1 / 0 at (x[i], y[i]) in the
+ * reader's coordinates, NaN outside the box or where the point is not finite; host float64 in, host float32 out.  Synchronous. */
+int odr_shape_contains(odr_ctx *ctx, odr_shape *shape, int64_t n, const double *x, const double *y, float *out);
+/* stats[0 .. 7]: cells, list entries, longest list, mean list of the cells that have one, times the grid's origin was shifted to
+ * keep its lines off the vertices, bytes of the index on the device, nx, ny */
+int odr_shape_stats(odr_ctx *ctx, odr_shape *shape, double *stats);
+/* device time [ms] of the launches of this process's last odr_shape_contains, or of the launch of its last odr_shape_sample if
+ * that came later (waits for it) */
+int odr_shape_last_kernel_ms(odr_ctx *ctx, float *ms);
+
 /* ---------------------------------------------------------------- ROMS sigma grid
  * The sigma -> z regridding reader_ROMS_native.get_variables applies to every 4-D variable of a block
  * (reader_ROMS_native.py:512-538,617-684) with roppy (readers/roppy/depth.py): sdepth (:31-113, rho points,

@@ -242,6 +242,12 @@ _SIGNATURES = {
     'odr_umesh_sample': [_vp, _vp, _vp, C.c_int32, C.c_int32, _ip, _ip],
     'odr_umesh_nearest': [_vp, _vp, C.c_int, C.c_int64, _dp, _dp, _ip],
     'odr_umesh_last_kernel_ms': [_vp, _fp],
+    'odr_shape_create': [_vp, _P(ProjDesc), C.c_int64, _dp, _dp, _dp, _dp, _ip, C.c_int32, C.c_int32, C.c_int32, C.c_int, _P(_vp)],
+    'odr_shape_destroy': [_vp, _vp],
+    'odr_shape_sample': [_vp, _vp, _vp, C.c_int],
+    'odr_shape_contains': [_vp, _vp, C.c_int64, _dp, _dp, _fp],
+    'odr_shape_stats': [_vp, _vp, _dp],
+    'odr_shape_last_kernel_ms': [_vp, _fp],
 }
 UMESH_MAX_VARIABLES, UMESH_LEVELS = 8, 3      # odr_umesh_sample, odr_umesh_set_level
 EXPORTS = sorted(list(_SIGNATURES) + ['odr_last_error', 'odr_version'])

@@ -577,6 +577,15 @@ class Context:
         check(self.lib.odr_umesh_last_kernel_ms(self.h, C.byref(ms)))
         return ms.value
 
+    def shape(self, x1, y1, x2, y2, poly, n_polygons, proj=None, invert=False, nx=0, ny=0):
+        """The device image of coastline polygons (odr_shape_create): Shape."""
+        return Shape(self, x1, y1, x2, y2, poly, n_polygons, proj=proj, invert=invert, nx=nx, ny=ny)
+
+    def shape_last_kernel_ms(self):
+        ms = C.c_float()
+        check(self.lib.odr_shape_last_kernel_ms(self.h, C.byref(ms)))
+        return ms.value
+
     def particles(self, capacity):
         return Particles(self, capacity)
 
@@ -705,6 +714,11 @@ class Particles:
             raise ValueError('%d variables and %d first flags' % (len(ids), len(first)))
         fl, pf = _i([int(bool(f)) for f in first])
         check(self.lib.odr_umesh_sample(self.ctx.h, self.h, mesh.ptr, int(slot), len(ids), pi, pf))
+
+    def shape_sample(self, shape, first):
+        """land_binary_mask of the polygons at every element, merged into the environment slot in one launch (odr_shape_sample):
+        the value is taken where `first` or where the slot holds nothing finite; elements outside the box keep what they have."""
+        check(self.lib.odr_shape_sample(self.ctx.h, self.h, shape.ptr, int(bool(first))))
 
     def env_add_noise(self, var_x, var_y, std, step=0, normals=None, uniform=False):
         """drift:current_uncertainty / wind_uncertainty (normal) or drift:current_uncertainty_uniform (uniform=True) on
@@ -1365,7 +1379,7 @@ def _touching(fn):
     return wrapper
 
 
-for _name in ('append', 'upload', 'env_sample', 'umesh_sample', 'env_upload', 'env_add_noise', 'advect', 'env_coast_advect',
+for _name in ('append', 'upload', 'env_sample', 'umesh_sample', 'shape_sample', 'env_upload', 'env_add_noise', 'advect', 'env_coast_advect',
               'update_positions', 'advect_wind', 'stokes_drift', 'advect_sea_ice', 'set_property', 'leeway_capsize', 'leeway', 'hdiffusion', 'movers',
               'vmix', 'vmix_analytic', 'vmix_oil', 'vertical_advection', 'vertical_buoyancy', 'coastline', 'coastline_crossing',
               'increase_age', 'deactivate_missing', 'remap_status', 'seafloor', 'deactivate', 'deactivate_outside', 'compact',
@@ -1474,6 +1488,48 @@ class UMesh:
     def close(self):
         if self.ptr and self.ctx.h:
             self.ctx.lib.odr_umesh_destroy(self.ctx.h, self.ptr)
+        self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Shape:
+    """Device image of coastline polygons (odr_shape_create / _destroy): the uniform grid over the box of the rings and the
+    per-cell lists of edges and corner toggles."""
+    STATS = ('cells', 'entries', 'longest_list', 'mean_list', 'nudges', 'bytes', 'nx', 'ny')
+
+    def __init__(self, ctx, x1, y1, x2, y2, poly, n_polygons, proj=None, invert=False, nx=0, ny=0):
+        (x1, p1), (y1, q1), (x2, p2), (y2, q2) = (_d(np.ravel(a)) for a in (x1, y1, x2, y2))
+        poly, pp = _i(np.ravel(poly))
+        if not (len(x1) == len(y1) == len(x2) == len(y2) == len(poly)):
+            raise ValueError('edge arrays of %d, %d, %d, %d and %d elements' % (len(x1), len(y1), len(x2), len(y2), len(poly)))
+        self.n_edges, self.n_polygons = len(x1), int(n_polygons)
+        pd = proj_desc(proj)
+        self.ctx, self.ptr = ctx, C.c_void_p()
+        check(ctx.lib.odr_shape_create(ctx.h, None if pd is None else C.byref(pd), self.n_edges, p1, q1, p2, q2, pp, self.n_polygons,
+                                       int(nx), int(ny), int(bool(invert)), C.byref(self.ptr)))
+
+    def contains(self, x, y):
+        """land_binary_mask at (x, y) in the polygons' coordinates (odr_shape_contains): float32 1 / 0, NaN outside the box."""
+        (x, px), (y, py) = _d(np.ravel(x)), _d(np.ravel(y))
+        if len(x) != len(y):
+            raise ValueError('%d x and %d y' % (len(x), len(y)))
+        out = np.empty(len(x), np.float32)
+        check(self.ctx.lib.odr_shape_contains(self.ctx.h, self.ptr, len(x), px, py, out.ctypes.data_as(_fp)))
+        return out
+
+    def stats(self):
+        a = np.zeros(len(self.STATS))
+        check(self.ctx.lib.odr_shape_stats(self.ctx.h, self.ptr, a.ctypes.data_as(_dp)))
+        return dict(zip(self.STATS, a.tolist()))
+
+    def close(self):
+        if self.ptr and self.ctx.h:
+            self.ctx.lib.odr_shape_destroy(self.ctx.h, self.ptr)
         self.ptr = C.c_void_p()
 
     def __del__(self):

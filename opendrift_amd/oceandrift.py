@@ -621,6 +621,9 @@ class OpenDriftSimulation(Configurable):
             raise ImportError("seed:ocean_only needs scipy.spatial.cKDTree to move elements seeded on land to the nearest ocean "
                               "point (basemodel/__init__.py:1020-1026); install SciPy or set_config('seed:ocean_only', False)") from e
         lon, lat = np.array(lon, dtype=np.float64), np.array(lat, dtype=np.float64)
+        head = self.priority_list.get('land_binary_mask', [None])[0]
+        if head in self.readers and getattr(self.readers[head], 'shape', None) is not None and len(lon) > 0:
+            return self._closest_ocean_points_shape(self.readers[head].reader, lon, lat)
         live = [n for n in self.priority_list.get('land_binary_mask', []) if n in self.readers and self.readers[n].sid is not None]
         if not live or len(lon) == 0:
             return lon, lat, None      # no land reader on the device (the reference would fetch the GSHHG landmask: not shipped)
@@ -655,6 +658,25 @@ class OpenDriftSimulation(Configurable):
         lon[land_indices] = np.float32(oceangridlons[indices])      # (stored into the float32 schedule)
         lat[land_indices] = np.float32(oceangridlats[indices])
         logger.info('Moved %i out of %i points from land to water' % (len(land_indices), len(lon)))
+        return lon, lat, land_indices
+
+    def _closest_ocean_points_shape(self, reader, lon, lat):
+        """The reference's branch for a shape reader (basemodel/__init__.py:960-968): the reader's own mask at the seeds, taken
+        as reader coordinates as there, and the land points moved to get_nearest_outside -- the nearest boundary vertex, found
+        with the device's exact k-d tree (odr_umesh_nearest) over the ring vertices; stored through float32, as the schedule is."""
+        land = np.asarray(reader.get_variables('land_binary_mask', x=lon, y=lat)['land_binary_mask'])
+        land_indices = np.where(land == 1)[0]
+        if len(land_indices):
+            def nearest(vx, vy, qx, qy):
+                tree = self.ctx.umesh(vx, vy)
+                try:
+                    return tree.nearest(qx, qy)
+                finally:
+                    tree.close()
+            x, y, _ = reader.get_nearest_outside(lon[land_indices], lat[land_indices], buffer_distance=reader._land_kdtree_buffer_distance,
+                                                 nearest=nearest)
+            lon[land_indices], lat[land_indices] = np.float32(x), np.float32(y)
+            logger.info('Moved %i out of %i points from land to water' % (len(land_indices), len(lon)))
         return lon, lat, land_indices
 
     # ------------------------------------------------------------------ loop pieces
@@ -866,7 +888,9 @@ class OpenDriftSimulation(Configurable):
             return
         if final:
             self.P.env_sample(['land_binary_mask'], _epoch(self.time))
-        precision = self.get_config('general:coastline_approximation_precision')
+            if any(getattr(b, 'shape', None) is not None for _, b in self._host_bindings()):      # polygons: behind the walk, as in the loop
+                self._sample_host_readers(['land_binary_mask'])
+        precision =self.get_config('general:coastline_approximation_precision')
         if precision:   # :726-746: coastline_crossing between the previous and the current position
             if getattr(self, '_landmask_sid', None) is None:
                 raise NotImplementedError('coastline_approximation_precision searches the global landmask: add '
@@ -995,13 +1019,15 @@ class OpenDriftSimulation(Configurable):
 
     def _host_bindings(self):
         """The bindings outside the device's own priority lists: readers evaluated on the host (user-defined ContinuousReaders)
-        and unstructured meshes, which the device samples in a launch of their own (odr_umesh_sample)."""
-        return [(n, b) for n, b in self.readers.items() if getattr(b, 'host_eval', False) or getattr(b, 'mesh', None) is not None]
+        and unstructured meshes and coastline polygons, which the device samples in a launch of their own (odr_umesh_sample,
+        odr_shape_sample)."""
+        return [(n, b) for n, b in self.readers.items() if getattr(b, 'host_eval', False) or getattr(b, 'mesh', None) is not None or
+                getattr(b, 'shape', None) is not None]
 
     def _unbound_off_list_readers(self):
         """Readers added but not bound yet (no device context so far) that will be among _host_bindings()."""
         return [n for n, (r, _) in self._readers_host.items() if n not in self.readers and n not in self.discarded_readers and
-                (getattr(r, 'device_kind', None) == 'umesh' or
+                (getattr(r, 'device_kind', None) in ('umesh', 'shape') or
                  (getattr(r, 'device_kind', None) is None and isinstance(r, ContinuousReader)))]
 
     def _ensemble_current(self):
@@ -1034,6 +1060,12 @@ class OpenDriftSimulation(Configurable):
             if getattr(b, 'mesh', None) is not None:      # the same rule in one launch: the positions stay on the device
                 try:
                     b.sample_mesh(P, vs, [self.priority_list[v][0] == name for v in vs], time)
+                except Exception as e:
+                    self._reader_failed(name, b, e)
+                continue
+            if getattr(b, 'shape', None) is not None:
+                try:
+                    b.sample_shape(P, self.priority_list[vs[0]][0] == name)
                 except Exception as e:
                     self._reader_failed(name, b, e)
                 continue
@@ -1497,6 +1529,9 @@ class OpenDriftSimulation(Configurable):
         if self._world > 1 and any(getattr(r, 'device_kind', None) == 'umesh' for r, _ in self._readers_host.values()):
             raise NotImplementedError('an UnstructuredReader in a sharded run: its time levels are not broadcast to the ranks '
                                       '(DESIGN.md section 8k)')
+        if self._world > 1 and any(getattr(r, 'device_kind', None) == 'shape' for r, _ in self._readers_host.values()):
+            raise NotImplementedError('a ShapeReader in a sharded run: the model samples it outside the launch a sharded step is '
+                                      '(DESIGN.md section 8l)')
         steps, out_every = self._time_arguments(time_step, steps, time_step_output, duration, end_time)
         # skip_if conditionals of required_variables (:1899-1906)
         for vn, var in list(self.required_variables.items()):

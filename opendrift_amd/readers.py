@@ -674,6 +674,153 @@ class UnstructuredReader(BaseReader):
         return out
 
 
+def _polygon_rings(geom):
+    """[[exterior, hole, ...], ...] of one entry of ShapeReader's `polygons`: an (n, 2) array, a pair (exterior, [holes]), or
+    anything with the __geo_interface__ / GeoJSON shape of a Polygon or MultiPolygon (a Feature is unwrapped)."""
+    g = getattr(geom, '__geo_interface__', geom)
+    if isinstance(g, dict):
+        if g.get('type') == 'Feature':
+            return _polygon_rings(g['geometry'])
+        if g.get('type') == 'Polygon':
+            return [[r for r in g['coordinates']]]
+        if g.get('type') == 'MultiPolygon':
+            return [[r for r in poly] for poly in g['coordinates']]
+        raise ValueError('a geometry of type %r: ShapeReader takes Polygon and MultiPolygon' % (g.get('type'),))
+    if isinstance(g, (tuple, list)) and len(g) == 2 and np.ndim(g[0]) == 2 and not np.isscalar(g[1]) and \
+            (len(g[1]) == 0 or np.ndim(g[1][0]) == 2):
+        return [[g[0]] + list(g[1])]
+    return [[g]]
+
+
+def _ring_edges(ring):
+    """(x1, y1, x2, y2) of the edges of one ring: closed if it is open, edges of zero length dropped."""
+    a = np.asarray(ring, dtype=np.float64)
+    if a.ndim != 2 or a.shape[1] < 2:
+        raise ValueError('a ring must be an (n, 2) array of vertices, got shape %s' % (a.shape,))
+    a = a[:, :2]
+    if not np.isfinite(a).all():
+        raise ValueError('a ring has a coordinate that is not finite')
+    if len(np.unique(a, axis=0)) < 3:
+        raise ValueError('a ring of fewer than three distinct vertices')
+    b = np.roll(a, -1, axis=0)
+    keep = (a[:, 0] != b[:, 0]) | (a[:, 1] != b[:, 1])
+    return a[keep, 0], a[keep, 1], b[keep, 0], b[keep, 1]
+
+
+class ShapeReader(ContinuousReader):
+    """reader_shape.Reader (readers/reader_shape.py): land_binary_mask from coastline polygons, given as arrays.  A point is on
+    land when any polygon contains it; a polygon contains a point inside its exterior ring and inside none of its holes;
+    polygons may overlap, an island in a lake is a polygon of its own.  invert=True: 1 - contains (:106-110).
+
+    polygons: a sequence of (n, 2) arrays (one ring), pairs (exterior, [hole, ...]) and objects or dicts with the
+    __geo_interface__ / GeoJSON shape of a Polygon or MultiPolygon (shapely geometries), mixed.  Rings may be closed or open, in
+    either orientation.  Coordinates are in the CRS `proj4_str`.
+
+    On the device (`device_kind = 'shape'`) the whole lookup of a get_environment call -- projection, coverage box, an exact
+    crossing-number test behind a uniform grid, invert, merge by priority -- is one launch (odr_shape_sample).
+    `get_variables` answers on the host with the same rule over all edges.  A point exactly on a ring is outside for shapely;
+    here it falls on whichever side the half-open crossing rule puts it.  `from_shpfiles` is not built."""
+    device_kind = 'shape'
+    name = 'shape'
+    variables = ['land_binary_mask']
+    always_valid = True
+
+    def __init__(self, polygons, proj4_str='+proj=lonlat +ellps=WGS84', invert=False, land_buffer_distance=None):
+        self._land_kdtree = None
+        self._land_kdtree_buffer_distance = land_buffer_distance
+        self.invert = bool(invert)
+        self.proj4 = proj4_str
+        pd = projection.parse_proj4(proj4_str)        # NotImplementedError: not on the device path
+        if pd.get('kind') == 'ob_tran':
+            raise NotImplementedError('polygons on a rotated pole (+proj=ob_tran) are not on the device path')
+        self.polys = [rings for g in list(polygons) for rings in _polygon_rings(g)]
+        if len(self.polys) == 0:
+            raise AssertionError('no geometries loaded')      # (the reference's assert, reader_shape.py:97)
+        parts, ids = [], []
+        for k, rings in enumerate(self.polys):
+            for ring in rings:
+                e = _ring_edges(ring)
+                parts.append(e)
+                ids.append(np.full(len(e[0]), k, np.int32))
+        self.x1, self.y1, self.x2, self.y2 = (np.ascontiguousarray(np.concatenate([p[k] for p in parts])) for k in range(4))
+        self.poly = np.ascontiguousarray(np.concatenate(ids))
+        self.n_polygons = len(self.polys)
+        super().__init__()
+        xmin, xmax, ymin, ymax = float(self.x1.min()), float(self.x1.max()), float(self.y1.min()), float(self.y1.max())
+        self.box = (xmin, xmax, ymin, ymax)      # of the rings, in their own coordinates: the coverage the device tests
+        if pd.get('kind', 'latlong') == 'latlong':      # reader_shape.py:102-104: the bounds through lonlat2xy (the identity here)
+            (self.xmin, self.ymin), (self.xmax, self.ymax) = (float(v) for v in self.lonlat2xy(xmin, ymin)), \
+                (float(v) for v in self.lonlat2xy(xmax, ymax))
+        else:      # (the reference hands projected bounds to lonlat2xy, which gives no box at all: the rings' own box here)
+            self.xmin, self.xmax, self.ymin, self.ymax = self.box
+
+    def modulate_longitude(self, lon):      # variables.py:259-280, for geographic polygons
+        lon = np.asarray(lon, dtype=np.float64)
+        return np.mod(lon + 180, 360) - 180 if self.box[0] < 0 else np.mod(lon, 360)
+
+    def contains(self, x, y, chunk=1 << 14):
+        """The definition, over all edges (csrc/odr_shape.hip.h): per polygon the parity of its edges with (y1 > py) != (y2 > py)
+        and x1 + (py - y1) * (x2 - x1) / (y2 - y1) < px; the OR over the polygons.  bool per point."""
+        x, y = np.atleast_1d(np.asarray(x, dtype=np.float64)).ravel(), np.atleast_1d(np.asarray(y, dtype=np.float64)).ravel()
+        out = np.zeros(len(x), bool)
+        first = np.r_[0, np.flatnonzero(np.diff(self.poly)) + 1]      # the edges are grouped by polygon
+        step = max(1, chunk * 64 // max(len(self.x1), 1))
+        with np.errstate(divide='ignore', invalid='ignore'):
+            for o in range(0, len(x), step):
+                px, py = x[o:o + step, None], y[o:o + step, None]
+                cross = ((self.y1 > py) != (self.y2 > py)) & (self.x1 + (py - self.y1) * (self.x2 - self.x1) / (self.y2 - self.y1) < px)
+                out[o:o + step] = (np.add.reduceat(cross, first, axis=1) & 1).any(axis=1)
+        return out
+
+    def _on_land(self, x, y):
+        c = self.contains(x, y)
+        return 1 - c if self.invert else c
+
+    def get_variables(self, requested_variables, time=None, x=None, y=None, z=None):
+        """{'land_binary_mask': 1 / 0 per position (x, y) in the reader's coordinates} -- for every position, covered or not (the
+        caller masks, as the reference's does)."""
+        if isinstance(requested_variables, str):
+            requested_variables = [requested_variables]
+        for v in requested_variables:
+            if v not in self.variables:
+                raise ValueError('Variable not available: %s\nAvailable parameters are: %s' % (v, self.variables))
+        shape = np.shape(x)
+        return {'x': x, 'y': y, 'land_binary_mask': np.reshape(self._on_land(x, y), shape)}
+
+    def mask(self, lon, lat):
+        """What the device launch gives an element with an empty slot, on the host: float32 1 / 0, NaN outside the box."""
+        lon, lat = np.atleast_1d(np.asarray(lon, dtype=np.float64)), np.atleast_1d(np.asarray(lat, dtype=np.float64))
+        geographic = projection.parse_proj4(self.proj4).get('kind', 'latlong') == 'latlong'
+        x, y = (self.modulate_longitude(lon), lat) if geographic else self.lonlat2xy(lon, lat)
+        x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+        with np.errstate(invalid='ignore'):
+            ok = np.isfinite(x + y) & (x >= self.box[0]) & (x <= self.box[1]) & (y >= self.box[2]) & (y <= self.box[3])
+        out = np.full(len(lon), np.nan, np.float32)
+        if ok.any():
+            out[ok] = self._on_land(x[ok], y[ok])
+        return out
+
+    def boundary_vertices(self):
+        """(x, y) of the vertices of all rings (reader_shape.py `unwrap` of the polygons' boundaries)."""
+        return self.x1, self.y1
+
+    def get_nearest_outside(self, x, y, buffer_distance=None, nearest=None):
+        """reader_shape.py:132-159 for buffer_distance None or 0: (x, y, distance) of the boundary vertex nearest to each point.
+        nearest: a function (vx, vy, qx, qy) -> indices (the model passes the device's exact k-d tree); default scipy's cKDTree."""
+        if buffer_distance not in (None, 0):
+            raise NotImplementedError('get_nearest_outside with a buffer distance of %r: polygon offsetting is not built' % (buffer_distance,))
+        x, y = np.atleast_1d(np.asarray(x, dtype=np.float64)), np.atleast_1d(np.asarray(y, dtype=np.float64))
+        vx, vy = self.boundary_vertices()
+        if nearest is None:
+            if self._land_kdtree is None:
+                from scipy.spatial import cKDTree
+                self._land_kdtree = cKDTree(np.c_[vx, vy])
+            ind = self._land_kdtree.query(np.c_[x, y])[1]
+        else:
+            ind = np.asarray(nearest(vx, vy, x, y), dtype=np.int64)
+        return vx[ind], vy[ind], np.sqrt((vx[ind] - x) ** 2 + (vy[ind] - y) ** 2)
+
+
 def _dev(a):
     """a block array as Context.upload_block_device wants it: the device pointer of a CUDA tensor, else the host array"""
     return int(a.data_ptr()) if hasattr(a, 'is_cuda') and a.is_cuda else a
@@ -783,6 +930,7 @@ class DeviceReaderBinding:
         self._dist_pre = {}            # sharded run: time index -> (tensors, works) of a level whose broadcast is under way
         self._ahead, self._ahead_last = None, None   # sharded run, rank 0: the next level read on a worker thread (ReadAhead)
         self.mesh = None               # device.UMesh of an UnstructuredReader
+        self.shape = None              # device.Shape of a ShapeReader
         kind = getattr(reader, 'device_kind', None)
         # a ContinuousReader the device has no closed form for (a user's analytic or point-wise reader,
         # basereader/continuous.py:20-46): evaluated on the host at the element positions, values uploaded
@@ -805,9 +953,14 @@ class DeviceReaderBinding:
             self.mesh = ctx.umesh(reader.x, reader.y, reader.xc, reader.yc, proj=projection.parse_proj4(reader.proj4),
                                   **{k: getattr(reader, k) for k in ('siglay', 'siglev', 'siglay_center', 'siglev_center', 'h', 'h_center')})
             self.mesh_slots = {}     # time index -> slot of the mesh (at most three resident)
+        elif kind == 'shape':
+            # coastline polygons: as a mesh, sampled in a launch of its own behind the priority-list walk (sample_shape)
+            self.sid = None
+            self.shape = ctx.shape(reader.x1, reader.y1, reader.x2, reader.y2, reader.poly, reader.n_polygons,
+                                   proj=projection.parse_proj4(reader.proj4), invert=reader.invert)
         else:
             self.sid = None  # created with the first block (the grid comes with it)
-        if kind and kind != 'umesh' and reader.start_time is not None:
+        if kind and kind not in ('umesh', 'shape') and reader.start_time is not None:
             ctx.set_time_coverage(self.sid, _epoch(reader.start_time), _epoch(reader.end_time), reader.always_valid)
 
     def _static_ids(self):
@@ -1037,6 +1190,11 @@ class DeviceReaderBinding:
         for o in range(0, len(ordered), _abi.UMESH_MAX_VARIABLES):
             vs = ordered[o:o + _abi.UMESH_MAX_VARIABLES]
             P.umesh_sample(self.mesh, self.mesh_slots[k], vs, [flag[v] for v in vs])
+
+    def sample_shape(self, P, first):
+        """The polygons' land_binary_mask for the particle set P, merged into its environment slot by priority (first: the reader
+        heads the variable's list) -- on the device, one launch (odr_shape_sample).  The reader is valid at every time."""
+        P.shape_sample(self.shape, first)
 
     def _read_and_broadcast(self, k, x, y, async_op):
         """Sharded run: rank 0 reads time level k, every rank receives it.  A reader failure on rank 0 reaches every rank as
