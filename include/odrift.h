@@ -79,7 +79,10 @@ enum { ODR_PROJ_LATLONG = 0, ODR_PROJ_STERE_EQUIT_SPHERE = 1, ODR_PROJ_STERE_POL
        ODR_PROJ_STERE_OBLIQUE = 8 /* +proj=stere with lat_0 not a pole (oblique, equatorial), sphere or ellipsoid, +k_0: Snyder ch. 21 */,
        ODR_PROJ_OB_TRAN = 9 /* +proj=ob_tran +o_proj=longlat: the rotated pole; lat1_deg = o_lat_p, lat2_deg = o_lon_p, lon0_deg = lon_0;
                                reader coordinates are rotated longitude / latitude in DEGREES (variables.py:117-123,136-138); vector
-                               pairs are rotated by the WGS84 azimuth of the 0.1-degree line along +y (variables.py:80-97) */ };
+                               pairs are rotated by the WGS84 azimuth of the 0.1-degree line along +y (variables.py:80-97) */,
+       ODR_PROJ_MOLL = 11 /* +proj=moll +lon_0 +x_0 +y_0 on the sphere of radius a (PROJ's moll; es is ignored): Snyder ch. 31.  A map
+                             grid only: the entry points of "projected density and concentration maps" below take it, every other
+                             one refuses it (10 is taken inside the library) */ };
 typedef struct {
   int32_t kind;
   double a, es;                  /* semi-major axis, eccentricity squared */
@@ -868,6 +871,59 @@ int odr_density_map(odr_ctx *ctx, int64_t n_trajectories, int32_t n_times, const
                     int32_t n_lat_edges, const double *lat_edges, double *H, double *H_submerged, double *H_stranded);
 /* device time [ms] of the kernel launches of this process's last odr_density_map, summed over its slabs (tools/bench_density.py) */
 int odr_density_last_kernel_ms(odr_ctx *ctx, float *ms);
+
+/* ---------------------------------------------------------------- projected density and concentration maps
+ * proj in all of these: the projection the map grid is regular in (NULL: longitude / latitude) -- ODR_PROJ_LATLONG, the two
+ * ODR_PROJ_STERE_*, ODR_PROJ_STERE_OBLIQUE, ODR_PROJ_MERC, ODR_PROJ_LCC, ODR_PROJ_TMERC, ODR_PROJ_LAEA and ODR_PROJ_MOLL; ODR_PROJ_OB_TRAN,
+ * ODR_PROJ_CURVILINEAR and unknown kinds are ODR_ERR_INVALID.  lon, lat, z, status, specie, weight: [trajectory][time] float32, each
+ * in host OR device memory (device arrays must be complete: no stream is waited for); host arrays are uploaded in slabs of whole
+ * trajectories within a byte budget (256 MiB; the environment variable ODR_CONC_SLAB_BYTES overrides it).  Every call is synchronous
+ * and checks all of its arguments before anything is launched (csrc/odr_conc.hip.h).
+ *
+ * odr_density_map_proj: OpenDriftSimulation.get_density_array_proj (models/basemodel/__init__.py:4148-4245) for GIVEN edges in
+ * projection units.  (x, y) = proj(lon, lat) in float64 from the float32 positions; the bin is np.histogram2d's on the edge arrays
+ * themselves, as in odr_density_map.  The reference takes an entry out of a map by MOVING it to (outsidex, outsidey) = 1.5 *
+ * (max(x_array), max(y_array)): out of H when z < 0, out of H_submerged when z >= 0, out of H_stranded when status != stranded_code
+ * (a NaN z stays in both, a NaN status is moved).  outside_bin: the bin ix * (n_y_edges - 1) + iy of that point when it lies INSIDE
+ * the grid (both maxima negative) -- moved entries are then counted there, whatever their own position -- or -1.  weight NULL:
+ * counts (32-bit integer adds, exact), else float64 sums of the float32 weights (atomic adds: the last bits depend on the order of
+ * arrival); a NaN weight of a moved entry makes outside_bin NaN, as in NumPy.  stranded_code < 0: no such category, H_stranded may
+ * be NULL and is zero-filled if given.  H, H_submerged, H_stranded: host, float64 [time][x_bin][y_bin].
+ * ODR_ERR_INVALID: fewer than two edges, edges not finite or not strictly increasing, more than 2^28 bins per output time, the
+ * three maps larger than 8 GiB on the device (3 * n_times * bins * 4 bytes, 8 bytes with weights), outside_bin outside -1 .. bins - 1,
+ * n_trajectories >= 2^32, a refused projection, a NULL pointer other than proj, weight and (stranded_code < 0) H_stranded. */
+int odr_density_map_proj(odr_ctx *ctx, int64_t n_trajectories, int32_t n_times, const float *lon, const float *lat, const float *z,
+                         const float *status, const float *weight, int32_t stranded_code, const odr_proj_desc *proj, int32_t n_x_edges,
+                         const double *x_edges, int32_t n_y_edges, const double *y_edges, int64_t outside_bin, double *H,
+                         double *H_submerged, double *H_stranded);
+/* odr_species_layer_map: RadionuclideDrift.get_radionuclide_density_array (models/radionuclides.py:1425-1492) for given edges and
+ * layer bounds, counts only: an entry counts in H[time][sp][zi][x_bin][y_bin] iff specie == sp (sp in 0 .. n_species - 1),
+ * z_array[zi] < z <= z_array[zi + 1] compared in float64, and its projected position has a bin; NaN z or specie: nowhere.  Nothing
+ * is moved.  z_array[n_z]: host, strictly increasing, finite, at most 256 values.  H: host, float64 (32-bit integer adds on the
+ * device, widened at the end).
+ * ODR_ERR_INVALID: as above for edges and projection; z_array not increasing or not finite; more than 2^28 bins per output time,
+ * species and layers included; the histogram larger than 8 GiB on the device (n_times * bins * 4 bytes); n_species < 1; a NULL
+ * pointer other than proj. */
+int odr_species_layer_map(odr_ctx *ctx, int64_t n_trajectories, int32_t n_times, const float *lon, const float *lat, const float *z,
+                          const float *specie, const odr_proj_desc *proj, int32_t n_x_edges, const double *x_edges, int32_t n_y_edges,
+                          const double *y_edges, int32_t n_z, const double *z_array, int32_t n_species, double *H);
+/* device time [ms] of the kernel launches of this process's last odr_density_map_proj or odr_species_layer_map, summed over its
+ * slabs (tools/bench_concentration.py) */
+int odr_conc_last_kernel_ms(odr_ctx *ctx, float *ms);
+/* odr_proj_extent: extent4 = (min x, max x, min y, max y) of (x, y) = proj(lon, lat) over the n positions whose projected
+ * coordinates are both finite -- what x.min() ... y.max() of the reference give for a result without NaN (+inf, -inf, +inf, -inf when
+ * no position is finite).  A reduction on the device: per-workgroup partial records, finished on the host; no float atomics. */
+int odr_proj_extent(odr_ctx *ctx, const odr_proj_desc *proj, int64_t n, const float *lon, const float *lat, double *extent4);
+/* odr_proj_grid_lonlat: lon, lat = proj(X, Y, inverse=True) of Y, X = np.meshgrid(ys, xs): host, float64 [nx][ny] degrees (NaN
+ * outside a projection's range).  xs[nx], ys[ny]: host, finite. */
+int odr_proj_grid_lonlat(odr_ctx *ctx, const odr_proj_desc *proj, int32_t nx, const double *xs, int32_t ny, const double *ys, double *lon,
+                         double *lat);
+/* odr_box_smooth: RadionuclideDrift.horizontal_smooth (models/radionuclides.py:1518-1551) of n_planes planes a[n0][n1], host
+ * float64: every value is truncated to an integer, the plane padded with n zeros all round, the (2 n + 1)^2 window summed and the sum
+ * divided by (2 n + 1)^2 in float64 -- integer sums, so the bits are the reference's.  n == 0 copies.  out may be a.
+ * ODR_ERR_INVALID: a value that is not finite, integer parts of a plane that sum to 2^53 or more, more than 2^28 cells per plane,
+ * n < 0 or n >= 2^26, a NULL pointer. */
+int odr_box_smooth(odr_ctx *ctx, int64_t n_planes, int32_t n0, int32_t n1, int32_t n, const double *a, double *out);
 
 /* ---------------------------------------------------------------- FTLE maps
  * physics_methods.ftle (models/physics_methods.py:458-484) of the displacements that OpenDriftSimulation.calculate_ftle

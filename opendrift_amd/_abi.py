@@ -30,6 +30,7 @@ VARIABLE_NAMES = {v: k for k, v in VARIABLES.items()}
 PROJ_LATLONG, PROJ_STERE_EQUIT_SPHERE, PROJ_STERE_POLAR = 0, 1, 2
 PROJ_MERC, PROJ_LCC = 4, 5
 PROJ_TMERC, PROJ_LAEA, PROJ_STERE_OBLIQUE, PROJ_OB_TRAN = 6, 7, 8, 9
+PROJ_MOLL = 11     # ODR_PROJ_MOLL: the map grids of odr_density_map_proj / odr_species_layer_map only
 SCHEME = {'euler': 0, 'runge-kutta': 1, 'runge-kutta4': 2}
 RNG_DEVICE, RNG_HOST = 0, 1
 STAGE_MATH = {'exact': 0, 'fast': 1}     # odr_ctx_set_stage_math
@@ -227,6 +228,12 @@ _SIGNATURES = {
     'odr_history_minmax': [_vp, _vp, C.c_int32, _dp, _dp],
     'odr_density_map': [_vp, C.c_int64, C.c_int32] + [_vp] * 5 + [C.c_int32, C.c_int32, _dp, C.c_int32, _dp, _dp, _dp, _dp],
     'odr_density_last_kernel_ms': [_vp, _fp],
+    'odr_density_map_proj': [_vp, C.c_int64, C.c_int32] + [_vp] * 5 + [C.c_int32, _P(ProjDesc), C.c_int32, _dp, C.c_int32, _dp, C.c_int64, _dp, _dp, _dp],
+    'odr_species_layer_map': [_vp, C.c_int64, C.c_int32] + [_vp] * 4 + [_P(ProjDesc), C.c_int32, _dp, C.c_int32, _dp, C.c_int32, _dp, C.c_int32, _dp],
+    'odr_conc_last_kernel_ms': [_vp, _fp],
+    'odr_proj_extent': [_vp, _P(ProjDesc), C.c_int64, _vp, _vp, _dp],
+    'odr_proj_grid_lonlat': [_vp, _P(ProjDesc), C.c_int32, _dp, C.c_int32, _dp, _dp, _dp],
+    'odr_box_smooth': [_vp, C.c_int64, C.c_int32, C.c_int32, C.c_int32, _dp, _dp],
     'odr_ftle_map': [_vp, _P(ProjDesc), C.c_int32, C.c_int32, _dp, _dp, C.c_double, C.c_double, _vp, _vp, _fp, _dp],
     'odr_ftle_last_kernel_ms': [_vp, _fp],
     'odr_geod_inverse': [_vp, C.c_int64, _dp, _dp, _dp, _dp, _dp, _dp, _dp],

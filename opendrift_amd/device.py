@@ -50,14 +50,17 @@ def _i(a, n=None):
     return a, a.ctypes.data_as(_ip)
 
 
-def proj_desc(proj):
+def proj_desc(proj, map_grid=False):
     """dict(kind='latlong'|'stere_equit_sphere'|'stere_polar'|'merc'|'lcc'|'tmerc'|'laea'|'stere_oblique'|'ob_tran', a, rf|es, lat0,
-    lon0, lat_ts, k0, x0, y0, lat1, lat2) -- projection.parse_proj4's output (ob_tran: lat1 = o_lat_p, lat2 = o_lon_p)"""
+    lon0, lat_ts, k0, x0, y0, lat1, lat2) -- projection.parse_proj4's output (ob_tran: lat1 = o_lat_p, lat2 = o_lon_p).
+    map_grid: the projection of a map grid (Context.density_map_proj ...), which may be 'moll' as well; no reader can."""
     if proj is None or proj.get('kind', 'latlong') == 'latlong':
         return None
+    if proj['kind'] == 'moll' and not map_grid:
+        raise NotImplementedError('+proj=moll serves map grids only (get_density_array_proj, get_radionuclide_density_array)')
     kind = {'stere_equit_sphere': _abi.PROJ_STERE_EQUIT_SPHERE, 'stere_polar': _abi.PROJ_STERE_POLAR,
             'merc': _abi.PROJ_MERC, 'lcc': _abi.PROJ_LCC, 'tmerc': _abi.PROJ_TMERC, 'laea': _abi.PROJ_LAEA,
-            'stere_oblique': _abi.PROJ_STERE_OBLIQUE, 'ob_tran': _abi.PROJ_OB_TRAN}[proj['kind']]
+            'stere_oblique': _abi.PROJ_STERE_OBLIQUE, 'ob_tran': _abi.PROJ_OB_TRAN, 'moll': _abi.PROJ_MOLL}[proj['kind']]
     if 'es' in proj:
         es = proj['es']
     else:
@@ -67,6 +70,13 @@ def proj_desc(proj):
     return _abi.ProjDesc(kind, proj.get('a', 6378137.0), es, proj.get('lat0', 0.0), proj.get('lon0', 0.0),
                          proj.get('lat_ts', 90.0), proj.get('k0', 1.0), proj.get('x0', 0.0), proj.get('y0', 0.0),
                          proj.get('lat1', 0.0), proj.get('lat2', proj.get('lat1', 0.0)))
+
+
+def _grid_proj(proj):
+    """The descriptor argument of the map-grid entry points: projection.parse_proj4's dict, an _abi.ProjDesc, or None (latlong)."""
+    if not isinstance(proj, _abi.ProjDesc):
+        proj = proj_desc(proj, map_grid=True)
+    return proj, (None if proj is None else C.byref(proj))
 
 
 class ContentIds:
@@ -451,6 +461,98 @@ class Context:
         ms = C.c_float()
         check(self.lib.odr_density_last_kernel_ms(self.h, C.byref(ms)))
         return ms.value
+
+    @staticmethod
+    def _traj_time_arrays(what, arrays, shape):
+        """[trajectory, time] float32 arrays or device addresses (int) -> (arrays kept alive, pointers, shape)"""
+        keep, ptrs = [], []
+        for a in arrays:
+            if isinstance(a, (int, np.integer)):
+                if shape is None:
+                    raise ValueError('device addresses need shape=(n_trajectories, n_times)')
+                ptrs.append(C.c_void_p(int(a)))
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.ndim != 2 or (shape is not None and a.shape != tuple(shape)):
+                raise ValueError('%s: an input of shape %s, not [trajectory, time] %s' % (what, a.shape, shape or ''))
+            shape = a.shape
+            keep.append(a)
+            ptrs.append(C.c_void_p(a.ctypes.data))
+        return keep, ptrs, (int(shape[0]), int(shape[1]))
+
+    def density_map_proj(self, proj, lon, lat, z, status, x_edges, y_edges, weight=None, stranded_code=-1, outside_bin=-1, shape=None):
+        """The three histograms per output time of get_density_array_proj for given edges in the units of `proj`
+        (odr_density_map_proj): (H, H_submerged, H_stranded), float64 [time, x_bin, y_bin].  proj: projection.parse_proj4's dict
+        (None: latlong) or an _abi.ProjDesc.  outside_bin: ix * (len(y_edges) - 1) + iy of the point the reference moves removed
+        entries to when that lies inside the grid, else -1.  Arrays as in density_map."""
+        keep, ptrs, (ntraj, nt) = self._traj_time_arrays('density_map_proj', [lon, lat, z, status] + ([weight] if weight is not None else []), shape)
+        if weight is None:
+            ptrs.append(None)
+        desc, pd = _grid_proj(proj)
+        xe, px = _d(np.asarray(x_edges, dtype=np.float64).ravel())
+        ye, py = _d(np.asarray(y_edges, dtype=np.float64).ravel())
+        out = [np.zeros((nt, max(len(xe) - 1, 0), max(len(ye) - 1, 0))) for _ in range(3)]
+        check(self.lib.odr_density_map_proj(self.h, ntraj, nt, *ptrs, int(stranded_code), pd, len(xe), px, len(ye), py, int(outside_bin),
+                                            *(o.ctypes.data_as(_dp) for o in out)))
+        return tuple(out)
+
+    def species_layer_map(self, proj, lon, lat, z, specie, x_edges, y_edges, z_array, n_species, shape=None):
+        """get_radionuclide_density_array's counts for given edges and layer bounds (odr_species_layer_map): float64
+        [time, species, layer, x_bin, y_bin].  Arrays as in density_map."""
+        keep, ptrs, (ntraj, nt) = self._traj_time_arrays('species_layer_map', [lon, lat, z, specie], shape)
+        desc, pd = _grid_proj(proj)
+        xe, px = _d(np.asarray(x_edges, dtype=np.float64).ravel())
+        ye, py = _d(np.asarray(y_edges, dtype=np.float64).ravel())
+        zb, pz = _d(np.asarray(z_array, dtype=np.float64).ravel())
+        out = np.zeros((nt, max(int(n_species), 0), max(len(zb) - 1, 0), max(len(xe) - 1, 0), max(len(ye) - 1, 0)))
+        check(self.lib.odr_species_layer_map(self.h, ntraj, nt, *ptrs, pd, len(xe), px, len(ye), py, len(zb), pz, int(n_species),
+                                             out.ctypes.data_as(_dp)))
+        return out
+
+    def conc_last_kernel_ms(self):
+        ms = C.c_float()
+        check(self.lib.odr_conc_last_kernel_ms(self.h, C.byref(ms)))
+        return ms.value
+
+    def proj_extent(self, proj, lon, lat, n=None):
+        """(min x, max x, min y, max y) of proj(lon, lat) over the positions whose projected coordinates are finite
+        (odr_proj_extent).  lon, lat: float32 arrays of any shape, or device addresses (int) with n entries."""
+        ptrs, keep = [], []
+        for a in (lon, lat):
+            if isinstance(a, (int, np.integer)):
+                if n is None:
+                    raise ValueError('device addresses need n')
+                ptrs.append(C.c_void_p(int(a)))
+                continue
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if n is not None and a.size != n:
+                raise ValueError('proj_extent: %d and %d positions' % (n, a.size))
+            n = a.size
+            keep.append(a)
+            ptrs.append(C.c_void_p(a.ctypes.data))
+        desc, pd = _grid_proj(proj)
+        out = np.empty(4)
+        check(self.lib.odr_proj_extent(self.h, pd, int(n), *ptrs, out.ctypes.data_as(_dp)))
+        return tuple(float(v) for v in out)
+
+    def proj_grid_lonlat(self, proj, xs, ys):
+        """proj(X, Y, inverse=True) of Y, X = np.meshgrid(ys, xs) (odr_proj_grid_lonlat): lon, lat float64 [len(xs), len(ys)]."""
+        xs, px = _d(np.asarray(xs, dtype=np.float64).ravel())
+        ys, py = _d(np.asarray(ys, dtype=np.float64).ravel())
+        desc, pd = _grid_proj(proj)
+        lon, lat = np.empty((len(xs), len(ys))), np.empty((len(xs), len(ys)))
+        check(self.lib.odr_proj_grid_lonlat(self.h, pd, len(xs), px, len(ys), py, lon.ctypes.data_as(_dp), lat.ctypes.data_as(_dp)))
+        return lon, lat
+
+    def box_smooth(self, a, n):
+        """horizontal_smooth of the last two dimensions of `a` (odr_box_smooth): float64, the shape of `a`."""
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.ndim < 2:
+            raise ValueError('box_smooth: %d-dimensional input' % a.ndim)
+        out = np.empty_like(a)
+        planes = int(np.prod(a.shape[:-2], dtype=np.int64))
+        check(self.lib.odr_box_smooth(self.h, planes, a.shape[-2], a.shape[-1], int(n), a.ctypes.data_as(_dp), out.ctypes.data_as(_dp)))
+        return out
 
     def ftle_map(self, proj, xs, ys, delta, duration_seconds, lon, lat, displacement=False):
         """physics_methods.ftle of the displacements of a grid of elements (odr_ftle_map): float32 [ny, nx], and with

@@ -1832,6 +1832,66 @@ class OpenDriftSimulation(Configurable):
             weight=None if weight is None else result[weight], stranded_code=strandnum)
         return H, H_submerged, H_stranded, lon_array, lat_array
 
+    def _map_grid(self, what, pixelsize_m, density_proj, default_proj4, corners):
+        """The grid of get_density_array_proj / get_radionuclide_density_array: (projection dict, x_array, y_array).  With all four
+        corners the edges are NumPy arithmetic on the projected corners; without, the extremes of the projected positions are
+        reduced on the device (odr_proj_extent) over the entries whose projection is finite."""
+        params = map_grid_projection(density_proj, default_proj4)
+        result = self.result
+        if corners[0] is not None:
+            if any(c is None for c in corners):
+                raise ValueError('%s: llcrnrlon, llcrnrlat, urcrnrlon and urcrnrlat go together' % what)
+            proj = projection.Proj.from_params(params)
+            llx, lly = (float(v) for v in proj(float(corners[0]), float(corners[1])))
+            urx, ury = (float(v) for v in proj(float(corners[2]), float(corners[3])))
+        else:
+            if self._world > 1:
+                raise NotImplementedError('%s of a sharded run needs llcrnrlon, llcrnrlat, urcrnrlon and urcrnrlat, the same on every '
+                                          'rank: the edges the reference derives come from the elements of all ranks' % what)
+            xmin, xmax, ymin, ymax = self.ctx.proj_extent(params, result['lon'], result['lat'])
+            if not np.isfinite([xmin, xmax, ymin, ymax]).all():
+                raise ValueError('%s: no position of the result has a finite projection' % what)
+            llx, lly, urx, ury = xmin - pixelsize_m, ymin - pixelsize_m, xmax + pixelsize_m, ymax + pixelsize_m
+        return params, np.arange(llx, urx, pixelsize_m), np.arange(lly, ury, pixelsize_m)
+
+    def get_density_array_proj(self, pixelsize_m, density_proj=None, llcrnrlon=None, llcrnrlat=None, urcrnrlon=None, urcrnrlat=None,
+                               weight=None):
+        """basemodel/__init__.py:4148-4245: (H, H_submerged, H_stranded, lon_array, lat_array) on a grid that is regular, with
+        spacing pixelsize_m, in density_proj -- a proj4 string, a projection.Proj, or anything with `.srs` / `definition_string()`
+        that projection.parse_proj4 understands (not ob_tran).  None is the reference's '+proj=longlat +a=6371229 +no_defs' (its
+        second assignment, :4172, wins): pixelsize_m is then in DEGREES.  H*: float64 [time, x_bin, y_bin]; lon_array, lat_array:
+        the inverse projection of np.meshgrid(y_array, x_array), float64 [len(x_array), len(y_array)].
+
+        The reference's quirk is kept: an entry a map does not want is MOVED to 1.5 * (max(x_array), max(y_array)), which is outside
+        the grid when both maxima are positive and INSIDE it when both are negative -- those entries are then counted in that bin.
+
+        Without the four corners the reference takes x.min() - pixelsize_m ... x.max() + pixelsize_m of all projected positions,
+        which works with pyproj only when no position is NaN.  Here the extremes are taken on the device over the entries whose
+        projection is finite: the same edges for a result without NaN, and edges where the reference has none otherwise.
+        Projection, binning and lon_array / lat_array run on the device (odr_density_map_proj).  A sharded run needs
+        the corners, the same on every rank, and returns each rank's share of every map."""
+        result = getattr(self, 'result', None)
+        if result is None:
+            raise RuntimeError('get_density_array_proj needs the result of run()')
+        for name in ('lon', 'lat', 'z', 'status') + ((weight, ) if weight is not None else ()):
+            if name not in result:
+                raise KeyError('%s is not in self.result (export_variables)' % name)
+        params, x_array, y_array = self._map_grid('get_density_array_proj', pixelsize_m, density_proj, '+proj=longlat +a=6371229 +no_defs',
+                                                  (llcrnrlon, llcrnrlat, urcrnrlon, urcrnrlat))
+        if len(x_array) < 2 or len(y_array) < 2:
+            raise ValueError('get_density_array_proj: %d x %d edges' % (len(x_array), len(y_array)))
+        ix, iy = edge_bin(max(x_array) * 1.5, x_array), edge_bin(max(y_array) * 1.5, y_array)      # (outsidex, outsidey), :4186
+        outside = ix * (len(y_array) - 1) + iy if ix >= 0 and iy >= 0 else -1
+        try:
+            strandnum = self.status_categories.index('stranded')
+        except ValueError:
+            strandnum = -1
+        H, H_submerged, H_stranded = self.ctx.density_map_proj(
+            params, result['lon'], result['lat'], result['z'], result['status'], x_array, y_array,
+            weight=None if weight is None else result[weight], stranded_code=strandnum, outside_bin=outside)
+        lon_array, lat_array = self.ctx.proj_grid_lonlat(params, x_array, y_array)
+        return H, H_submerged, H_stranded, lon_array, lat_array
+
     def get_residence_time(self, pixelsize_m):
         """basemodel/__init__.py:4247-4251: (H summed over the output times, lon_array, lat_array)."""
         H, H_sub, H_str, lon_array, lat_array = self.get_density_array(pixelsize_m)
@@ -2157,6 +2217,35 @@ def density_edges(lon, lat, pixelsize_m):
     lat_array = np.arange(lat_lo - dlat, lat_hi + dlat, dlat)
     lon_array = np.arange(lon_lo - dlat, lon_hi + dlon, dlon)
     return lon_array, lat_array
+
+
+def map_grid_projection(density_proj, default_proj4):
+    """projection.parse_proj4's dict of the density_proj argument of get_density_array_proj / get_radionuclide_density_array: a
+    proj4 string, a projection.Proj, or an object with `.srs` or `definition_string()` (pyproj.Proj); None: default_proj4.  The
+    rotated pole and anything parse_proj4 does not know are refused."""
+    if density_proj is None:
+        density_proj = default_proj4
+    if isinstance(density_proj, projection.Proj):
+        params = density_proj.params
+    else:
+        if not isinstance(density_proj, str):
+            if hasattr(density_proj, 'srs'):
+                density_proj = density_proj.srs
+            elif hasattr(density_proj, 'definition_string'):
+                density_proj = density_proj.definition_string()
+            else:
+                raise TypeError('density_proj: a proj4 string or an object with .srs / definition_string(), not %r' % type(density_proj))
+        params = projection.parse_proj4(str(density_proj))
+    if params['kind'] == 'ob_tran':
+        raise NotImplementedError('density_proj: a rotated pole (+proj=ob_tran) has no grid regular in metres')
+    return params
+
+
+def edge_bin(v, edges):
+    """np.histogram2d's bin of the scalar v on `edges` (a value equal to the last edge belongs to the last bin), or -1."""
+    if not (v >= edges[0] and v <= edges[-1]):
+        return -1
+    return min(int(np.searchsorted(edges, v, side='right')) - 1, len(edges) - 2)
 
 
 def last_valid(a):

@@ -5,7 +5,8 @@ Stands in for pyproj.Proj as used by readers (basereader/__init__.py:119-137,
 variables.py:111-143) for the projections on the path: latlong, stereographic (Snyder, USGS PP 1395, ch. 21: polar,
 equatorial and oblique aspects), Mercator (ch. 7), Lambert conformal conic (ch. 15), transverse Mercator / UTM (Krueger's
 series to order 6 in the third flattening: Karney 2011), Lambert azimuthal equal-area (ch. 24), sphere or ellipsoid, and the
-rotated pole (+proj=ob_tran +o_proj=longlat, Snyder 5-7..5-10b).
+rotated pole (+proj=ob_tran +o_proj=longlat, Snyder 5-7..5-10b).  Mollweide (ch. 31, PROJ's moll: the sphere of radius a) serves map
+grids only (get_density_array_proj, get_radionuclide_density_array; csrc/odr_conc.hip.h): no reader can have it.
 """
 import re
 
@@ -29,9 +30,9 @@ def parse_proj4(proj4):
             raise NotImplementedError('ob_tran: only the +o_lat_p / +o_lon_p form without +to_meter is on the device path')
         return dict(kind='ob_tran', a=1.0, rf=0.0, lat0=0.0, lon0=float(p.get('lon_0', 0)), k0=1.0, x0=0.0, y0=0.0,
                     lat1=float(p.get('o_lat_p', 90.0)), lat2=float(p.get('o_lon_p', 0.0)), lat_ts=0.0)
-    if name not in ('stere', 'merc', 'lcc', 'tmerc', 'utm', 'laea'):
+    if name not in ('stere', 'merc', 'lcc', 'tmerc', 'utm', 'laea', 'moll'):
         raise NotImplementedError('projection +proj=%s is not on the device path (latlong, stere, merc, lcc, tmerc, utm, laea, '
-                                  'ob_tran with o_proj=longlat are)' % name)
+                                  'ob_tran with o_proj=longlat are; moll for map grids)' % name)
     a, rf = _ELLPS[p.get('ellps', 'WGS84')]
     if 'R' in p:
         a, rf = float(p['R']), 0.0
@@ -63,6 +64,8 @@ def parse_proj4(proj4):
         out.update(kind='tmerc', lat_ts=0.0)
     elif name == 'laea':
         out.update(kind='laea', lat_ts=0.0, k0=1.0)
+    elif name == 'moll':      # PROJ's moll is spherical: the radius is the semi-major axis, +lat_0 and +k_0 do nothing
+        out.update(kind='moll', rf=0.0, lat0=0.0, k0=1.0, lat_ts=0.0)
     elif name == 'merc':
         out.update(kind='merc', lat_ts=float(p.get('lat_ts', 0.0)))
     elif name == 'lcc':
@@ -384,6 +387,51 @@ def laea_inverse(x, y, **p):
     return np.degrees(_wrap(lam + np.radians(p['lon0']))), np.degrees(phi)
 
 
+# ---- Mollweide on the sphere of radius a (Snyder 31-1..31-8), the arithmetic of csrc/odr_conc.hip.h: 2 th + sin 2 th = pi sin phi is
+# solved for eps = pi - 2 |th|, eps - sin eps = 2 pi sin^2((pi/2 - |phi|) / 2), whose derivative vanishes at the pole only
+def _eps_minus_sin(e):
+    q = e * e
+    ser = e * q * (1 / 6 - q * (1 / 120 - q * (1 / 5040 - q * (1 / 362880 - q * (1 / 39916800 - q / 6227020800)))))
+    return np.where(e < 0.25, ser, e - np.sin(e))
+
+
+def _moll_eps(alat_deg):
+    sh = np.sin(0.5 * np.radians(90.0 - alat_deg))
+    c = 2 * np.pi * sh * sh
+    e = np.cbrt(6 * c)
+    for _ in range(12):
+        with np.errstate(invalid='ignore', divide='ignore'):
+            d = np.where(c > 0, (_eps_minus_sin(e) - c) / (2 * np.sin(0.5 * e) ** 2), 0.0)
+        e = e - d
+    return e
+
+
+def moll_forward(lon, lat, **p):
+    lat = np.asarray(lat, dtype=np.float64)
+    lam = np.radians(np.asarray(lon, dtype=np.float64)) - np.radians(p['lon0'])
+    with np.errstate(invalid='ignore'):
+        lam = np.where(np.abs(lam) <= np.pi + 1e-12, lam, _wrap(lam))      # (PROJ's adjlon: +-180 degrees stay where they are)
+    alat = np.abs(lat)
+    with np.errstate(invalid='ignore'):
+        half = 0.5 * _moll_eps(np.where(alat <= 90.0, alat, np.nan))      # th = pi/2 - eps/2
+    return (p['a'] * (2 * np.sqrt(2.0) / np.pi) * lam * np.sin(half) + p['x0'],
+            p['a'] * np.sqrt(2.0) * np.copysign(np.cos(half), lat) + p['y0'])
+
+
+def moll_inverse(x, y, **p):
+    X = (np.asarray(x, dtype=np.float64) - p['x0']) / p['a']
+    Y = (np.asarray(y, dtype=np.float64) - p['y0']) / p['a'] / np.sqrt(2.0)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        sy = np.where(np.abs(Y) <= 1.0 + 1e-12, np.minimum(np.abs(Y), 1.0), np.nan)
+        cos_th = np.sqrt((1 - sy) * (1 + sy))
+        eps = 2 * np.arctan2(cos_th, sy)
+        colat = 2 * np.arcsin(np.minimum(np.sqrt(_eps_minus_sin(eps) / (2 * np.pi)), 1.0))
+        lam = np.where(cos_th > 0, np.pi * X / (2 * np.sqrt(2.0) * cos_th), np.where(X == 0, 0.0, np.nan))
+        lam = np.where(np.abs(lam) <= np.pi * (1 + 1e-12), np.clip(lam, -np.pi, np.pi), np.nan)
+    lat = np.where(np.isnan(lam), np.nan, np.copysign(90.0 - np.degrees(colat), Y))
+    return np.degrees(_wrap(lam + np.radians(p['lon0']))), lat
+
+
 # ---- rotated pole (PROJ's ob_tran o_forward / o_inverse with o_proj=longlat): reader coordinates in DEGREES
 def ob_tran_forward(lon, lat, **p):
     lam = _wrap(np.radians(np.asarray(lon, dtype=np.float64)) - np.radians(p['lon0']))
@@ -411,6 +459,14 @@ class Proj:
         self.params = parse_proj4(proj4)
         self.is_geographic = self.params['kind'] in ('latlong', 'ob_tran')   # (pyproj: a derived geographic CRS)
 
+    @classmethod
+    def from_params(cls, params, srs=''):
+        """The Proj of a dict that parse_proj4 made."""
+        self = cls.__new__(cls)
+        self.srs, self.params = srs, params
+        self.is_geographic = params['kind'] in ('latlong', 'ob_tran')
+        return self
+
     def __call__(self, a, b, inverse=False):
         p = self.params
         if p['kind'] == 'latlong':
@@ -430,4 +486,6 @@ class Proj:
             return stere_oblique_inverse(a, b, **p) if inverse else stere_oblique_forward(a, b, **p)
         if p['kind'] == 'ob_tran':
             return ob_tran_inverse(a, b, **p) if inverse else ob_tran_forward(a, b, **p)
+        if p['kind'] == 'moll':
+            return moll_inverse(a, b, **p) if inverse else moll_forward(a, b, **p)
         return stere_polar_inverse(a, b, **p) if inverse else stere_polar_forward(a, b, **p)

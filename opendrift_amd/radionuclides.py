@@ -352,6 +352,56 @@ class RadionuclideDrift(OceanDrift):
         if n_new != num_elements:      # (a single draw would have been taken for every element)
             raise ValueError('%s elements were seeded, but the species were drawn for %s' % (n_new, num_elements))
 
+    # ------------------------------------------------------------------ concentration maps (:1425-1492, :1518-1551)
+    def prepare_run(self):   # :224-225
+        self.depthintervals = [float(item) for item in self.get_config('radionuclide:output:depthintervals').split(',')]
+        super().prepare_run()
+
+    def get_radionuclide_density_array(self, pixelsize_m, z_array, density_proj=None, llcrnrlon=None, llcrnrlat=None, urcrnrlon=None,
+                                       urcrnrlat=None, weight=None, origin_marker=None):
+        """radionuclides.py:1425-1492: (H, lon_array, lat_array), H float64 [time, species, layer, x_bin, y_bin] the number of
+        elements of each species in each depth layer z_array[zi] < z <= z_array[zi + 1] per pixel of pixelsize_m in density_proj
+        (as in get_density_array_proj; None: the reference's '+proj=moll +ellps=WGS84 +lon_0=0.0').  z_array: strictly increasing,
+        finite.  The comparisons are made in float64; an element whose z or specie is NaN counts nowhere.  lon_array, lat_array:
+        the inverse projection of np.meshgrid(y_array, x_array).
+
+        weight / origin_marker: the reference hands np.histogram2d the whole row of weights with a selection of the positions
+        (:1476-1485), which NumPy rejects -- there is nothing to reproduce, so both are refused.
+
+        Without the four corners the extremes are taken on the device over the entries whose projection is finite (the reference's
+        x.min() ... need a result without NaN); a sharded run needs the corners.  Projection, classification and binning run on
+        the device (odr_species_layer_map)."""
+        if weight is not None or origin_marker is not None:
+            raise NotImplementedError('get_radionuclide_density_array: weight / origin_marker make the reference pass np.histogram2d a '
+                                      'whole row of weights with a selection of the positions (radionuclides.py:1476-1485), which NumPy '
+                                      'rejects; counts only')
+        result = getattr(self, 'result', None)
+        if result is None:
+            raise RuntimeError('get_radionuclide_density_array needs the result of run()')
+        for name in ('lon', 'lat', 'z', 'specie'):
+            if name not in result:
+                raise KeyError('%s is not in self.result (export_variables)' % name)
+        z_array = np.asarray(z_array, dtype=np.float64).ravel()
+        if len(z_array) < 2 or not np.isfinite(z_array).all() or not (np.diff(z_array) > 0).all():
+            raise ValueError('get_radionuclide_density_array: z_array must be finite and strictly increasing, at least two values')
+        params, x_array, y_array = self._map_grid('get_radionuclide_density_array', pixelsize_m, density_proj,
+                                                  '+proj=moll +ellps=WGS84 +lon_0=0.0', (llcrnrlon, llcrnrlat, urcrnrlon, urcrnrlat))
+        if len(x_array) < 2 or len(y_array) < 2:
+            raise ValueError('get_radionuclide_density_array: %d x %d edges' % (len(x_array), len(y_array)))
+        H = self.ctx.species_layer_map(params, result['lon'], result['lat'], result['z'], result['specie'], x_array, y_array, z_array,
+                                       self.nspecies)
+        lon_array, lat_array = self.ctx.proj_grid_lonlat(params, x_array, y_array)
+        return H, lon_array, lat_array
+
+    def horizontal_smooth(self, a, n=0):
+        """radionuclides.py:1518-1551: the mean over the (2 n + 1)^2 window of the values of `a` truncated to integers, the plane
+        padded with n zeros all round; n == 0 returns `a` itself.  The sums are of integers, so the result is the reference's bit for
+        bit.  Beyond the reference's 2-D input, any leading dimensions are accepted (the 5-D H) and the last two are smoothed.  On
+        the device (odr_box_smooth)."""
+        if n == 0:
+            return a
+        return self.ctx.box_smooth(a, n)
+
     # ------------------------------------------------------------------ the run
     def run(self, *args, **kwargs):
         action = self.get_config('general:seafloor_action', 'lift_to_seafloor')
