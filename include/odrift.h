@@ -742,6 +742,13 @@ int odr_particles_vmix_layout_stats(odr_ctx *ctx, odr_particles *p, uint64_t *ou
  *         launches that read the node records}.
  * The environment variable ODR_NO_KPLANE=1 keeps every launch on the node records (the planes are still written). */
 int odr_particles_vmix_kplane_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out2);
+/* The launches of the K-column kernel for C3's static configuration on a 12-level column (counted in out3[1] of
+ * odr_particles_vmix_layout_stats) since the set was created:
+ * out3 = {launches that gathered two of the column's three K quads per particle (csrc/odr_kernels.hip.h VMixC3W), launches that
+ *         gathered the whole column, elements the two-quad launches redid on the whole column because a sub-step left the
+ *         resident levels (read from the device: waits for the stream)}.
+ * The environment variable ODR_NO_VMIX_WINDOW=1 keeps every such launch on the whole column. */
+int odr_particles_vmix_window_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out3);
 /* counts and min/max used for the per-step log line and early-outs (:2212-2233):
  * out16 = {n_active, lon_min, lon_max, lat_min, lat_max, z_min, z_max, D_max, stokes_sum_max,
  *          wind_speed_max, wdf_surface_max, n_surface, hs_max, tp_max, 0, 0} */

@@ -480,6 +480,7 @@ struct VMixDesc {
   double wgt;            // weight_after (structured.py:353-354)
   float Kfb, pad2;
   const unsigned long long *guard;   // nullptr, or: the launch does nothing unless *guard != 0 (odr_ctx_guard_next_vmix)
+  unsigned long long *redone;        // a two-quad launch (VMixC3W) counts the elements it redid on the whole column here
 };
 
 // The configuration of k_vmix_col -- the K source's longitude convention, projection, level count and level spacing, and the
@@ -489,6 +490,7 @@ struct VMixDesc {
 // (vmix_layout_matches, odr_mix.hip); the arithmetic and its rounding points are the same.
 struct VMixRT {
   static constexpr bool STATIC = false;
+  static constexpr bool WINDOW = false;
   __host__ __device__ static constexpr int proj_kind(int k) { return k; }
   __host__ __device__ static constexpr int lon_mode(int m) { return m; }
   __host__ __device__ static constexpr int mod360_x(int m) { return m; }
@@ -508,6 +510,7 @@ struct VMixRT {
 // (fuse_vertical_advection=False), ten sub-steps, K gathered from the levels' K planes (16 NQ bytes per node)
 struct VMixC3 {
   static constexpr bool STATIC = true;
+  static constexpr bool WINDOW = false;
   __host__ __device__ static constexpr int proj_kind(int) { return PROJ_LATLONG; }
   __host__ __device__ static constexpr int lon_mode(int) { return 1; }
   __host__ __device__ static constexpr int mod360_x(int) { return 0; }
@@ -527,13 +530,33 @@ struct VMixC3 {
 struct VMixC3Rec : VMixC3 {
   __host__ __device__ static constexpr unsigned kstride(unsigned b, int /*NQ*/) { return b; }
 };
+// The 12-level column of the same configurations with TWO of its three quads gathered per particle, chosen per lane and aligned:
+// quads Q0 and Q0 + 1, Q0 = min(max(lv0 - 2, 0) >> 2, NQ - 2) for the starting level lv0 of the particle.  For every lv0 in
+// 1 .. 10 the resident levels 4 Q0 .. 4 Q0 + 7 hold lv0 - 2 .. lv0 + 2 clipped to the profile -- all that the terms of the cached
+// window lv0 - 1 .. lv0 + 1 read (lv0 <= 5: levels 0 .. 7; lv0 >= 6: levels 4 .. 11).  The values land in the same LDS slots as
+// the whole column's; the slots of the third quad stay unwritten.  A sub-step that leaves the cached window derives its terms
+// from the column: when a level it reads is not resident the lane is marked, none of its results is stored, and the launch
+// redoes it from its state in memory with the whole-column configuration Full -- same bits (vmix_col_walk, k_vmix_col).
+// 16 gathers per particle instead of 24 between two time levels, none of them across a line.
+struct VMixWin { int lv0, q0; bool escaped; };
+struct VMixC3W : VMixC3 {
+  static constexpr bool WINDOW = true;
+  using Full = VMixC3;
+};
+struct VMixC3RecW : VMixC3Rec {
+  static constexpr bool WINDOW = true;
+  using Full = VMixC3Rec;
+};
 
 // K column of one particle at (lon, lat) -> Kp[level][tid] (LDS), time-interpolated like the ReaderBlock's profiles
 // hook: arithmetic of the caller that does not depend on the column (the first Philox block of the particle's stream), run
 // right behind the gathers of the first quad so that it overlaps their flight instead of standing in front of their issue
+// q0: a two-quad configuration (VM::WINDOW) fills quads q0 and q0 + 1 of the column, per lane; else 0
 template <int NQ, bool TL, class VM, class HOOK>
 __device__ __forceinline__ void vmix_col_fill(const DevSource &s, const VMixDesc &D, double lon, double lat, double *Kp,
-                                              int tid, HOOK &&hook) {
+                                              int tid, int q0, HOOK &&hook) {
+  static_assert(!VM::WINDOW || NQ >= 2, "a two-quad configuration needs two quads");
+  constexpr int NF = VM::WINDOW ? 2 : NQ;   // quads filled
   const double Kfb = (double)D.Kfb;
   double x, y;
   const int lon_mode = VM::lon_mode(s.lon_mode);
@@ -553,15 +576,20 @@ __device__ __forceinline__ void vmix_col_fill(const DevSource &s, const VMixDesc
   // the stride of a K plane is never longer than the record's)
   const unsigned recb = VM::kstride(D.kstride, NQ);
   const unsigned r0 = __umul24((unsigned)ay.i0, (unsigned)nx), r1 = __umul24((unsigned)ay.i1, (unsigned)nx);
-  const unsigned o00 = cov ? __umul24(r0 + (unsigned)ax.i0, recb) : 0u, o01 = cov ? __umul24(r0 + (unsigned)ax.i1, recb) : 0u;
-  const unsigned o10 = cov ? __umul24(r1 + (unsigned)ax.i0, recb) : 0u, o11 = cov ? __umul24(r1 + (unsigned)ax.i1, recb) : 0u;
+  unsigned o00 = cov ? __umul24(r0 + (unsigned)ax.i0, recb) : 0u, o01 = cov ? __umul24(r0 + (unsigned)ax.i1, recb) : 0u;
+  unsigned o10 = cov ? __umul24(r1 + (unsigned)ax.i0, recb) : 0u, o11 = cov ? __umul24(r1 + (unsigned)ax.i1, recb) : 0u;
+  if constexpr (VM::WINDOW) {   // the lane's first quad: gathers and LDS slots q0 quads further on (inside the node's column)
+    const unsigned qb = 16u * (unsigned)q0;
+    o00 += qb; o01 += qb; o10 += qb; o11 += qb;
+    Kp += 4 * q0 * BLOCK;
+  }
   const float *kb = D.kb, *ka = TL ? D.ka : D.kb;
   // horizontal weights multiplied out once for the whole column (float64; the layer value is rounded to float32 like
   // the ReaderBlock's: same bits as (v*wy)*wx summed, but for a float64 round-off that reaches the float32 rounding
   // in ~1e-8 of the values)
   const double w00 = wy0 * wx0, w01 = wy0 * tx, w10 = ty * wx0, w11 = ty * tx;
 #pragma unroll
-  for (int q = 0; q < NQ; ++q) {
+  for (int q = 0; q < NF; ++q) {
     // (a static configuration: fences in front of and behind the gathers of quads 1 .. NQ - 1.  Without them the scheduler
     // hoists part of a quad's gathers into the previous quad's arithmetic -- the 8-level column with two time levels then spills
     // 8-12 B at 80 registers -- or splits its gathers into two round trips.  With them every quad's gathers are one clause,
@@ -619,18 +647,36 @@ __device__ __forceinline__ MixRng mix_rng_begin(const VMixArgs &A, int id) {
   }
   return R;
 }
+// level boundaries (see k_vmix) in scalar registers; levels past the profile never match
+template <int NL>
+__device__ __forceinline__ void vmix_level_bounds(const DevSource &s, int nzp, double (&zm)[NL - 1]) {
+#pragma unroll
+  for (int k = 0; k < NL - 1; ++k) zm[k] = k < nzp - 1 ? s.zmid[k] : __builtin_inf();
+}
+// centre lv0 of the cached window [lv0-1, lv0+1] of a particle that starts at z
+template <int NL>
+__device__ __forceinline__ int vmix_start_level(const double (&zm)[NL - 1], int nzp, double z) {
+  const double d0 = -z;
+  int zs = 0;
+#pragma unroll
+  for (int k = 0; k < NL - 1; ++k) zs += ((k & 1) ? d0 >= zm[k] : d0 > zm[k]) ? 1 : 0;
+  int lv0 = zs < 1 ? 1 : (zs > nzp - 2 ? nzp - 2 : zs);
+  if (nzp < 3) lv0 = 1;
+  return lv0;
+}
+// win (a two-quad configuration, VM::WINDOW; else nullptr): in, the starting level the fill chose its quads by and the first
+// of them; out, escaped -- a sub-step read a level that is not resident: the returned z and everything else the walk formed for
+// this lane is to be discarded
 template <int NQ, class VM = VMixRT>
 __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, const double *Kp, const double *gsh, int tid,
                                                 const VMixArgs &A, long long i, long long n, int id, double z, int &moving,
-                                                float Zmin, float tv, int &sf_flags, const MixRng *pre) {
+                                                float Zmin, float tv, int &sf_flags, const MixRng *pre, VMixWin *win = nullptr) {
   constexpr int NL = 4 * NQ;
   static_assert(!VM::STATIC || NL >= 3, "a static configuration has the three-level window inside the profile");
   const double dt = A.dt;
   const int mix_at_surface = VM::mix_at_surface(A.mix_at_surface), rng_mode = VM::rng_mode(A.rng_mode), sfl = A.sfl;
-  // level boundaries (see k_vmix) in scalar registers; levels past the profile never match
   double zm[NL - 1];
-#pragma unroll
-  for (int k = 0; k < NL - 1; ++k) zm[k] = k < nzp - 1 ? s.zmid[k] : __builtin_inf();
+  vmix_level_bounds<NL>(s, nzp, zm);
   const bool uniform_z = VM::uniform_z(s.vg_uniform != 0);
   const double gd0 = s.vg_d[0], gi0 = s.vg_id[0], gd1 = s.vg_d[1], gi1 = s.vg_id[1], gd2 = s.vg_d[2], gi2 = s.vg_id[2];
   const double sgn = dt > 0 ? 1.0 : (dt < 0 ? -1.0 : 0.0);
@@ -665,14 +711,8 @@ __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, con
   // (branch-free selection in the loop); anything else is derived on demand.  With a per-iteration "derive when the
   // level changes" scheme the 64 lanes of a wave make that branch fire in practically every sub-step.
   int lv0;
-  {
-    const double d0 = -z;
-    int zs = 0;
-#pragma unroll
-    for (int k = 0; k < NL - 1; ++k) zs += ((k & 1) ? d0 >= zm[k] : d0 > zm[k]) ? 1 : 0;
-    lv0 = zs < 1 ? 1 : (zs > nzp - 2 ? nzp - 2 : zs);   // centre of the cached window [lv0-1, lv0+1]
-    if (nzp < 3) lv0 = 1;
-  }
+  if constexpr (VM::WINDOW) lv0 = win->lv0;     // (formed by the caller, in front of the fill, by the same expression)
+  else lv0 = vmix_start_level<NL>(zm, nzp, z);
   double c_dk[3], c_sg[3];
 #pragma unroll
   for (int q = 0; q < 3; ++q) {
@@ -720,7 +760,13 @@ __device__ __forceinline__ double vmix_col_walk(const DevSource &s, int nzp, con
     }
     double dKdt = q == 0 ? c_dk[0] : (q == 1 ? c_dk[1] : c_dk[2]);
     double sig = q == 0 ? c_sg[0] : (q == 1 ? c_sg[1] : c_sg[2]);
-    if (q < 0 || q > 2) level_terms(AnyLevel(), zi, dKdt, sig);
+    if (q < 0 || q > 2) {
+      if constexpr (VM::WINDOW) {   // the levels level_terms reads of zi: zi and its neighbours inside the profile
+        const int lo = zi > 0 ? zi - 1 : 0, hi = zi < nzp - 1 ? zi + 1 : nzp - 1;
+        if (lo < 4 * win->q0 || hi > 4 * win->q0 + 7) win->escaped = true;
+      }
+      level_terms(AnyLevel(), zi, dKdt, sig);
+    }
     double R;
     if (rng_mode == 1) R = __dsub_rn(__dmul_rn(2.0, A.huni[(size_t)it * n + i]), 1.0);
     else R = mix_R_of(mix_word(u4, (unsigned)k5));
@@ -1960,8 +2006,9 @@ __device__ __forceinline__ VMixState vmix_load_state(const PView &p, long long i
   return S;
 }
 // one particle of k_vmix_col: column into the thread's LDS slots, sub-steps, stores
+// Returns true, and stores nothing, when a two-quad configuration (VM::WINDOW) could not finish the particle (VMixWin::escaped)
 template <int NQ, bool TL, class VM>
-__device__ __forceinline__ void vmix_col_particle(const DevSource &s, const PView &p, const VMixDesc &D, const VMixArgs &A,
+__device__ __forceinline__ bool vmix_col_particle(const DevSource &s, const PView &p, const VMixDesc &D, const VMixArgs &A,
                                                   int vadv, long long i, double *Kp, const double *gsh, int tid, const VMixState &S) {
   const int nzp = VM::nzp(D.nzp, 4 * NQ), sfl = A.sfl;
   const double dt = A.dt;
@@ -1971,11 +2018,21 @@ __device__ __forceinline__ void vmix_col_particle(const DevSource &s, const PVie
   const int id0 = S.id;
   MixRng R0;
   R0.key = mix_key(A.seed, A.step, id0); R0.q = make_uint4(0u, 0u, 0u, 0u); R0.primed = false;
+  VMixWin win = {0, 0, false};
+  if constexpr (VM::WINDOW) {   // the starting level decides which two quads the lane gathers
+    double zm[4 * NQ - 1];
+    vmix_level_bounds<4 * NQ>(s, nzp, zm);
+    win.lv0 = vmix_start_level<4 * NQ>(zm, nzp, z0);
+    const int qa = (win.lv0 > 2 ? win.lv0 - 2 : 0) >> 2;
+    win.q0 = qa < NQ - 2 ? qa : NQ - 2;
+  }
   // the stream's first block behind the first gathers of the column: its arithmetic runs while they are in flight
-  vmix_col_fill<NQ, TL, VM>(s, D, slon, slat, Kp, tid, [&]() { R0 = mix_rng_begin<VM>(A, id0); });
+  vmix_col_fill<NQ, TL, VM>(s, D, slon, slat, Kp, tid, win.q0, [&]() { R0 = mix_rng_begin<VM>(A, id0); });
   int sf_flags = VM::sf_action(sfl & 255) == 5 ? sf_species_flag(p, sfl, i) : 0;
   const float Zmin = __fmul_rn(-1.f, __fadd_rn(dep0, ssh0));  // float32 (:408)
-  double z = vmix_col_walk<NQ, VM>(s, nzp, Kp, gsh, tid, A, i, p.n, id0, z0, moving, Zmin, tv0, sf_flags, &R0);
+  double z = vmix_col_walk<NQ, VM>(s, nzp, Kp, gsh, tid, A, i, p.n, id0, z0, moving, Zmin, tv0, sf_flags, &R0,
+                                   VM::WINDOW ? &win : nullptr);
+  if (VM::WINDOW && win.escaped) return true;
   if (sf_flags & 1) {   // deactivate_elements(reason='seafloor') (basemodel/__init__.py:1774-1795)
     if (p.status[i] == 0) p.status[i] = sfl >> 8;
     p.moving[i] = 0;
@@ -1991,6 +2048,7 @@ __device__ __forceinline__ void vmix_col_particle(const DevSource &s, const PVie
     z = zz < 0 ? zz : 0.0;
   }
   p.z[i] = z;
+  return false;
 }
 // VM: the mixing configuration (VMixRT / VMixC3 above)
 template <int NQ, bool TL, class VM = VMixRT>
@@ -2020,7 +2078,19 @@ __global__ __launch_bounds__(BLOCK, ODR_VMIX_WAVES) void k_vmix_col(const DevWor
   VMixArgs A;
   A.dt = dt; A.dt_mix_cfg = dt_mix_cfg; A.mix_at_surface = mix_at_surface; A.rng_mode = rng_mode; A.sfl = sfl; A.pad = 0;
   A.huni = huni; A.seed = seed; A.step = step;
-  vmix_col_particle<NQ, TL, VM>(s, p, D, A, vadv, i, Kp, gsh, tid, S);
+  const bool escaped = vmix_col_particle<NQ, TL, VM>(s, p, D, A, vadv, i, Kp, gsh, tid, S);
+  if constexpr (VM::WINDOW) {
+    // the lanes a two-quad pass could not finish (rare: none in C3's field) run the whole-column routine from scratch, their
+    // state read again -- nothing of them has been stored, so the result is that launch's; one atomic per wave counts them
+    const unsigned long long esc = __ballot(escaped);
+    if (esc != 0ull) {
+      if (escaped) {
+        const VMixState S2 = vmix_load_state(p, i);
+        vmix_col_particle<NQ, TL, typename VM::Full>(s, p, D, A, vadv, i, Kp, gsh, tid, S2);
+        if (D.redone && (tid & 63) == __ffsll((long long)esc) - 1) atomicAdd(D.redone, (unsigned long long)__popcll(esc));
+      }
+    }
+  }
 }
 
 // ---- k_vmix_win: the same mixing with the diffusivity of FIVE levels per particle instead of the whole column.

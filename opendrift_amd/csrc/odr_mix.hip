@@ -105,8 +105,14 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
                       vmix_layout_matches<VMixC3Rec>(c->hw.src[D.sid], D, nq, dt, dt_mix, mix_at_surface, rng_mode, c->seafloor, vadv) &&
                       !getenv("ODR_NO_VMIX_SPEC");
     const bool specp = spec && vmix_layout_matches<VMixC3>(c->hw.src[D.sid], D, nq, dt, dt_mix, mix_at_surface, rng_mode, c->seafloor, vadv);
+    // the 12-level static launch gathers two of the column's three quads per particle (VMixC3W / VMixC3RecW: lanes whose
+    // sub-steps leave them are redone on the whole column inside the launch, counted in vmix_redone);
+    // ODR_NO_VMIX_WINDOW=1 keeps the whole-column launch (A/B runs and tests)
+    const bool quadwin = spec && nq == 3 && !getenv("ODR_NO_VMIX_WINDOW");
     p->vmix_launches[win ? 2 : spec ? 1 : 0]++;
     p->vmix_kplane[kplanes ? 0 : 1]++;
+    if (spec && nq == 3) p->vmix_window[quadwin ? 0 : 1]++;
+    D.redone = quadwin ? p->vmix_redone : nullptr;
 #define VMIX_COL(NQ, VM)                                                                                          \
   do {                                                                                                            \
     size_t l2 = sizeof(double) * ((size_t)(4 * NQ) * BLOCK + 4 * (size_t)(4 * NQ));                               \
@@ -123,8 +129,10 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
                               c->seed, st, vadv, c->seafloor);
     }
     else if (specp && nq == 2) VMIX_COL(2, VMixC3);
+    else if (specp && quadwin) VMIX_COL(3, VMixC3W);
     else if (specp) VMIX_COL(3, VMixC3);
     else if (spec && nq == 2) VMIX_COL(2, VMixC3Rec);
+    else if (spec && quadwin) VMIX_COL(3, VMixC3RecW);
     else if (spec) VMIX_COL(3, VMixC3Rec);
     // the smallest instantiated quad count >= nq; over-read stays inside the 64-byte array padding
     else if (nq <= 1) VMIX_COL(1, VMixRT);
@@ -157,6 +165,15 @@ int odr_particles_vmix_layout_stats(odr_ctx *c, odr_particles *p, uint64_t *out3
 int odr_particles_vmix_kplane_stats(odr_ctx *c, odr_particles *p, uint64_t *out2) {
   REQUIRE(c && p && out2, "NULL argument");
   out2[0] = p->vmix_kplane[0]; out2[1] = p->vmix_kplane[1];
+  return 0;
+}
+
+int odr_particles_vmix_window_stats(odr_ctx *c, odr_particles *p, uint64_t *out3) {
+  REQUIRE(c && p && out3, "NULL argument");
+  unsigned long long redone = 0;
+  D2H(&redone, p->vmix_redone, sizeof redone);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  out3[0] = p->vmix_window[0]; out3[1] = p->vmix_window[1]; out3[2] = redone;
   return 0;
 }
 

@@ -133,6 +133,8 @@ int odr_particles_create(odr_ctx *c, int64_t capacity, odr_particles **out) {
   HIPCHK(hipMalloc((void **)&p->bcount, sizeof(unsigned) * (size_t)(nblk(capacity) + 1)));
   HIPCHK(hipMalloc((void **)&p->wcount, sizeof(unsigned) * (size_t)(nblk(capacity) + 1) * (BLOCK / 64)));
   p->wcount_epoch = ~0ull;
+  HIPCHK(hipMalloc((void **)&p->vmix_redone, sizeof(unsigned long long)));
+  HIPCHK(hipMemset(p->vmix_redone, 0, sizeof(unsigned long long)));
   *out = p;
   return 0;
 }
@@ -152,6 +154,7 @@ int odr_particles_destroy(odr_ctx *c, odr_particles *p) {
   for (int k = 0; k < 9; ++k) { fr(p->aux[k]); fr(p->altaux[k]); fr(p->aux_snap[k]); }
   fr(p->bcount);
   fr(p->wcount);
+  fr(p->vmix_redone);
   fr(p->scratch);
   fr(p->rank); fr(p->rank_words); fr(p->rank_before); fr(p->rank_bsum);
   fr(p->wg_tab); fr(p->wg_total); fr(p->wg_list); fr(p->z_keep);

@@ -1415,6 +1415,14 @@ class Particles:
         check(self.lib.odr_particles_vmix_kplane_stats(self.ctx.h, self.h, out))
         return dict(planes=int(out[0]), records=int(out[1]))
 
+    def vmix_window_stats(self):
+        """The static 12-level K-column launches (odr_particles_vmix_window_stats): those that gathered two K quads per
+        particle, those that gathered the whole column, and the elements the two-quad launches redid on the whole column."""
+        import ctypes as C
+        out = (C.c_uint64 * 3)()
+        check(self.lib.odr_particles_vmix_window_stats(self.ctx.h, self.h, out))
+        return dict(windowed=int(out[0]), full=int(out[1]), redone=int(out[2]))
+
     def reduce_global(self, combine, wind_drift_depth=0.1, relative_wind=False):
         """Sharded run: this set's raw reductions -> combine(raw16) over the ranks (counts summed, maxima maximised) ->
         installed for the movers that follow, until reduce_unpin()."""
