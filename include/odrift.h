@@ -1080,6 +1080,41 @@ int odr_shape_stats(odr_ctx *ctx, odr_shape *shape, double *stats);
  * that came later (waits for it) */
 int odr_shape_last_kernel_ms(odr_ctx *ctx, float *ms);
 
+/* ---------------------------------------------------------------- reader operators (sums, numbers, Gaussian blends)
+ * The reference's readers/operators/: `a + b` (ops.py:14-25 -> readerops.Combined), `n + r`, `n * r`, `r / n`, `r - n` (ops.py:30-50
+ * -> numops.Combined) and r.combine_gaussian(measurements, std) (ops.py:52-96), evaluated per element and variable on the device
+ * (csrc/odr_combine.hip.h).  The caller flattens the expression to postfix: */
+enum { ODR_COMBINE_SOURCE = 0,      /* push the value of source `index` at the element (its own time interpolation and rotation) */
+       ODR_COMBINE_UNIFORM = 1,     /* push uniform leaf `index`: one value per variable, resolved by the caller (a time series) */
+       ODR_COMBINE_ADD = 2,         /* the two topmost values become their sum (readerops.py:107) */
+       ODR_COMBINE_GAUSS_TERM = 3,  /* behind a blend's model operand, once per measurement: uniform leaf `index` measured at
+                                     * longitude d[0], latitude d[1], with standard deviation d[2] [m] (readerops.py:110-123) */
+       ODR_COMBINE_GAUSS_END = 4,   /* top = top (1 - sum f) + sum b f, f = exp(-(distance / std)^2 / 2) on WGS84 */
+       ODR_COMBINE_NUM_ADD = 5,     /* top = d[0] + top   (numops.py:28-30) -- a number-op is the last operation of a program */
+       ODR_COMBINE_NUM_MUL = 6,     /* top = d[0] * top   (numops.py:32-34) */
+       ODR_COMBINE_NUM_DIV = 7 };   /* top = top / d[0]   (numops.py:40-42) */
+typedef struct { int32_t kind, index; double d[3]; } odr_combine_op;
+/* odr_combined_create (Combined.__init__, readerops.py:25-60; numops.py:20-27): 1 .. 32 operations, at most three values held at a
+ * time -- (a + b) + (c + d) and every left-deep chain fit -- and 8 uniform leaves.  ODR_ERR_INVALID otherwise, and for a source id
+ * that is not in use.  A value is float32 where the reference's array is: a 2-D block level of a reader that covers EVERY element
+ * of the call (a reader that misses one hands out a masked float64 array, variables.py:840-858); float32 + float32 is a float32
+ * sum, number o float32 a float64 operation (the reference's operands are masked arrays).  The operands' vector pairs are NOT rotated: readerops.py:84-101 does not pass
+ * rotate_to_proj on. */
+typedef struct odr_combined odr_combined;
+int odr_combined_create(odr_ctx *ctx, int32_t n_ops, const odr_combine_op *ops, odr_combined **out);
+int odr_combined_destroy(odr_ctx *ctx, odr_combined *combined);
+/* Combined.get_variables_interpolated (readerops.py:78-133; numops.py:52-71) behind get_environment's reader loop
+ * (environment.py:597-762, the float32 cast of :695) for every element of the particle set at time t_epoch: the reader front
+ * door once per leaf (its projection and coverage, which also settle the leaf's dtype class; the positions go through the particle
+ * set's scratch memory), then ONE sampling launch for var_ids (1 .. 8, none twice).  The result is missing where an operand is; a
+ * finite value is taken where first[k] != 0 or where the slot of variable k holds nothing finite; a slot that was never sampled
+ * starts as NaN.  uniform_values: [nvars][n_uniform].  ODR_ERR_STATE when a gridded leaf's resident levels do not serve t_epoch;
+ * ODR_ERR_INVALID for a leaf with ensemble members.  Enqueued on the context's stream. */
+int odr_combined_sample(odr_ctx *ctx, odr_particles *p, odr_combined *combined, int32_t nvars, const int32_t *var_ids, const uint8_t *first,
+                        double t_epoch, int32_t n_uniform, const double *uniform_values);
+/* device time [ms] of the two launches of this process's last odr_combined_sample (waits for them) */
+int odr_combined_last_kernel_ms(odr_ctx *ctx, float *ms);
+
 /* ---------------------------------------------------------------- ROMS sigma grid
  * The sigma -> z regridding reader_ROMS_native.get_variables applies to every 4-D variable of a block
  * (reader_ROMS_native.py:512-538,617-684) with roppy (readers/roppy/depth.py): sdepth (:31-113, rho points,

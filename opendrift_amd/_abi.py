@@ -66,6 +66,13 @@ class ProjDesc(C.Structure):
                 ('x0', C.c_double), ('y0', C.c_double), ('lat1_deg', C.c_double), ('lat2_deg', C.c_double)]
 
 
+class CombineOp(C.Structure):   # odr_combine_op
+    _fields_ = [('kind', C.c_int32), ('index', C.c_int32), ('d', C.c_double * 3)]
+# ODR_COMBINE_*: the kinds of an odr_combine_op; the limits of a program (csrc/odr_combine.hip.h)
+COMBINE_SOURCE, COMBINE_UNIFORM, COMBINE_ADD, COMBINE_GAUSS_TERM, COMBINE_GAUSS_END, COMBINE_NUM_ADD, COMBINE_NUM_MUL, COMBINE_NUM_DIV = range(8)
+COMBINE_MAX_OPS, COMBINE_MAX_UNIFORM, COMBINE_MAX_VARIABLES, COMBINE_STACK = 32, 8, 8, 3
+
+
 class OdrError(RuntimeError):
     code = 0          # the ODR_ERR_* value (include/odrift.h): -3 = a capacity of the device library is exhausted
 
@@ -256,6 +263,10 @@ _SIGNATURES = {
     'odr_shape_contains': [_vp, _vp, C.c_int64, _dp, _dp, _fp],
     'odr_shape_stats': [_vp, _vp, _dp],
     'odr_shape_last_kernel_ms': [_vp, _fp],
+    'odr_combined_create': [_vp, C.c_int32, _P(CombineOp), _P(_vp)],
+    'odr_combined_destroy': [_vp, _vp],
+    'odr_combined_sample': [_vp, _vp, _vp, C.c_int32, _ip, _P(C.c_uint8), C.c_double, C.c_int32, _dp],
+    'odr_combined_last_kernel_ms': [_vp, _fp],
 }
 UMESH_MAX_VARIABLES, UMESH_LEVELS = 8, 3      # odr_umesh_sample, odr_umesh_set_level
 EXPORTS = sorted(list(_SIGNATURES) + ['odr_last_error', 'odr_version'])

@@ -688,6 +688,15 @@ class Context:
         check(self.lib.odr_shape_last_kernel_ms(self.h, C.byref(ms)))
         return ms.value
 
+    def combined(self, ops):
+        """The device program of a reader expression (odr_combined_create): Combined.  ops: (kind, index, (d0, d1, d2)) in postfix."""
+        return Combined(self, ops)
+
+    def combined_last_kernel_ms(self):
+        ms = C.c_float()
+        check(self.lib.odr_combined_last_kernel_ms(self.h, C.byref(ms)))
+        return ms.value
+
     def particles(self, capacity):
         return Particles(self, capacity)
 
@@ -821,6 +830,20 @@ class Particles:
         """land_binary_mask of the polygons at every element, merged into the environment slot in one launch (odr_shape_sample):
         the value is taken where `first` or where the slot holds nothing finite; elements outside the box keep what they have."""
         check(self.lib.odr_shape_sample(self.ctx.h, self.h, shape.ptr, int(bool(first))))
+
+    def combined_sample(self, combined, variables, first, t_epoch, uniform=None):
+        """The expression's values at every element at time t_epoch, merged into the environment slots in one launch
+        (odr_combined_sample): a finite value is taken where first[k] or where the slot holds nothing finite.  uniform:
+        [variable][uniform leaf] values of the program's uniform leaves."""
+        ids, pi = _i([self.ctx._vid(v) for v in variables])
+        if len(first) != len(ids):
+            raise ValueError('%d variables and %d first flags' % (len(ids), len(first)))
+        fl = np.ascontiguousarray([bool(f) for f in first], dtype=np.uint8)
+        uni = np.zeros((len(ids), 0)) if uniform is None else np.ascontiguousarray(uniform, dtype=np.float64)
+        if uni.ndim != 2 or uni.shape[0] != len(ids):
+            raise ValueError('uniform values of shape %s for %d variables' % (uni.shape, len(ids)))
+        check(self.lib.odr_combined_sample(self.ctx.h, self.h, combined.ptr, len(ids), pi, fl.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                           float(t_epoch), uni.shape[1], uni.ctypes.data_as(_dp) if uni.size else None))
 
     def env_add_noise(self, var_x, var_y, std, step=0, normals=None, uniform=False):
         """drift:current_uncertainty / wind_uncertainty (normal) or drift:current_uncertainty_uniform (uniform=True) on
@@ -1489,7 +1512,7 @@ def _touching(fn):
     return wrapper
 
 
-for _name in ('append', 'upload', 'env_sample', 'umesh_sample', 'shape_sample', 'env_upload', 'env_add_noise', 'advect', 'env_coast_advect',
+for _name in ('append', 'upload', 'env_sample', 'umesh_sample', 'shape_sample', 'combined_sample', 'env_upload', 'env_add_noise', 'advect', 'env_coast_advect',
               'update_positions', 'advect_wind', 'stokes_drift', 'advect_sea_ice', 'set_property', 'leeway_capsize', 'leeway', 'hdiffusion', 'movers',
               'vmix', 'vmix_analytic', 'vmix_oil', 'vertical_advection', 'vertical_buoyancy', 'coastline', 'coastline_crossing',
               'increase_age', 'deactivate_missing', 'remap_status', 'seafloor', 'deactivate', 'deactivate_outside', 'compact',
@@ -1640,6 +1663,32 @@ class Shape:
     def close(self):
         if self.ptr and self.ctx.h:
             self.ctx.lib.odr_shape_destroy(self.ctx.h, self.ptr)
+        self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Combined:
+    """The flattened program of a reader expression (odr_combined_create / _destroy; csrc/odr_combine.hip.h)."""
+
+    def __init__(self, ctx, ops):
+        ops = list(ops)
+        arr = (_abi.CombineOp * max(len(ops), 1))()
+        for k, (kind, index, d) in enumerate(ops):
+            arr[k].kind, arr[k].index = int(kind), int(index)
+            for j, v in enumerate(tuple(d)[:3]):
+                arr[k].d[j] = float(v)
+        self.n_ops = len(ops)
+        self.ctx, self.ptr = ctx, C.c_void_p()
+        check(ctx.lib.odr_combined_create(ctx.h, len(ops), arr, C.byref(self.ptr)))
+
+    def close(self):
+        if self.ptr and self.ctx.h:
+            self.ctx.lib.odr_combined_destroy(self.ctx.h, self.ptr)
         self.ptr = C.c_void_p()
 
     def __del__(self):

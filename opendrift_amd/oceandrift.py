@@ -198,8 +198,12 @@ class OpenDriftSimulation(Configurable):
             self._readers_host['constant_reader_config'] = (ConstantReader(consts), list(consts))
             for v in consts:
                 self.priority_list.setdefault(v, []).insert(0, 'constant_reader_config')
+        # a reader expression samples a leaf that was also added on its own through that reader's binding: those are made first
+        plain = {name: DeviceReaderBinding(self.ctx, r, variables=vs) for name, (r, vs) in self._readers_host.items()
+                 if getattr(r, 'device_kind', None) != 'combined'}
+        shared = {id(b.reader): b for b in plain.values()}
         for name, (r, vs) in self._readers_host.items():
-            self.readers[name] = DeviceReaderBinding(self.ctx, r, variables=vs)
+            self.readers[name] = plain[name] if name in plain else DeviceReaderBinding(self.ctx, r, variables=vs, shared=shared)
             self.readers[name].set_extent(getattr(self, '_block_extent', getattr(self, 'simulation_extent', None)))
         landmasks = [n for n, (r, _) in self._readers_host.items() if getattr(r, 'device_kind', None) == 'landmask']
         self._landmask_sid = self.readers[landmasks[0]].sid if landmasks else None
@@ -1019,16 +1023,45 @@ class OpenDriftSimulation(Configurable):
 
     def _host_bindings(self):
         """The bindings outside the device's own priority lists: readers evaluated on the host (user-defined ContinuousReaders)
-        and unstructured meshes and coastline polygons, which the device samples in a launch of their own (odr_umesh_sample,
-        odr_shape_sample)."""
+        and unstructured meshes, coastline polygons and reader expressions, which the device samples in a launch of their own
+        (odr_umesh_sample, odr_shape_sample, odr_combined_sample)."""
         return [(n, b) for n, b in self.readers.items() if getattr(b, 'host_eval', False) or getattr(b, 'mesh', None) is not None or
-                getattr(b, 'shape', None) is not None]
+                getattr(b, 'shape', None) is not None or getattr(b, 'leaves', None) is not None]
 
     def _unbound_off_list_readers(self):
         """Readers added but not bound yet (no device context so far) that will be among _host_bindings()."""
         return [n for n, (r, _) in self._readers_host.items() if n not in self.readers and n not in self.discarded_readers and
-                (getattr(r, 'device_kind', None) in ('umesh', 'shape') or
+                (getattr(r, 'device_kind', None) in ('umesh', 'shape', 'combined') or
                  (getattr(r, 'device_kind', None) is None and isinstance(r, ContinuousReader)))]
+
+    def _check_reader_expressions(self):
+        """What a reader expression (readers.CombinedReader / NumCombinedReader / FilteredReader) cannot do on the device is
+        refused by name when the run starts."""
+        from . import readers as R
+        exprs = [(n, r) for n, (r, _) in self._readers_host.items() if getattr(r, 'device_kind', None) == 'combined']
+        if not exprs:
+            return
+        if self._world > 1:
+            raise NotImplementedError('reader expression %s in a sharded run: the model samples it outside the launch a sharded step '
+                                      'is (DESIGN.md section 8n)' % exprs[0][1].name)
+        leaves = {}
+        for name, r in exprs:
+            for op, leaf, _ in R.check_device_expression(r):
+                if op == _abi.COMBINE_SOURCE:
+                    leaves[id(leaf)] = leaf
+            mixing = 'drift:vertical_mixing' in self._config and self.get_config('drift:vertical_mixing') and \
+                self.get_config('vertical_mixing:diffusivitymodel') == 'environment'
+            if mixing and name in self.priority_list.get('ocean_vertical_diffusivity', []):
+                raise NotImplementedError('reader expression %s would be the source of the ocean_vertical_diffusivity profiles of '
+                                          'vertical mixing: a combined reader yields no vertical profiles (the reference\'s does not '
+                                          'forward them either)' % r.name)
+        sources = {id(r): r for _, (r, _) in self._readers_host.items()
+                   if getattr(r, 'device_kind', None) not in ('combined', 'umesh', 'shape') and
+                   not (getattr(r, 'device_kind', None) is None and isinstance(r, ContinuousReader))}
+        sources.update(leaves)
+        if len(sources) > 16:
+            raise NotImplementedError('the readers and the leaves of the reader expressions need %d device sources, a context holds 16'
+                                      % len(sources))
 
     def _ensemble_current(self):
         """The current comes (also) from a reader that hands it out as a list of ensemble members."""
@@ -1067,6 +1100,16 @@ class OpenDriftSimulation(Configurable):
                 try:
                     b.sample_shape(P, self.priority_list[vs[0]][0] == name)
                 except Exception as e:
+                    self._reader_failed(name, b, e)
+                continue
+            if getattr(b, 'leaves', None) is not None:      # a reader expression: its leaves and its arithmetic in one launch
+                try:
+                    b.sample_combined(P, vs, [self.priority_list[v][0] == name for v in vs], time)
+                except ReaderLevelsError:
+                    raise
+                except Exception as e:
+                    if getattr(e, 'code', 0) == -3:      # ODR_ERR_CAPACITY: the device library is out of sources / slots
+                        raise
                     self._reader_failed(name, b, e)
                 continue
             d = P.download() if d is None else d
@@ -1532,6 +1575,7 @@ class OpenDriftSimulation(Configurable):
         if self._world > 1 and any(getattr(r, 'device_kind', None) == 'shape' for r, _ in self._readers_host.values()):
             raise NotImplementedError('a ShapeReader in a sharded run: the model samples it outside the launch a sharded step is '
                                       '(DESIGN.md section 8l)')
+        self._check_reader_expressions()
         steps, out_every = self._time_arguments(time_step, steps, time_step_output, duration, end_time)
         # skip_if conditionals of required_variables (:1899-1906)
         for vn, var in list(self.required_variables.items()):

@@ -15,6 +15,7 @@ every ReaderBlock.interpolate becomes a device gather.  Analytic readers that th
 evaluates in closed form (constant, double gyre, oscillating) are recognised by `device_kind`.
 """
 from datetime import datetime, timedelta
+from numbers import Number
 
 import threading
 
@@ -27,7 +28,53 @@ def _epoch(t):
     return (t - datetime(1970, 1, 1)).total_seconds()
 
 
-class BaseReader:
+class ReaderOperators:
+    """readers/operators/ops.py: the arithmetic of readers (Combine, :9-96) and the variable filters (Filter, :100-117).  What the
+    reference rejects is rejected here in the same way: `r1 - r2`, `r1 + 2 * r2`, `2 * (3 * r1)` and `(2 * r1) + 1` are TypeErrors,
+    because a reader combined with a number (NumCombinedReader) is no reader and has no operators."""
+
+    def __add__(self, other):
+        if isinstance(other, Number):
+            return NumCombinedReader.add(other, self)
+        if isinstance(other, BaseReader):
+            return CombinedReader(self, other)
+        return NotImplemented
+
+    def __radd__(self, other):
+        return self.__add__(other)
+
+    def __mul__(self, other):
+        if isinstance(other, Number):
+            return NumCombinedReader.mul(other, self)
+        return NotImplemented
+
+    def __rmul__(self, other):
+        return self.__mul__(other)
+
+    def __truediv__(self, other):
+        if isinstance(other, Number):
+            return NumCombinedReader.div(other, self)
+        return NotImplemented
+
+    def __sub__(self, other):
+        return self + (-1 * other)
+
+    def combine_gaussian(self, measurement_reader, std):
+        """ops.py:52-96: this reader pulled towards a point measurement (a TimeseriesReader with `lon` / `lat`) with the weight
+        exp(-(d / std)^2 / 2) of the WGS84 distance d; std [m].  The reference's form with a LIST of measurement readers is
+        refused (NotImplementedError)."""
+        return CombinedReader(self, measurement_reader, kind='gaussian', std=std)
+
+    def filter_vars(self, vars):
+        """Only keep the specified variables."""
+        return FilteredReader(self, vars)
+
+    def exclude_vars(self, vars):
+        """Remove the specified variables."""
+        return FilteredReader(self, [v for v in self.variables if v not in set(vars)])
+
+
+class BaseReader(ReaderOperators):
     """Attributes of basereader/__init__.py:107-118 + variables.ReaderDomain (variables.py:20-46)."""
     name = 'reader'
     proj4 = '+proj=latlong'
@@ -72,7 +119,31 @@ class BaseReader:
 
 
 class ContinuousReader(BaseReader):
-    pass
+    def get_variables_interpolated(self, variables, profiles=None, profiles_depth=None, time=None, lon=None, lat=None, z=None,
+                                   rotate_to_proj=None):
+        """ContinuousReader._get_variables_interpolated_ (continuous.py:31-46) on the host: ({variable: values exactly at the
+        positions, NaN where the reader does not cover position or time}, None) -- what the host evaluation of a reader
+        expression asks of its leaves."""
+        lon, lat = np.atleast_1d(np.asarray(lon, dtype=np.float64)), np.atleast_1d(np.asarray(lat, dtype=np.float64))
+        n = len(lon)
+        z = np.zeros(n) if z is None else np.atleast_1d(np.asarray(z, dtype=np.float64)) * np.ones(n)
+        env = {v: np.full(n, np.nan) for v in variables}
+        if time is not None and not self.covers_time(time):
+            return env, None
+        x, y = self.lonlat2xy(lon, lat)
+        x, y = np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64)
+        ok = np.ones(n, bool)
+        if self.xmin is not None:
+            ok &= (x >= self.xmin) & (x <= self.xmax) & (y >= self.ymin) & (y <= self.ymax)
+        ok &= (z >= self.zmin) & (z <= self.zmax)
+        if ok.any():
+            res = self.get_variables(list(variables), time, x[ok], y[ok], z[ok])
+            for v in variables:
+                a = np.ma.filled(np.ma.asarray(res[v]), np.nan) * np.ones(int(ok.sum()))
+                if a.dtype == np.float32:      # the operand keeps its dtype (a float32 array stays one under n * x)
+                    env[v] = env[v].astype(np.float32)
+                env[v][ok] = a
+        return env, None
 
 
 class StructuredReader(BaseReader):
@@ -292,6 +363,40 @@ def wgs84_forward_azimuth(lon1, lat1, lon2, lat2):
         if done:
             break
     return np.degrees(np.arctan2(cU2 * np.sin(lam), cU1 * sU2 - sU1 * cU2 * np.cos(lam)))
+
+
+def wgs84_distance(lon1, lat1, lon2, lat2):
+    """Length [m] of the WGS84 geodesic between two points -- pyproj.Geod(ellps='WGS84').inv(...)[2] -- by Vincenty's inverse
+    iteration: within a millimetre of it except between nearly antipodal points, where the iteration does not converge (the
+    device's inverse, csrc/odr_geodinv.hip.h, has no such limit)."""
+    a, f = 6378137.0, 1 / 298.257223563
+    b = (1 - f) * a
+    L = np.radians(np.asarray(lon2, dtype=np.float64) - np.asarray(lon1, dtype=np.float64))
+    L = (L + np.pi) % (2 * np.pi) - np.pi
+    U1 = np.arctan((1 - f) * np.tan(np.radians(np.asarray(lat1, dtype=np.float64))))
+    U2 = np.arctan((1 - f) * np.tan(np.radians(np.asarray(lat2, dtype=np.float64))))
+    sU1, cU1, sU2, cU2 = np.sin(U1), np.cos(U1), np.sin(U2), np.cos(U2)
+    lam = L * np.ones(np.broadcast(sU1, sU2).shape)
+    for _ in range(100):
+        sl, cl = np.sin(lam), np.cos(lam)
+        ss = np.hypot(cU2 * sl, cU1 * sU2 - sU1 * cU2 * cl)
+        cs = sU1 * sU2 + cU1 * cU2 * cl
+        sig = np.arctan2(ss, cs)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            sa = np.where(ss > 0, cU1 * cU2 * sl / ss, 0.0)
+            c2a = 1 - sa * sa
+            c2m = np.where(c2a > 0, cs - 2 * sU1 * sU2 / c2a, 0.0)
+        Cc = f / 16 * c2a * (4 + f * (4 - 3 * c2a))
+        new = L + (1 - Cc) * f * sa * (sig + Cc * ss * (c2m + Cc * cs * (-1 + 2 * c2m * c2m)))
+        done = np.all(np.abs(new - lam) < 1e-15) if np.size(new) else True
+        lam = new
+        if done:
+            break
+    u2 = c2a * (a * a - b * b) / (b * b)
+    A = 1 + u2 / 16384 * (4096 + u2 * (-768 + u2 * (320 - 175 * u2)))
+    B = u2 / 1024 * (256 + u2 * (-128 + u2 * (74 - 47 * u2)))
+    dsig = B * ss * (c2m + B / 4 * (cs * (-1 + 2 * c2m * c2m) - B / 6 * c2m * (-3 + 4 * ss * ss) * (-3 + 4 * c2m * c2m)))
+    return b * A * (sig - dsig)
 
 
 def node_y_azimuth(lon2d, lat2d):
@@ -821,6 +926,245 @@ class ShapeReader(ContinuousReader):
         return vx[ind], vy[ind], np.sqrt((vx[ind] - x) ** 2 + (vy[ind] - y) ** 2)
 
 
+class TimeseriesReader(ContinuousReader):
+    """reader_timeseries.Reader (readers/reader_timeseries.py): {'time': [datetimes], variable: [values], 'lon': , 'lat': } -- the value
+    of the nearest time level, the same everywhere.  `lon` / `lat` are kept as attributes (the centre of the measurement for
+    combine_gaussian), not as variables.  Added to a model on its own it is evaluated on the host like any user-defined
+    ContinuousReader; as a leaf of a reader expression it is one scalar per variable and call (a uniform leaf of the device
+    program)."""
+
+    def __init__(self, parameter_value_map):
+        m = dict(parameter_value_map)
+        self.times = m.pop('time')
+        if not hasattr(self.times, '__len__'):
+            raise ValueError('time must be an array of datetime objects')
+        self.times = list(self.times)
+        for key in ('lon', 'lat'):
+            if key in m:
+                setattr(self, key, m.pop(key))
+        for key in m:
+            m[key] = np.atleast_1d(m[key]).astype(np.float64)
+            if len(m[key]) != len(self.times):
+                raise ValueError('All variables must have same length as time array')
+        self._parameter_value_map = m
+        self.variables = list(m)
+        self.proj4 = '+proj=latlong'
+        self.xmin, self.xmax, self.ymin, self.ymax = -180, 180, -90, 90
+        self.start_time, self.end_time = self.times[0], self.times[-1]
+        self.time_step = (self.times[1] - self.times[0]) if len(self.times) > 1 else None
+        self.name = 'reader_timeseries'
+        times = self.times
+        super().__init__()
+        self.times = times
+
+    def nearest_index(self, time):
+        """indx_nearest of variables.py:402-443 from the bracketing levels of BaseReader.nearest_time; midway: the later."""
+        ib, ia = self.nearest_time(time)
+        return ib if (time - self.times[ib]) < (self.times[ia] - time) else ia
+
+    def value(self, variable, time):
+        return float(self._parameter_value_map[variable][self.nearest_index(time)])
+
+    def get_variables(self, requested_variables, time=None, x=None, y=None, z=None):
+        out = {'time': time, 'x': x, 'y': y, 'z': z}
+        for v in requested_variables:
+            out[v] = self.value(v, time) * np.ones(np.shape(x))
+        return out
+
+
+def _none_or(a, b, cmp):      # readerops.py:7-13
+    return b if a is None else a if b is None else cmp(a, b)
+
+
+class CombinedReader(BaseReader):
+    """readerops.Combined (readers/operators/readerops.py): `a + b`, or a.combine_gaussian(b, std).  It is a reader, so it nests:
+    (r1 + r2) + r1.  variables: those both operands have (in a's order); start_time the later, end_time the earlier of the two;
+    covers_time the AND.  The result is missing wherever an operand is, and there are no vertical profiles (the reference's
+    get_variables_interpolated does not forward `profiles`).  It does not forward `rotate_to_proj` either: the operands' vector
+    pairs are NOT rotated to east / north, the components of a projected grid are added along the grid's own axes
+    (readerops.py:84-101; tools/gen_golden_reader_ops.py records it) -- and so they are here.
+
+    In a model (`device_kind = 'combined'`) every call of get_environment is one launch over the flattened expression
+    (odr_combined_sample); get_variables_interpolated is the NumPy evaluation for expressions whose leaves are all
+    ContinuousReaders."""
+    device_kind = 'combined'
+
+    def __init__(self, a, b, kind='add', std=None):
+        self.a, self.b, self.kind, self.std = a, b, kind, std
+        others = list(b) if isinstance(b, (list, tuple)) else [b]
+        if kind == 'gaussian' and isinstance(b, (list, tuple)):
+            raise NotImplementedError('combine_gaussian with a list of measurement readers: the reference\'s list form could not be '
+                                      'run for a known answer (tools/gen_golden_reader_ops.py); blend towards one measurement reader')
+        if kind == 'gaussian':
+            for r in others:
+                if not (isinstance(r, TimeseriesReader) and hasattr(r, 'lon') and hasattr(r, 'lat')):
+                    raise TypeError('combine_gaussian: the measurement reader must be a TimeseriesReader with lon and lat')
+            stds = np.atleast_1d(np.asarray(std, dtype=np.float64))
+            if len(stds) not in (1, len(others)) or not (np.isfinite(stds).all() and (stds > 0).all()):
+                raise ValueError('combine_gaussian: std must be a positive number, or one per measurement reader')
+            self.stds = [float(stds[k if len(stds) > 1 else 0]) for k in range(len(others))]
+        elif kind != 'add' or isinstance(b, (list, tuple)):
+            raise TypeError('readers are combined with + or combine_gaussian')
+        self.variables = [v for v in a.variables if all(v in r.variables for r in others)]
+        self.start_time, self.end_time = a.start_time, a.end_time
+        for r in others:
+            self.start_time = _none_or(self.start_time, r.start_time, max)
+            self.end_time = _none_or(self.end_time, r.end_time, min)
+        self.name = 'Combined(%s | %s)' % (a.name, b.name)
+        self.xmin, self.xmax, self.ymin, self.ymax = -180, 180, -90, 90
+        self.proj4 = '+proj=latlong'
+        super().__init__()
+
+    def _others(self):
+        return list(self.b) if isinstance(self.b, (list, tuple)) else [self.b]
+
+    def covers_time(self, time):
+        return all(r.covers_time(time) for r in [self.a] + self._others())
+
+    def get_variables_interpolated(self, variables, profiles=None, profiles_depth=None, time=None, lon=None, lat=None, z=None,
+                                   rotate_to_proj=None):
+        assert set(variables).issubset(self.variables), '%s is not subset of %s' % (variables, self.variables)
+        env_a, _ = _interpolated(self.a, variables, time, lon, lat, z)
+        env_b = [_interpolated(r, variables, time, lon, lat, z)[0] for r in self._others()]
+        env = {}
+        for v in variables:
+            if self.kind == 'add':
+                env[v] = env_a[v] + env_b[0][v]
+            else:
+                f = np.stack([gaussian_factor(lon, lat, r.lon, r.lat, s) for r, s in zip(self._others(), self.stds)])
+                env[v] = env_a[v] * (1 - np.sum(f, axis=0)) + np.sum(np.stack([e[v] for e in env_b]) * f, axis=0)
+        return env, None
+
+
+def gaussian_factor(lon, lat, lon_center, lat_center, std):
+    """exp(-(d / std)^2 / 2), d the WGS84 distance to the centre (ops.py:59-94; wgs84_distance)."""
+    lon, lat = np.broadcast_arrays(np.asarray(lon, dtype=np.float64), np.asarray(lat, dtype=np.float64))
+    d = wgs84_distance(lon, lat, float(lon_center), float(lat_center))
+    return np.exp(-np.power(d / float(std), 2.) / 2)
+
+
+def _interpolated(reader, variables, time, lon, lat, z):
+    if not hasattr(reader, 'get_variables_interpolated') or isinstance(reader, StructuredReader):
+        raise NotImplementedError('reader %s is evaluated on the device only: the host evaluation of a reader expression takes '
+                                  'ContinuousReaders as leaves' % reader.name)
+    return reader.get_variables_interpolated(variables, time=time, lon=lon, lat=lat, z=z)
+
+
+class NumCombinedReader:
+    """numops.Combined (readers/operators/numops.py): a reader combined with a number -- n + r, n * r, r / n (r - n is r + (-n)).
+    It is NOT a reader and has no operators of its own, so it is always the root of an expression; everything else is forwarded
+    to its reader.  On the device the result is float64 whatever the operand's class: the reference's operand is a masked array,
+    whose arithmetic makes a 0-d float64 array of the number (tools/gen_golden_reader_ops.py)."""
+    device_kind = 'combined'
+
+    def __init__(self, n, r, op, descop='|'):
+        assert isinstance(n, Number)
+        assert isinstance(r, BaseReader)
+        self.n, self.r, self.op = n, r, op
+        self.name = 'NumCombined(%s %s %s)' % (r.name, descop, n)
+
+    @staticmethod
+    def add(n, r):
+        return NumCombinedReader(n, r, 'add', '+')
+
+    @staticmethod
+    def mul(n, r):
+        return NumCombinedReader(n, r, 'mul', '*')
+
+    @staticmethod
+    def div(n, r):
+        return NumCombinedReader(n, r, 'div', '/')
+
+    def __getattr__(self, attr):
+        if attr in ('n', 'r', 'op'):      # (not set yet: no forwarding loop)
+            raise AttributeError(attr)
+        return getattr(self.r, attr)
+
+    def apply(self, x):
+        return self.n + x if self.op == 'add' else self.n * x if self.op == 'mul' else x / self.n
+
+    def get_variables_interpolated(self, variables, *args, **kwargs):
+        assert set(variables).issubset(self.r.variables), '%s is not a subset of variables in %s' % (variables, self.r.name)
+        env, _ = self.r.get_variables_interpolated(variables, *args, **kwargs)
+        return {v: self.apply(env[v]) for v in variables}, None
+
+
+class FilteredReader(ReaderOperators):
+    """filter.FilterVariables (readers/operators/filter.py): a reader of which only some variables are forwarded."""
+    device_kind = 'combined'
+
+    def __init__(self, r, vars):
+        vars = list(vars)
+        assert set(vars).issubset(r.variables), '%s is not a subset of variables in %s' % (vars, r.name)
+        self.r, self.v = r, vars
+        self.name = 'Filter(%s | %s)' % (r.name, vars)
+
+    @property
+    def variables(self):
+        return self.v
+
+    def __getattr__(self, attr):
+        if attr in ('r', 'v'):
+            raise AttributeError(attr)
+        return getattr(self.r, attr)
+
+
+def expression_postfix(reader):
+    """The expression in postfix, as the device program has it: [(kind, payload, (d0, d1, d2))] with kind one of _abi.COMBINE_* and
+    payload the leaf reader of a SOURCE / UNIFORM / GAUSS_TERM entry."""
+    if isinstance(reader, NumCombinedReader):
+        kind = {'add': _abi.COMBINE_NUM_ADD, 'mul': _abi.COMBINE_NUM_MUL, 'div': _abi.COMBINE_NUM_DIV}[reader.op]
+        return expression_postfix(reader.r) + [(kind, None, (float(reader.n), 0.0, 0.0))]
+    if isinstance(reader, FilteredReader):
+        return expression_postfix(reader.r)
+    if isinstance(reader, CombinedReader):
+        if reader.kind == 'add':
+            return expression_postfix(reader.a) + expression_postfix(reader.b) + [(_abi.COMBINE_ADD, None, (0.0, 0.0, 0.0))]
+        return expression_postfix(reader.a) + [(_abi.COMBINE_GAUSS_TERM, r, (float(r.lon), float(r.lat), s))
+                                               for r, s in zip(reader._others(), reader.stds)] + \
+            [(_abi.COMBINE_GAUSS_END, None, (0.0, 0.0, 0.0))]
+    if isinstance(reader, TimeseriesReader):
+        return [(_abi.COMBINE_UNIFORM, reader, (0.0, 0.0, 0.0))]
+    return [(_abi.COMBINE_SOURCE, reader, (0.0, 0.0, 0.0))]
+
+
+def expression_depth(postfix):
+    """The most values the program holds at once."""
+    depth = deepest = 0
+    for kind, _, _ in postfix:
+        depth += 1 if kind in (_abi.COMBINE_SOURCE, _abi.COMBINE_UNIFORM) else -1 if kind == _abi.COMBINE_ADD else 0
+        deepest = max(deepest, depth)
+    return deepest
+
+
+def check_device_expression(reader):
+    """NotImplementedError, with the reason, for an expression the device program does not take."""
+    name = reader.name
+    post = expression_postfix(reader)
+    for kind, r, _ in post:
+        if kind != _abi.COMBINE_SOURCE:
+            continue
+        dk = getattr(r, 'device_kind', None)
+        if dk in ('umesh', 'shape'):
+            raise NotImplementedError('reader expression %s: operators on a mesh or shape reader (%s) are not built' % (name, r.name))
+        if dk is None and isinstance(r, ContinuousReader):
+            raise NotImplementedError('reader expression %s: leaf %s is a ContinuousReader evaluated on the host; the device '
+                                      'program takes gridded, constant, analytic, landmask and timeseries readers' % (name, r.name))
+        if dk is None and not isinstance(r, StructuredReader):
+            raise NotImplementedError('reader expression %s: leaf %s is no reader the device can sample' % (name, r.name))
+        if any(isinstance(a, (list, tuple)) for a in getattr(r, 'arrays', {}).values()):
+            raise NotImplementedError('reader expression %s: leaf %s hands out ensemble members' % (name, r.name))
+    if expression_depth(post) > _abi.COMBINE_STACK:
+        raise NotImplementedError('reader expression %s is deeper than the device program supports: it would hold %d values at once, '
+                                  'at most %d fit (an accumulator and two saved temporaries)' % (name, expression_depth(post), _abi.COMBINE_STACK))
+    if len(post) > _abi.COMBINE_MAX_OPS:
+        raise NotImplementedError('reader expression %s has %d operations, at most %d fit' % (name, len(post), _abi.COMBINE_MAX_OPS))
+    uniform = {id(r) for kind, r, _ in post if kind in (_abi.COMBINE_UNIFORM, _abi.COMBINE_GAUSS_TERM)}
+    if len(uniform) > _abi.COMBINE_MAX_UNIFORM:
+        raise NotImplementedError('reader expression %s has %d timeseries readers, at most %d fit' % (name, len(uniform), _abi.COMBINE_MAX_UNIFORM))
+    return post
+
+
 def _dev(a):
     """a block array as Context.upload_block_device wants it: the device pointer of a CUDA tensor, else the host array"""
     return int(a.data_ptr()) if hasattr(a, 'is_cuda') and a.is_cuda else a
@@ -917,7 +1261,9 @@ class DeviceReaderBinding:
     NSLOTS = 6        # = MAXLEVELS of the device source: t0, t0 + dt/2 and t0 + dt may each sit between two different levels
     PREFETCH = True   # stage the next time level on the upload stream while the current one is in use
 
-    def __init__(self, ctx, reader, variables=None):
+    def __init__(self, ctx, reader, variables=None, shared=None):
+        """shared: {id(reader): binding} of the bindings the model made for readers added on their own -- a reader expression
+        samples a leaf that is among them through that binding (one source id, one set of resident levels)."""
         self.ctx, self.reader = ctx, reader
         self.variables = [v for v in (variables or reader.variables)]
         self.slots = {}      # time index -> slot
@@ -931,6 +1277,7 @@ class DeviceReaderBinding:
         self._ahead, self._ahead_last = None, None   # sharded run, rank 0: the next level read on a worker thread (ReadAhead)
         self.mesh = None               # device.UMesh of an UnstructuredReader
         self.shape = None              # device.Shape of a ShapeReader
+        self.leaves = None             # a reader expression: [(leaf reader, its binding, made here and not shared)]
         kind = getattr(reader, 'device_kind', None)
         # a ContinuousReader the device has no closed form for (a user's analytic or point-wise reader,
         # basereader/continuous.py:20-46): evaluated on the host at the element positions, values uploaded
@@ -958,9 +1305,30 @@ class DeviceReaderBinding:
             self.sid = None
             self.shape = ctx.shape(reader.x1, reader.y1, reader.x2, reader.y2, reader.poly, reader.n_polygons,
                                    proj=projection.parse_proj4(reader.proj4), invert=reader.invert)
+        elif kind == 'combined':
+            # a reader expression (CombinedReader, NumCombinedReader, FilteredReader): no source of its own; every leaf the device
+            # samples has a binding -- the model's, when the same reader object was also added on its own and delivers the
+            # expression's variables, else one made here -- and the whole expression is one launch behind the priority-list
+            # walk (sample_combined).  Timeseries leaves are resolved on the host, per call.
+            self.sid = None
+            self.host_eval = False
+            self.postfix = check_device_expression(reader)
+            self.leaves, self.program, self._program_key = [], None, None
+            for op, leaf, _ in self.postfix:
+                if op != _abi.COMBINE_SOURCE or any(leaf is r for r, _, _ in self.leaves):
+                    continue
+                b = (shared or {}).get(id(leaf))
+                if b is not None and set(self.variables) <= set(b.variables):
+                    self.leaves.append((leaf, b, False))
+                else:
+                    self.leaves.append((leaf, DeviceReaderBinding(ctx, leaf, variables=[v for v in leaf.variables if v in self.variables]), True))
+            self.uniform = []            # the timeseries readers, in the order of their uniform-leaf index
+            for op, leaf, _ in self.postfix:
+                if op in (_abi.COMBINE_UNIFORM, _abi.COMBINE_GAUSS_TERM) and not any(leaf is r for r in self.uniform):
+                    self.uniform.append(leaf)
         else:
             self.sid = None  # created with the first block (the grid comes with it)
-        if kind and kind not in ('umesh', 'shape') and reader.start_time is not None:
+        if kind and kind not in ('umesh', 'shape', 'combined') and reader.start_time is not None:
             ctx.set_time_coverage(self.sid, _epoch(reader.start_time), _epoch(reader.end_time), reader.always_valid)
 
     def _static_ids(self):
@@ -1065,6 +1433,9 @@ class DeviceReaderBinding:
     def close_read_ahead(self):
         """End of the run, a re-cut window, a discarded reader: the worker's read in flight is waited for (the caller may close
         the reader's file afterwards) and the pool is shut down; a later read starts a new one."""
+        for _, b, own in (self.leaves or ()):
+            if own:
+                b.close_read_ahead()
         a, self._ahead = self._ahead, None
         if a is not None:
             self._ahead_stats = tuple(x + y for x, y in zip(getattr(self, '_ahead_stats', (0, 0, 0.0)), (a.hits, a.misses, a.worker_s)))
@@ -1086,6 +1457,11 @@ class DeviceReaderBinding:
         step samples THIS reader at (default: t0, the middle and t1 -- a Runge-Kutta-4 step of a reader that holds the
         current; the model passes [t0] for Euler and for readers the stages do not sample)."""
         r = self.reader
+        if self.leaves is not None:      # the leaves made here; a shared leaf is the model's to keep resident
+            for _, b, own in self.leaves:
+                if own:
+                    b.ensure_levels(t0, t1, extent=extent, broadcast=broadcast, times=times)
+            return
         if self.mesh is not None:
             return self._ensure_mesh_levels(times if times is not None else (t0, t0 + (t1 - t0) / 2, t1))
         if extent is None:
@@ -1195,6 +1571,36 @@ class DeviceReaderBinding:
         """The polygons' land_binary_mask for the particle set P, merged into its environment slot by priority (first: the reader
         heads the variable's list) -- on the device, one launch (odr_shape_sample).  The reader is valid at every time."""
         P.shape_sample(self.shape, first)
+
+    def sample_combined(self, P, variables, first, time):
+        """The expression's values for the particle set P at `time`, merged into its environment slots by priority (first[k]: the
+        expression heads the list of variable k) -- on the device, one launch per eight variables (odr_combined_sample).  Outside
+        the expression's time coverage nothing is sampled.  The levels of every gridded leaf that bracket `time` are made
+        resident here, at the time of the call; the program is rebuilt when a leaf's source id changed (its first block, a re-cut
+        window)."""
+        r = self.reader
+        if not r.covers_time(time):
+            return
+        for _, b, _ in self.leaves:
+            if b.is_grid():
+                b.ensure_levels(time, time, times=[time])
+        sids = tuple(b.sid for _, b, _ in self.leaves)
+        if any(sid is None for sid in sids):
+            raise RuntimeError('reader expression %s: a leaf has no device source at %s' % (r.name, time))
+        if self.program is None or self._program_key != sids:
+            if self.program is not None:
+                self.program.close()
+            sid_of = {id(leaf): b.sid for leaf, b, _ in self.leaves}
+            uni_of = {id(leaf): k for k, leaf in enumerate(self.uniform)}
+            self.program = self.ctx.combined([(op, sid_of[id(leaf)] if op == _abi.COMBINE_SOURCE else uni_of.get(id(leaf), 0), d)
+                                              for op, leaf, d in self.postfix])
+            self._program_key = sids
+        # (no vector pair has to stay together: the reference's Combined does not rotate its operands, see CombinedReader)
+        ordered, flag, t = list(variables), dict(zip(variables, first)), _epoch(time)
+        for o in range(0, len(ordered), _abi.COMBINE_MAX_VARIABLES):
+            vs = ordered[o:o + _abi.COMBINE_MAX_VARIABLES]
+            uniform = [[leaf.value(v, time) for leaf in self.uniform] for v in vs] if self.uniform else None
+            P.combined_sample(self.program, vs, [flag[v] for v in vs], t, uniform)
 
     def _read_and_broadcast(self, k, x, y, async_op):
         """Sharded run: rank 0 reads time level k, every rank receives it.  A reader failure on rank 0 reaches every rank as
