@@ -749,6 +749,13 @@ int odr_particles_vmix_kplane_stats(odr_ctx *ctx, odr_particles *p, uint64_t *ou
  *         resident levels (read from the device: waits for the stream)}.
  * The environment variable ODR_NO_VMIX_WINDOW=1 keeps every such launch on the whole column. */
 int odr_particles_vmix_window_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out3);
+/* The launches of the K-column kernel (k_vmix_col, every configuration) since the set was created.  A workgroup of that kernel
+ * owns a tile of 4 x 256 consecutive elements, leaves out those the launch cannot change -- z == 0 on entry while the call does
+ * not mix at the surface, does not advect the surface vertically and the sea floor is not above the surface: the launch stores
+ * z = +0.0 for them whatever their column holds -- and mixes the rest densely packed:
+ * out2 = {tiled launches, elements they skipped (read from the device: waits for the stream)}.
+ * The environment variable ODR_NO_VMIX_SKIP=1 keeps the tiling and skips no element. */
+int odr_particles_vmix_skip_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out2);
 /* counts and min/max used for the per-step log line and early-outs (:2212-2233):
  * out16 = {n_active, lon_min, lon_max, lat_min, lat_max, z_min, z_max, D_max, stokes_sum_max,
  *          wind_speed_max, wdf_surface_max, n_surface, hs_max, tp_max, 0, 0} */

@@ -39,11 +39,11 @@ constexpr int BLOCK = ODR_BLOCK;  // threads per workgroup (A/B builds may overr
 // the natural order the eight L2s all stream the whole (spatially sorted) particle range and every field tile is
 // fetched by all of them.  pid() gives XCD x the x-th contiguous eighth of the range instead: the particles of one
 // region -- and the field records they gather -- stay in one L2.
-__device__ __forceinline__ long long pid() {
+__device__ __forceinline__ unsigned pid_wg() {   // the workgroup's place in that order
   const unsigned nb = gridDim.x, b = blockIdx.x, per = nb >> 3, rem = nb & 7u, x = b & 7u, j = b >> 3;
-  const unsigned lb = x * per + (x < rem ? x : rem) + j;
-  return (long long)lb * BLOCK + threadIdx.x;
+  return x * per + (x < rem ? x : rem) + j;
 }
+__device__ __forceinline__ long long pid() { return (long long)pid_wg() * BLOCK + threadIdx.x; }
 
 struct PView {  // device pointers of the active set
   long long n;
@@ -478,9 +478,11 @@ struct VMixDesc {
   const float *kb, *ka;  // K of the bracketing time levels (ka == nullptr: on a time level): the levels' K planes when every
                          // resident level has one (DevBlock::kplane), else the K part of their node records
   double wgt;            // weight_after (structured.py:353-354)
-  float Kfb, pad2;
+  float Kfb;
+  int noskip;            // k_vmix_col: no element is skipped at the surface (ODR_NO_VMIX_SKIP=1; the tiling stays)
   const unsigned long long *guard;   // nullptr, or: the launch does nothing unless *guard != 0 (odr_ctx_guard_next_vmix)
   unsigned long long *redone;        // a two-quad launch (VMixC3W) counts the elements it redid on the whole column here
+  unsigned long long *skipped;       // k_vmix_col counts the elements it skipped at the surface here (nullptr: not counted)
 };
 
 // The configuration of k_vmix_col -- the K source's longitude convention, projection, level count and level spacing, and the
@@ -2030,7 +2032,10 @@ __device__ __forceinline__ bool vmix_col_particle(const DevSource &s, const PVie
   vmix_col_fill<NQ, TL, VM>(s, D, slon, slat, Kp, tid, win.q0, [&]() { R0 = mix_rng_begin<VM>(A, id0); });
   int sf_flags = VM::sf_action(sfl & 255) == 5 ? sf_species_flag(p, sfl, i) : 0;
   const float Zmin = __fmul_rn(-1.f, __fadd_rn(dep0, ssh0));  // float32 (:408)
-  double z = vmix_col_walk<NQ, VM>(s, nzp, Kp, gsh, tid, A, i, p.n, id0, z0, moving, Zmin, tv0, sf_flags, &R0,
+  // (the run-time configuration reads the terminal velocity here: held through the fill of its longest columns it was the one
+  // value that went to scratch memory at 80 registers; the static ones keep it in the state's round trip)
+  const float tv1 = VM::STATIC ? tv0 : p.tv[i];
+  double z = vmix_col_walk<NQ, VM>(s, nzp, Kp, gsh, tid, A, i, p.n, id0, z0, moving, Zmin, tv1, sf_flags, &R0,
                                    VM::WINDOW ? &win : nullptr);
   if (VM::WINDOW && win.escaped) return true;
   if (sf_flags & 1) {   // deactivate_elements(reason='seafloor') (basemodel/__init__.py:1774-1795)
@@ -2050,6 +2055,38 @@ __device__ __forceinline__ bool vmix_col_particle(const DevSource &s, const PVie
   p.z[i] = z;
   return false;
 }
+// A workgroup of k_vmix_col owns a TILE of VMIX_TILE_ROUNDS * BLOCK consecutive elements (tiles in the XCD-contiguous order of
+// pid()), drops the elements the launch cannot change, and runs the rest densely packed.  An element that enters with z == 0
+// while the call does not mix at the surface and the fused vertical advection leaves the surface alone (vadv != 1) ends every
+// sub-step in z = 0.0 (vmix_col_walk: "if (!mix_at_surface && surface) z = 0.0") unless the sea floor is above the surface
+// (Zmin > 0; a NaN Zmin never compares): no flag, no status, nothing but z = +0.0 comes out of it, whatever its column holds.
+// C3's vertical advection clips upwelled elements to the surface, where the reference's rule then keeps them -- a third of the
+// elements after 200 steps -- but the re-sort orders by horizontal cell only, so they sit scattered through every wave, and an
+// issue-bound launch gains nothing from predicated lanes.  The tile's elements are therefore compacted, stably (neighbours in
+// memory stay neighbours in a wave: the gathers stay local): one ballot per round and wave, an exclusive prefix over the
+// (round, wave) counts through LDS, and a list of tile-relative 16-bit offsets in LDS.  Pass r hands thread tid the entry
+// r BLOCK + tid; a wave without an entry leaves (wave-uniform).  LDS per workgroup: column and tables + 4 BLOCK x 2 bytes of list
+// + 64 bytes of counts (12 levels: 24 960 + 2 048 + 64 = 27 072 <= 163 840 / 6: six workgroups per CU stay resident).
+constexpr int VMIX_TILE_ROUNDS = 4;
+constexpr int VMIX_TILE = VMIX_TILE_ROUNDS * BLOCK;
+static_assert(VMIX_TILE <= 65536, "tile-relative offsets are 16 bits");
+// dynamic LDS of a k_vmix_col<NQ> workgroup: K column [4 NQ][BLOCK] and tables [4][4 NQ] (float64), offset list, counts
+__host__ __device__ constexpr size_t vmix_col_lds_bytes(int nq) {
+  return sizeof(double) * ((size_t)(4 * nq) * BLOCK + 4 * (size_t)(4 * nq)) + sizeof(unsigned short) * VMIX_TILE +
+         sizeof(unsigned) * VMIX_TILE_ROUNDS * (BLOCK / 64);
+}
+// a launch constant at the head of a pass: the same bits, still one scalar per wave, but nothing derived from it can be moved
+// out of the loop over the passes
+__device__ __forceinline__ float vmix_per_pass(float v) {
+  asm volatile("" : "+v"(v));
+  return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v)));
+}
+__device__ __forceinline__ double vmix_per_pass(double v) {
+  asm volatile("" : "+v"(v));
+  const long long b = __double_as_longlong(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)b), hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(b >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
 // VM: the mixing configuration (VMixRT / VMixC3 above)
 template <int NQ, bool TL, class VM = VMixRT>
 __global__ __launch_bounds__(BLOCK, ODR_VMIX_WAVES) void k_vmix_col(const DevWorld *__restrict__ W, PView p, VMixDesc D,
@@ -2057,37 +2094,117 @@ __global__ __launch_bounds__(BLOCK, ODR_VMIX_WAVES) void k_vmix_col(const DevWor
                                                     int rng_mode, const double *__restrict__ huni,
                                                     unsigned long long seed, unsigned long long step,
                                                     int vadv, int sfl) {
-  constexpr int NL = 4 * NQ;
+  constexpr int NL = 4 * NQ, NW = BLOCK / 64;
   extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x;
-  const DevSource &s = W->src[D.sid];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int nzp = VM::nzp(D.nzp, NL);
   double *Kp = (double *)smem;              // [NL][BLOCK]
   double *gsh = Kp + (size_t)NL * BLOCK;    // [4][NL]
-  // the particle's state is requested first: its loads and the tables' are one round trip (threads past the end read element 0)
+  unsigned short *list = (unsigned short *)(gsh + 4 * NL);   // [VMIX_TILE] tile-relative offsets of the elements to mix, ascending
+  unsigned *cnt = (unsigned *)(list + VMIX_TILE);            // [VMIX_TILE_ROUNDS][NW] of them per round and wave
   if (D.guard && *D.guard == 0ull) return;   // (wave-uniform: the launch was enqueued before the host knew whether it may run)
-  const long long i = pid();
-  const bool valid = i < p.n;
-  const VMixState S = vmix_load_state(p, valid ? i : 0);
+  const long long base = (long long)pid_wg() * VMIX_TILE;
+  // what decides the skip is requested first, coalesced, four elements per thread: its loads and the tables' are one round trip
+  // (elements past the end read element 0).  Static configurations fold the two tests on the call's settings away.
+  const bool may_skip = VM::mix_at_surface(mix_at_surface) == 0 && VM::vadv(vadv) != 1 && !D.noskip;
+  unsigned long long keep[VMIX_TILE_ROUNDS];
+  if (may_skip) {
+    double z[VMIX_TILE_ROUNDS];
+    float dep[VMIX_TILE_ROUNDS], ssh[VMIX_TILE_ROUNDS];
+#pragma unroll
+    for (int r = 0; r < VMIX_TILE_ROUNDS; ++r) {
+      const long long e = base + r * BLOCK + tid, ec = e < p.n ? e : 0;
+      z[r] = p.z[ec]; dep[r] = p.env[VAR_DEPTH][ec]; ssh[r] = p.env[VAR_SSH][ec];
+    }
+    // a walk of no sub-step hands z back as it came: only then a -0.0 stays (sub-step count as vmix_col_walk forms it)
+    const double sgn = dt > 0 ? 1.0 : (dt < 0 ? -1.0 : 0.0);
+    const bool walks = VM::ntimes(abs((int)(dt / (dt_mix_cfg * sgn)))) > 0;
+#pragma unroll
+    for (int r = 0; r < VMIX_TILE_ROUNDS; ++r) {
+      const long long e = base + r * BLOCK + tid;
+      const float Zmin = __fmul_rn(-1.f, __fadd_rn(dep[r], ssh[r]));  // (vmix_col_particle's)
+      const bool skip = e < p.n && z[r] == 0 && !(Zmin > 0.f);
+      // the launch stores z = +0.0 for it: all there is to do when -0.0 came in
+      if (skip && walks && __double_as_longlong(z[r]) != 0ll) p.z[e] = 0.0;
+      keep[r] = __ballot(e < p.n && !skip);
+    }
+  } else {
+#pragma unroll
+    for (int r = 0; r < VMIX_TILE_ROUNDS; ++r) keep[r] = __ballot(base + r * BLOCK + tid < p.n);
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int r = 0; r < VMIX_TILE_ROUNDS; ++r) cnt[r * NW + wave] = (unsigned)__popcll(keep[r]);
+  }
   if (tid < nzp) {
+    const DevSource &s = W->src[D.sid];
     gsh[tid] = s.vg_a[tid]; gsh[NL + tid] = s.vg_b[tid]; gsh[2 * NL + tid] = s.vg_c[tid];
     gsh[3 * NL + tid] = s.zmid[tid];     // level boundaries (entries >= nzp - 1 are not read)
   }
   __syncthreads();
-  if (!valid) return;  // no barrier below: every thread touches only its own LDS column
-  VMixArgs A;
-  A.dt = dt; A.dt_mix_cfg = dt_mix_cfg; A.mix_at_surface = mix_at_surface; A.rng_mode = rng_mode; A.sfl = sfl; A.pad = 0;
-  A.huni = huni; A.seed = seed; A.step = step;
-  const bool escaped = vmix_col_particle<NQ, TL, VM>(s, p, D, A, vadv, i, Kp, gsh, tid, S);
-  if constexpr (VM::WINDOW) {
-    // the lanes a two-quad pass could not finish (rare: none in C3's field) run the whole-column routine from scratch, their
-    // state read again -- nothing of them has been stored, so the result is that launch's; one atomic per wave counts them
-    const unsigned long long esc = __ballot(escaped);
-    if (esc != 0ull) {
-      if (escaped) {
-        const VMixState S2 = vmix_load_state(p, i);
-        vmix_col_particle<NQ, TL, typename VM::Full>(s, p, D, A, vadv, i, Kp, gsh, tid, S2);
-        if (D.redone && (tid & 63) == __ffsll((long long)esc) - 1) atomicAdd(D.redone, (unsigned long long)__popcll(esc));
+  // exclusive prefix over the (round, wave) counts, in that order; the kept elements of this wave's rounds go behind theirs
+  unsigned total = 0, off[VMIX_TILE_ROUNDS];
+#pragma unroll
+  for (int r = 0; r < VMIX_TILE_ROUNDS; ++r) {
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      if (w == wave) off[r] = total;
+      total += cnt[r * NW + w];
+    }
+  }
+  if (tid == 0 && D.skipped) {   // one atomic per workgroup that skipped any
+    const long long left = p.n - base;
+    const unsigned in_tile = left < (long long)VMIX_TILE ? (unsigned)left : (unsigned)VMIX_TILE;
+    if (in_tile > total) atomicAdd(D.skipped, (unsigned long long)(in_tile - total));
+  }
+  total = __builtin_amdgcn_readfirstlane(total);   // (the same in every lane: a scalar for the passes' bounds)
+  if (total == 0) return;   // (workgroup-uniform)
+  const unsigned long long below = (1ull << lane) - 1ull;
+#pragma unroll
+  for (int r = 0; r < VMIX_TILE_ROUNDS; ++r)
+    if ((keep[r] >> lane) & 1ull) list[off[r] + (unsigned)__popcll(keep[r] & below)] = (unsigned short)(r * BLOCK + tid);
+  __syncthreads();
+  const DevSource &s = W->src[D.sid];
+  // no barrier below: every thread touches only its own LDS column, pass after pass
+  const unsigned wave0 = (unsigned)__builtin_amdgcn_readfirstlane(tid - lane);   // the wave's first thread: a scalar
+#pragma unroll 1
+  for (unsigned e0 = 0; e0 + wave0 < total; e0 += BLOCK) {   // (wave-uniform: a wave without an entry leaves)
+    // What a particle's routine derives from the launch's constants alone -- 1 - wgt, the fallback K as float64, the sub-steps'
+    // factors -- is derived again in every pass, as the one pass of a thread did before the tiles: hoisted out of this loop
+    // those values occupy vector registers across it, and the routine no longer fits its 80 (vmix_per_pass).
+    VMixDesc Dp = D;
+    Dp.wgt = vmix_per_pass(D.wgt); Dp.Kfb = vmix_per_pass(D.Kfb);
+    VMixArgs A;
+    A.dt = vmix_per_pass(dt); A.dt_mix_cfg = vmix_per_pass(dt_mix_cfg);
+    A.mix_at_surface = mix_at_surface; A.rng_mode = rng_mode; A.sfl = sfl; A.pad = 0;
+    A.huni = huni; A.seed = seed; A.step = step;
+    // (likewise the thread's number: formed again from the wave's scalar and the lane's count, no vector register carries it
+    // or any of the forms the routine takes of it from pass to pass)
+    int t;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=&v"(t));
+    t += (int)wave0;
+    const unsigned e = e0 + (unsigned)t;
+    long long i = 0;
+    bool escaped = false;
+    if (e < total) {
+      i = base + list[e];
+      long long i1 = i;   // (opaque: the addresses of the loads are not kept for the stores, which form theirs from i)
+      asm volatile("" : "+v"(i1));
+      const VMixState S = vmix_load_state(p, i1);
+      escaped = vmix_col_particle<NQ, TL, VM>(s, p, Dp, A, vadv, i, Kp, gsh, t, S);
+    }
+    if constexpr (VM::WINDOW) {
+      // the lanes a two-quad pass could not finish (rare: none in C3's field) run the whole-column routine from scratch, their
+      // state read again -- nothing of them has been stored, so the result is that launch's; one atomic per wave counts them
+      const unsigned long long esc = __ballot(escaped);
+      if (esc != 0ull) {
+        if (escaped) {
+          long long i2 = i;
+          asm volatile("" : "+v"(i2));
+          const VMixState S2 = vmix_load_state(p, i2);
+          vmix_col_particle<NQ, TL, typename VM::Full>(s, p, Dp, A, vadv, i, Kp, gsh, t, S2);
+          if (D.redone && (t & 63) == __ffsll((long long)esc) - 1) atomicAdd(D.redone, (unsigned long long)__popcll(esc));
+        }
       }
     }
   }

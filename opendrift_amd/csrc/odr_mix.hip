@@ -3,6 +3,9 @@
 #define ODR_TU_MIX 1
 #include "odr_host.h"
 
+// (the 12-level launch keeps six workgroups per CU resident: its dynamic LDS, vmix_col_lds_bytes, within a sixth of 160 KB)
+static_assert(vmix_col_lds_bytes(3) <= 163840 / ODR_VMIX_WAVES, "k_vmix_col<3>: column, tables and offset list exceed a sixth of the LDS");
+
 // the K source and the call's settings are exactly the static mixing configuration VM (odr_kernels.hip.h VMixC3): every
 // run-time value equals its constant, the column has no padding level (nzp = 4 nq).  (ntimes as vmix_col_walk forms it)
 template <class VM>
@@ -113,9 +116,14 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
     p->vmix_kplane[kplanes ? 0 : 1]++;
     if (spec && nq == 3) p->vmix_window[quadwin ? 0 : 1]++;
     D.redone = quadwin ? p->vmix_redone : nullptr;
+    // k_vmix_col: a workgroup per tile of VMIX_TILE elements, those at the surface that the launch cannot change left out
+    // (odr_particles_vmix_skip_stats); ODR_NO_VMIX_SKIP=1 keeps the tiling and skips none (A/B runs and tests)
+    D.skipped = p->vmix_redone + 1;
+    D.noskip = getenv("ODR_NO_VMIX_SKIP") ? 1 : 0;
+    if (!win) { g = dim3((unsigned)((p->n + VMIX_TILE - 1) / VMIX_TILE)); p->vmix_tiled++; }
 #define VMIX_COL(NQ, VM)                                                                                          \
   do {                                                                                                            \
-    size_t l2 = sizeof(double) * ((size_t)(4 * NQ) * BLOCK + 4 * (size_t)(4 * NQ));                               \
+    const size_t l2 = vmix_col_lds_bytes(NQ);                                                                     \
     if (tl) hipLaunchKernelGGL((k_vmix_col<NQ, true, VM>), g, b, l2, c->stream, c->dw, v, D, dt, dt_mix,          \
                                mix_at_surface, rng_mode, du, c->seed, st, vadv, c->seafloor);                                  \
     else hipLaunchKernelGGL((k_vmix_col<NQ, false, VM>), g, b, l2, c->stream, c->dw, v, D, dt, dt_mix,            \
@@ -165,6 +173,15 @@ int odr_particles_vmix_layout_stats(odr_ctx *c, odr_particles *p, uint64_t *out3
 int odr_particles_vmix_kplane_stats(odr_ctx *c, odr_particles *p, uint64_t *out2) {
   REQUIRE(c && p && out2, "NULL argument");
   out2[0] = p->vmix_kplane[0]; out2[1] = p->vmix_kplane[1];
+  return 0;
+}
+
+int odr_particles_vmix_skip_stats(odr_ctx *c, odr_particles *p, uint64_t *out2) {
+  REQUIRE(c && p && out2, "NULL argument");
+  unsigned long long skipped = 0;
+  D2H(&skipped, p->vmix_redone + 1, sizeof skipped);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  out2[0] = p->vmix_tiled; out2[1] = skipped;
   return 0;
 }
 

@@ -133,8 +133,8 @@ int odr_particles_create(odr_ctx *c, int64_t capacity, odr_particles **out) {
   HIPCHK(hipMalloc((void **)&p->bcount, sizeof(unsigned) * (size_t)(nblk(capacity) + 1)));
   HIPCHK(hipMalloc((void **)&p->wcount, sizeof(unsigned) * (size_t)(nblk(capacity) + 1) * (BLOCK / 64)));
   p->wcount_epoch = ~0ull;
-  HIPCHK(hipMalloc((void **)&p->vmix_redone, sizeof(unsigned long long)));
-  HIPCHK(hipMemset(p->vmix_redone, 0, sizeof(unsigned long long)));
+  HIPCHK(hipMalloc((void **)&p->vmix_redone, 2 * sizeof(unsigned long long)));
+  HIPCHK(hipMemset(p->vmix_redone, 0, 2 * sizeof(unsigned long long)));
   *out = p;
   return 0;
 }

@@ -1446,6 +1446,14 @@ class Particles:
         check(self.lib.odr_particles_vmix_window_stats(self.ctx.h, self.h, out))
         return dict(windowed=int(out[0]), full=int(out[1]), redone=int(out[2]))
 
+    def vmix_skip_stats(self):
+        """The tiled K-column launches (odr_particles_vmix_skip_stats) and the elements they skipped at the surface: z == 0
+        on entry with no mixing and no vertical advection at the surface, for which the launch stores z = +0.0 anyway."""
+        import ctypes as C
+        out = (C.c_uint64 * 2)()
+        check(self.lib.odr_particles_vmix_skip_stats(self.ctx.h, self.h, out))
+        return dict(launches=int(out[0]), skipped=int(out[1]))
+
     def reduce_global(self, combine, wind_drift_depth=0.1, relative_wind=False):
         """Sharded run: this set's raw reductions -> combine(raw16) over the ranks (counts summed, maxima maximised) ->
         installed for the movers that follow, until reduce_unpin()."""
