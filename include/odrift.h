@@ -756,6 +756,13 @@ int odr_particles_vmix_window_stats(odr_ctx *ctx, odr_particles *p, uint64_t *ou
  * out2 = {tiled launches, elements they skipped (read from the device: waits for the stream)}.
  * The environment variable ODR_NO_VMIX_SKIP=1 keeps the tiling and skips no element. */
 int odr_particles_vmix_skip_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out2);
+/* A static configuration of that kernel whose settings allow the skip compacts the whole launch instead of each tile: three small
+ * kernels build one ascending list of the elements to mix on the device, and a one-element-per-thread launch (k_vmix_dense)
+ * runs over it; its grid covers every element, the list's length is never read back.  Such a launch counts as a tiled launch
+ * in odr_particles_vmix_skip_stats too, and its skipped elements count there.
+ * out2 = {dense launches, elements they listed (read from the device: waits for the stream)}.
+ * The environment variable ODR_NO_VMIX_DENSE=1 keeps the tiled launch. */
+int odr_particles_vmix_dense_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out2);
 /* counts and min/max used for the per-step log line and early-outs (:2212-2233):
  * out16 = {n_active, lon_min, lon_max, lat_min, lat_max, z_min, z_max, D_max, stokes_sum_max,
  *          wind_speed_max, wdf_surface_max, n_surface, hs_max, tp_max, 0, 0} */

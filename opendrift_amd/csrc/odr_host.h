@@ -181,8 +181,12 @@ struct odr_particles {
   unsigned long long vmix_launches[3];       // host: odr_vmix launches of k_vmix_col with the run-time configuration [0], a static one [1], of the other mixing kernels [2]
   unsigned long long vmix_kplane[2];         // host: odr_vmix launches of k_vmix_col / k_vmix_win that gathered K from the levels' K planes [0], from the node records [1]
   unsigned long long vmix_window[2];         // host: static 12-level launches of k_vmix_col that gathered two K quads per particle [0], the whole column [1]
-  unsigned long long vmix_tiled;             // host: launches of k_vmix_col (every one compacts its tiles)
-  unsigned long long *vmix_redone;           // device: [0] elements the two-quad launches redid on the whole column, [1] elements k_vmix_col skipped at the surface
+  unsigned long long vmix_tiled;             // host: launches of k_vmix_col (every one compacts its tiles) and of k_vmix_dense
+  unsigned long long vmix_dense;             // host: dense mixing launches (k_vmix_dense behind the three list kernels); each counts in vmix_tiled too
+  unsigned long long *vmix_redone;           // device: [0] elements the two-quad launches redid on the whole column, [1] elements the mixing launches skipped at the surface,
+                                             // [2] elements the dense launches listed, [3] two words: length of the last list, workgroups it fills (VMixKeep::hdr)
+  unsigned long long *vmix_mask;             // device, by capacity: the dense launch's keep ballots, tile counts / offsets and list (VMixKeep)
+  unsigned *vmix_toff, *vmix_list;
   double *z_keep;       // odr_particles_truncate_z: the elements' own z while the sampling calls see the clipped one
   long long z_keep_n;
   bool z_truncated;

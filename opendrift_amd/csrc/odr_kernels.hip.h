@@ -39,10 +39,11 @@ constexpr int BLOCK = ODR_BLOCK;  // threads per workgroup (A/B builds may overr
 // the natural order the eight L2s all stream the whole (spatially sorted) particle range and every field tile is
 // fetched by all of them.  pid() gives XCD x the x-th contiguous eighth of the range instead: the particles of one
 // region -- and the field records they gather -- stay in one L2.
-__device__ __forceinline__ unsigned pid_wg() {   // the workgroup's place in that order
-  const unsigned nb = gridDim.x, b = blockIdx.x, per = nb >> 3, rem = nb & 7u, x = b & 7u, j = b >> 3;
+__device__ __forceinline__ unsigned pid_wg_of(unsigned nb) {   // the workgroup's place in that order among the first nb of the grid
+  const unsigned b = blockIdx.x, per = nb >> 3, rem = nb & 7u, x = b & 7u, j = b >> 3;
   return x * per + (x < rem ? x : rem) + j;
 }
+__device__ __forceinline__ unsigned pid_wg() { return pid_wg_of(gridDim.x); }
 __device__ __forceinline__ long long pid() { return (long long)pid_wg() * BLOCK + threadIdx.x; }
 
 struct PView {  // device pointers of the active set
@@ -2205,6 +2206,193 @@ __global__ __launch_bounds__(BLOCK, ODR_VMIX_WAVES) void k_vmix_col(const DevWor
           vmix_col_particle<NQ, TL, typename VM::Full>(s, p, Dp, A, vadv, i, Kp, gsh, t, S2);
           if (D.redone && (t & 63) == __ffsll((long long)esc) - 1) atomicAdd(D.redone, (unsigned long long)__popcll(esc));
         }
+      }
+    }
+  }
+}
+
+// ---- The dense mixing launch: the same skip (see k_vmix_col) with the compaction over the WHOLE launch instead of per tile.
+// Three small kernels in front of the mixing launch build one stable list of the elements to mix -- k_vmix_keep: the predicate,
+// a 64-bit keep ballot per 64 consecutive elements and a count per tile of VMIX_TILE; k_vmix_keep_scan: the exclusive prefix
+// over the tile counts, the total and the workgroups it fills; k_vmix_keep_fill: the kept indices, ascending (neighbours in
+// memory stay neighbours in a wave) -- and k_vmix_dense runs the one-element-per-thread routine over list[0 .. total): no
+// loop over passes, no offset list in LDS, no workgroup that waits for its slowest pass.  The host sizes the mixing launch for
+// every element without reading the total back; the workgroups past the list return at once.  No workgroup of any of these
+// kernels waits for another one.  Static configurations only (odr_vmix); everything else keeps k_vmix_col.
+struct VMixKeep {
+  unsigned long long *mask;    // [16 per tile] keep ballot of elements 64 g .. 64 g + 63 (bits past the end: 0)
+  unsigned *toff;              // [tiles] k_vmix_keep: kept elements of the tile; after k_vmix_keep_scan: kept elements before it
+  unsigned *list;              // [capacity] indices of the elements to mix, ascending
+  unsigned *hdr;               // [0] length of the list, [1] workgroups of BLOCK that it fills
+  unsigned long long *listed;  // running sum of the list lengths (odr_particles_vmix_dense_stats)
+};
+__global__ __launch_bounds__(BLOCK) void k_vmix_keep(PView p, VMixKeep K, const unsigned long long *guard, double dt,
+                                                      double dt_mix_cfg) {
+  if (guard && *guard == 0ull) return;   // (a guarded launch that may not run changes nothing: see k_vmix_col)
+  constexpr int NW = BLOCK / 64;
+  __shared__ unsigned cnt[NW];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long base = (long long)blockIdx.x * VMIX_TILE;
+  double z[VMIX_TILE_ROUNDS];
+  float dep[VMIX_TILE_ROUNDS], ssh[VMIX_TILE_ROUNDS];
+#pragma unroll
+  for (int r = 0; r < VMIX_TILE_ROUNDS; ++r) {   // coalesced, four elements per thread (elements past the end read element 0)
+    const long long e = base + r * BLOCK + tid, ec = e < p.n ? e : 0;
+    z[r] = p.z[ec]; dep[r] = p.env[VAR_DEPTH][ec]; ssh[r] = p.env[VAR_SSH][ec];
+  }
+  // a walk of no sub-step hands z back as it came: only then a -0.0 stays (sub-step count as vmix_col_walk forms it)
+  const double sgn = dt > 0 ? 1.0 : (dt < 0 ? -1.0 : 0.0);
+  const bool walks = abs((int)(dt / (dt_mix_cfg * sgn))) > 0;
+  unsigned mine = 0;
+#pragma unroll
+  for (int r = 0; r < VMIX_TILE_ROUNDS; ++r) {
+    const long long e = base + r * BLOCK + tid;
+    const float Zmin = __fmul_rn(-1.f, __fadd_rn(dep[r], ssh[r]));  // (vmix_col_particle's)
+    const bool skip = e < p.n && z[r] == 0 && !(Zmin > 0.f);
+    // the mixing launch would store z = +0.0 for it: all there is to do when -0.0 came in
+    if (skip && walks && __double_as_longlong(z[r]) != 0ll) p.z[e] = 0.0;
+    const unsigned long long keep = __ballot(e < p.n && !skip);
+    if (lane == 0) K.mask[(size_t)blockIdx.x * (VMIX_TILE / 64) + r * NW + wave] = keep;
+    mine += (unsigned)__popcll(keep);
+  }
+  if (lane == 0) cnt[wave] = mine;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned t = 0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) t += cnt[w];
+    K.toff[blockIdx.x] = t;
+  }
+}
+// Exclusive prefix over the tile counts by ONE workgroup, VMIX_SCAN_ROWS rows of 1024 counts at a time (k_cmp_scan's scheme:
+// thread t owns counts t, t + 1024, ... of the batch, all of its loads in flight together; every row is scanned wave by wave
+// with shuffles, the wave totals by the first wave, which carries the running total from batch to batch).  Writes the list's
+// length and the workgroups it fills, and adds n - length to `skipped` and the length to K.listed.  A guarded launch that may
+// not run leaves a list of length 0 and the counters alone.
+constexpr int VMIX_SCAN_ROWS = 16;   // x 1024 tiles x 1024 elements = 16.8 M elements per batch
+__global__ __launch_bounds__(1024) void k_vmix_keep_scan(VMixKeep K, long long ntiles, long long n,
+                                                          const unsigned long long *guard, unsigned long long *skipped) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  if (guard && *guard == 0ull) {
+    if (tid == 0) { K.hdr[0] = 0u; K.hdr[1] = 0u; }
+    return;
+  }
+  constexpr int G = VMIX_SCAN_ROWS;
+  __shared__ unsigned wtot[G * 16];
+  unsigned carry = 0;                          // (the first wave's: kept elements of the batches before this one)
+  for (long long k0 = 0; k0 < ntiles; k0 += (long long)G * 1024) {
+    unsigned v[G], x[G];
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      const long long k = k0 + (long long)u * 1024 + tid;
+      v[u] = k < ntiles ? K.toff[k] : 0u;
+    }
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      x[u] = v[u];                             // inclusive scan inside the wave
+#pragma unroll
+      for (int o = 1; o < 64; o <<= 1) { const unsigned y = __shfl_up(x[u], o, 64); if (lane >= o) x[u] += y; }
+      if (lane == 63) wtot[u * 16 + wv] = x[u];
+    }
+    __syncthreads();
+    if (wv == 0) {                             // exclusive scan of the wave totals (row-major: element order), 64 at a time
+#pragma unroll
+      for (int b0 = 0; b0 < G * 16; b0 += 64) {
+        const unsigned t0 = wtot[b0 + lane];
+        unsigned s = t0;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const unsigned y = __shfl_up(s, o, 64); if (lane >= o) s += y; }
+        wtot[b0 + lane] = carry + s - t0;
+        carry += __shfl(s, 63, 64);
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      const long long k = k0 + (long long)u * 1024 + tid;
+      if (k < ntiles) K.toff[k] = x[u] - v[u] + wtot[u * 16 + wv];
+    }
+    __syncthreads();                           // (the next batch writes wtot again)
+  }
+  if (tid == 0) {
+    K.hdr[0] = carry;
+    K.hdr[1] = (carry + (unsigned)BLOCK - 1u) / (unsigned)BLOCK;
+    if (skipped && (unsigned long long)n > carry) atomicAdd(skipped, (unsigned long long)n - carry);
+    if (carry) atomicAdd(K.listed, (unsigned long long)carry);
+  }
+}
+__global__ __launch_bounds__(BLOCK) void k_vmix_keep_fill(VMixKeep K, const unsigned long long *guard) {
+  if (guard && *guard == 0ull) return;
+  constexpr int NW = BLOCK / 64;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const unsigned long long *m = K.mask + (size_t)blockIdx.x * (VMIX_TILE / 64);
+  unsigned run = K.toff[blockIdx.x], off[VMIX_TILE_ROUNDS];
+  unsigned long long keep[VMIX_TILE_ROUNDS];
+#pragma unroll
+  for (int g = 0; g < VMIX_TILE / 64; ++g) {   // element order: (round, wave, lane), as k_vmix_keep formed the ballots
+    const unsigned long long mg = m[g];
+    if ((g % NW) == wave) { off[g / NW] = run; keep[g / NW] = mg; }
+    run += (unsigned)__popcll(mg);
+  }
+  const unsigned long long below = (1ull << lane) - 1ull;
+  const unsigned first = (unsigned)blockIdx.x * (unsigned)VMIX_TILE;   // (odr_vmix: n < 2^32)
+#pragma unroll
+  for (int r = 0; r < VMIX_TILE_ROUNDS; ++r)
+    if ((keep[r] >> lane) & 1ull) K.list[off[r] + (unsigned)__popcll(keep[r] & below)] = first + (unsigned)(r * BLOCK + tid);
+}
+// dynamic LDS of a k_vmix_dense<NQ> workgroup: K column [4 NQ][BLOCK] and tables [4][4 NQ] (float64)
+__host__ __device__ constexpr size_t vmix_dense_lds_bytes(int nq) {
+  return sizeof(double) * ((size_t)(4 * nq) * BLOCK + 4 * (size_t)(4 * nq));
+}
+// Thread d of the first hdr[1] workgroups mixes element list[d].  The grid covers every element (the host does not know the
+// list's length); the workgroups that the list fills take their places from the XCD-contiguous order among THEMSELVES
+// (pid_wg_of(hdr[1])): with the grid's order the empty tail would fall on the last XCDs.
+template <int NQ, bool TL, class VM>
+__global__ __launch_bounds__(BLOCK, ODR_VMIX_WAVES) void k_vmix_dense(const DevWorld *__restrict__ W, PView p, VMixDesc D,
+                                                      const unsigned *__restrict__ list, const unsigned *__restrict__ hdr,
+                                                      double dt, double dt_mix_cfg, int mix_at_surface,
+                                                      int rng_mode, const double *__restrict__ huni,
+                                                      unsigned long long seed, unsigned long long step,
+                                                      int vadv, int sfl) {
+  static_assert(VM::STATIC, "the dense launch exists for the static configurations");
+  constexpr int NL = 4 * NQ;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x;
+  const DevSource &s = W->src[D.sid];
+  const int nzp = VM::nzp(D.nzp, NL);
+  double *Kp = (double *)smem;              // [NL][BLOCK]
+  double *gsh = Kp + (size_t)NL * BLOCK;    // [4][NL]
+  if (D.guard && *D.guard == 0ull) return;   // (wave-uniform, see k_vmix_col; the list then has length 0 as well)
+  const unsigned total = hdr[0], nbd = hdr[1];
+  if (blockIdx.x >= nbd) return;             // (workgroup-uniform)
+  const unsigned d = pid_wg_of(nbd) * BLOCK + (unsigned)tid;
+  const bool valid = d < total;
+  // the element's index is requested with the tables, its state behind it (threads past the end read the list's first entry)
+  const long long i = list[valid ? d : 0u];
+  if (tid < nzp) {
+    gsh[tid] = s.vg_a[tid]; gsh[NL + tid] = s.vg_b[tid]; gsh[2 * NL + tid] = s.vg_c[tid];
+    gsh[3 * NL + tid] = s.zmid[tid];     // level boundaries (entries >= nzp - 1 are not read)
+  }
+  long long i1 = i;   // (opaque: the addresses of the loads are not kept for the stores, which form theirs from i)
+  asm volatile("" : "+v"(i1));
+  const VMixState S = vmix_load_state(p, i1);
+  __syncthreads();
+  if (!valid) return;  // no barrier below: every thread touches only its own LDS column
+  VMixArgs A;
+  A.dt = dt; A.dt_mix_cfg = dt_mix_cfg; A.mix_at_surface = mix_at_surface; A.rng_mode = rng_mode; A.sfl = sfl; A.pad = 0;
+  A.huni = huni; A.seed = seed; A.step = step;
+  const bool escaped = vmix_col_particle<NQ, TL, VM>(s, p, D, A, vadv, i, Kp, gsh, tid, S);
+  if constexpr (VM::WINDOW) {
+    // the lanes a two-quad pass could not finish run the whole-column routine from scratch (see k_vmix_col)
+    const unsigned long long esc = __ballot(escaped);
+    if (esc != 0ull) {
+      if (escaped) {
+        long long i2 = i;
+        asm volatile("" : "+v"(i2));
+        const VMixState S2 = vmix_load_state(p, i2);
+        vmix_col_particle<NQ, TL, typename VM::Full>(s, p, D, A, vadv, i, Kp, gsh, tid, S2);
+        if (D.redone && (tid & 63) == __ffsll((long long)esc) - 1) atomicAdd(D.redone, (unsigned long long)__popcll(esc));
       }
     }
   }

@@ -5,6 +5,8 @@
 
 // (the 12-level launch keeps six workgroups per CU resident: its dynamic LDS, vmix_col_lds_bytes, within a sixth of 160 KB)
 static_assert(vmix_col_lds_bytes(3) <= 163840 / ODR_VMIX_WAVES, "k_vmix_col<3>: column, tables and offset list exceed a sixth of the LDS");
+static_assert(vmix_dense_lds_bytes(3) <= 163840 / ODR_VMIX_WAVES, "k_vmix_dense<3>: column and tables exceed a sixth of the LDS");
+static_assert(VMIX_TILE == 1024, "odr_particles_create sizes the keep ballots and tile counts for tiles of 1024 elements");
 
 // the K source and the call's settings are exactly the static mixing configuration VM (odr_kernels.hip.h VMixC3): every
 // run-time value equals its constant, the column has no padding level (nzp = 4 nq).  (ntimes as vmix_col_walk forms it)
@@ -121,6 +123,29 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
     D.skipped = p->vmix_redone + 1;
     D.noskip = getenv("ODR_NO_VMIX_SKIP") ? 1 : 0;
     if (!win) { g = dim3((unsigned)((p->n + VMIX_TILE - 1) / VMIX_TILE)); p->vmix_tiled++; }
+    // k_vmix_dense: a static configuration whose settings allow the skip compacts the whole launch, not each tile -- the three
+    // list kernels and the mixing launch back to back on the stream, the grid sized for every element (the list's length stays
+    // on the device).  ODR_NO_VMIX_DENSE=1 keeps the tiled launch (A/B runs and tests).  (The list holds 32-bit indices.)
+    const bool dense = spec && mix_at_surface == 0 && vadv != 1 && !D.noskip && !getenv("ODR_NO_VMIX_DENSE") &&
+                       p->n <= 0xffffffffLL;
+    VMixKeep K;
+    K.mask = p->vmix_mask; K.toff = p->vmix_toff; K.list = p->vmix_list;
+    K.hdr = (unsigned *)(p->vmix_redone + 3); K.listed = p->vmix_redone + 2;
+    if (dense) {
+      hipLaunchKernelGGL(k_vmix_keep, g, b, 0, c->stream, v, K, D.guard, dt, dt_mix);
+      hipLaunchKernelGGL(k_vmix_keep_scan, dim3(1), dim3(1024), 0, c->stream, K, (long long)g.x, (long long)p->n, D.guard, D.skipped);
+      hipLaunchKernelGGL(k_vmix_keep_fill, g, b, 0, c->stream, K, D.guard);
+      g = dim3(nblk(p->n));
+      p->vmix_dense++;
+    }
+#define VMIX_DENSE(NQ, VM)                                                                                        \
+  do {                                                                                                            \
+    const size_t l2 = vmix_dense_lds_bytes(NQ);                                                                   \
+    if (tl) hipLaunchKernelGGL((k_vmix_dense<NQ, true, VM>), g, b, l2, c->stream, c->dw, v, D, K.list, K.hdr, dt, dt_mix, \
+                               mix_at_surface, rng_mode, du, c->seed, st, vadv, c->seafloor);                     \
+    else hipLaunchKernelGGL((k_vmix_dense<NQ, false, VM>), g, b, l2, c->stream, c->dw, v, D, K.list, K.hdr, dt, dt_mix, \
+                            mix_at_surface, rng_mode, du, c->seed, st, vadv, c->seafloor);                        \
+  } while (0)
 #define VMIX_COL(NQ, VM)                                                                                          \
   do {                                                                                                            \
     const size_t l2 = vmix_col_lds_bytes(NQ);                                                                     \
@@ -136,6 +161,12 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
       else hipLaunchKernelGGL((k_vmix_win<false>), g, b, lw, c->stream, c->dw, v, D, dt, dt_mix, mix_at_surface, rng_mode, du,
                               c->seed, st, vadv, c->seafloor);
     }
+    else if (dense && specp && nq == 2) VMIX_DENSE(2, VMixC3);
+    else if (dense && specp && quadwin) VMIX_DENSE(3, VMixC3W);
+    else if (dense && specp) VMIX_DENSE(3, VMixC3);
+    else if (dense && nq == 2) VMIX_DENSE(2, VMixC3Rec);
+    else if (dense && quadwin) VMIX_DENSE(3, VMixC3RecW);
+    else if (dense) VMIX_DENSE(3, VMixC3Rec);
     else if (specp && nq == 2) VMIX_COL(2, VMixC3);
     else if (specp && quadwin) VMIX_COL(3, VMixC3W);
     else if (specp) VMIX_COL(3, VMixC3);
@@ -152,6 +183,7 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
     else if (nq <= 12) VMIX_COL(12, VMixRT);
     else VMIX_COL(16, VMixRT);
 #undef VMIX_COL
+#undef VMIX_DENSE
   } else if (oil) {
     if (nzp <= 16) hipLaunchKernelGGL((k_vmix<16, true>), g, b, lds, c->stream, c->dw, v, t, dt, dt_mix, mix_at_surface, rng_mode, du, c->seed, st, vadv, sfl_cut, c->oil);
     else if (nzp <= 32) hipLaunchKernelGGL((k_vmix<32, true>), g, b, lds, c->stream, c->dw, v, t, dt, dt_mix, mix_at_surface, rng_mode, du, c->seed, st, vadv, sfl_cut, c->oil);
@@ -182,6 +214,15 @@ int odr_particles_vmix_skip_stats(odr_ctx *c, odr_particles *p, uint64_t *out2) 
   D2H(&skipped, p->vmix_redone + 1, sizeof skipped);
   HIPCHK(hipStreamSynchronize(c->stream));
   out2[0] = p->vmix_tiled; out2[1] = skipped;
+  return 0;
+}
+
+int odr_particles_vmix_dense_stats(odr_ctx *c, odr_particles *p, uint64_t *out2) {
+  REQUIRE(c && p && out2, "NULL argument");
+  unsigned long long listed = 0;
+  D2H(&listed, p->vmix_redone + 2, sizeof listed);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  out2[0] = p->vmix_dense; out2[1] = listed;
   return 0;
 }
 

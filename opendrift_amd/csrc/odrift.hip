@@ -133,8 +133,13 @@ int odr_particles_create(odr_ctx *c, int64_t capacity, odr_particles **out) {
   HIPCHK(hipMalloc((void **)&p->bcount, sizeof(unsigned) * (size_t)(nblk(capacity) + 1)));
   HIPCHK(hipMalloc((void **)&p->wcount, sizeof(unsigned) * (size_t)(nblk(capacity) + 1) * (BLOCK / 64)));
   p->wcount_epoch = ~0ull;
-  HIPCHK(hipMalloc((void **)&p->vmix_redone, 2 * sizeof(unsigned long long)));
-  HIPCHK(hipMemset(p->vmix_redone, 0, 2 * sizeof(unsigned long long)));
+  HIPCHK(hipMalloc((void **)&p->vmix_redone, 4 * sizeof(unsigned long long)));
+  HIPCHK(hipMemset(p->vmix_redone, 0, 4 * sizeof(unsigned long long)));
+  // the dense mixing launch's list (VMixKeep): 16 ballots and one count per tile of 1024 elements, one index per element
+  const size_t vtiles = ((size_t)capacity + 1023) / 1024;
+  HIPCHK(hipMalloc((void **)&p->vmix_mask, sizeof(unsigned long long) * 16 * vtiles));
+  HIPCHK(hipMalloc((void **)&p->vmix_toff, sizeof(unsigned) * vtiles));
+  HIPCHK(hipMalloc((void **)&p->vmix_list, sizeof(unsigned) * (size_t)capacity));
   *out = p;
   return 0;
 }
@@ -155,6 +160,7 @@ int odr_particles_destroy(odr_ctx *c, odr_particles *p) {
   fr(p->bcount);
   fr(p->wcount);
   fr(p->vmix_redone);
+  fr(p->vmix_mask); fr(p->vmix_toff); fr(p->vmix_list);
   fr(p->scratch);
   fr(p->rank); fr(p->rank_words); fr(p->rank_before); fr(p->rank_bsum);
   fr(p->wg_tab); fr(p->wg_total); fr(p->wg_list); fr(p->z_keep);

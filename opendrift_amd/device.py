@@ -1454,6 +1454,14 @@ class Particles:
         check(self.lib.odr_particles_vmix_skip_stats(self.ctx.h, self.h, out))
         return dict(launches=int(out[0]), skipped=int(out[1]))
 
+    def vmix_dense_stats(self):
+        """The dense mixing launches (odr_particles_vmix_dense_stats: the compaction over the whole launch, static
+        configurations whose settings allow the skip) and the elements their lists held."""
+        import ctypes as C
+        out = (C.c_uint64 * 2)()
+        check(self.lib.odr_particles_vmix_dense_stats(self.ctx.h, self.h, out))
+        return dict(launches=int(out[0]), listed=int(out[1]))
+
     def reduce_global(self, combine, wind_drift_depth=0.1, relative_wind=False):
         """Sharded run: this set's raw reductions -> combine(raw16) over the ranks (counts summed, maxima maximised) ->
         installed for the movers that follow, until reduce_unpin()."""
