@@ -669,7 +669,10 @@ int odr_radio_resuspend(odr_ctx *ctx, odr_particles *p, odr_radio *radio, int sp
 /* number of active-set elements currently flagged with status_code (not yet removed by odr_compact) */
 int odr_particles_count_status(odr_ctx *ctx, odr_particles *p, int32_t status_code, int64_t *n);
 /* status_categories grow in the order in which reasons FIRST OCCUR (deactivate_elements, :1778-1781): a caller hands
- * out a provisional code for a reason not seen yet, counts it, and renumbers it once the category index is known */
+ * out a provisional code for a reason not seen yet, counts it, and renumbers it once the category index is known.
+ * Renumbering one reason into another leaves the active set alone; from_code or to_code 0 deactivates / re-activates
+ * elements (their `moving` flag is not touched) and counts as such: the cached reductions and the counts of
+ * odr_scan_status are void afterwards */
 int odr_particles_remap_status(odr_ctx *ctx, odr_particles *p, int32_t from_code, int32_t to_code);
 /* deactivate elements flagged by the host (deactivate_elements, :1774-1795) */
 int odr_deactivate(odr_ctx *ctx, odr_particles *p, const uint8_t *mask_host, int32_t status_code);
@@ -765,7 +768,12 @@ int odr_particles_vmix_skip_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out2
 int odr_particles_vmix_dense_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out2);
 /* counts and min/max used for the per-step log line and early-outs (:2212-2233):
  * out16 = {n_active, lon_min, lon_max, lat_min, lat_max, z_min, z_max, D_max, stokes_sum_max,
- *          wind_speed_max, wdf_surface_max, n_surface, hs_max, tp_max, 0, 0} */
+ *          wind_speed_max, wdf_surface_max, n_surface, hs_max, tp_max, rel_wind_speed_max, mld_max}
+ * over the elements with status 0 (deactivated, not yet compacted ones do not count); a maximum of nothing -- no such
+ * element, the variable not sampled, no element at the surface -- is -inf, a minimum +inf; NaN values are ignored.  The
+ * wind slots (9, 10, 11, 14) run over the elements with z >= -|wind_drift_depth|; relative_wind is 0 here, so slot 14
+ * equals slot 9.  Always a pass over the arrays (never the cache); like odr_reduce_local it releases installed values
+ * (odr_reduce_install), which it overwrites. */
 int odr_reduce_scalars(odr_ctx *ctx, odr_particles *p, double wind_drift_depth, double *out16);
 /* The global tests the movers open with -- no element at the surface, wind_drift_factor / (relative) wind speed / Stokes
  * drift / horizontal diffusivity identically zero (physics_methods.py:741-747,771-780,799-804, basemodel/__init__.py:1754)
@@ -783,6 +791,13 @@ int odr_ctx_set_step_reduce(odr_ctx *ctx, int on, double wind_drift_depth, int r
 int odr_reduce_local(odr_ctx *ctx, odr_particles *p, double wind_drift_depth, int relative_wind, double *out16);
 int odr_reduce_install(odr_ctx *ctx, odr_particles *p, const double *in16);
 int odr_reduce_unpin(odr_ctx *ctx);
+/* What the last mover on this context read: the 16 RAW slots as they stand on the device (nothing is reduced), and what
+ * the cache says about them -- *state bit 0: they describe `p` in its present state (a mover on `p` would reuse them),
+ * bit 1: the lon / lat / z extremes (slots 1..6) are filled (the movers' own pass leaves them at -inf), bit 2: formed by
+ * the launch of odr_env_coast_advect (odr_ctx_set_step_reduce): slots 7, 8, 10, 14 hold +1 / 0 / -inf for "some element
+ * > 0" / "none > 0, some == 0" / "neither", slot 11 the count, the others nothing; bit 3: installed (odr_reduce_install).
+ * For tests and diagnostics; waits for the stream. */
+int odr_reduce_cached(odr_ctx *ctx, odr_particles *p, double *out16, int32_t *state);
 
 /* Until the first update_positions of a run the reference's elements.lon / lat are float32 ARRAYS (elements/elements.py:71-88),
  * so modulate_longitude (readers/basereader/variables.py:259-280, called on the elements' longitudes :914) forms

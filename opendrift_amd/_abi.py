@@ -221,6 +221,7 @@ _SIGNATURES = {
     'odr_reduce_local': [_vp, _vp, C.c_double, C.c_int, _dp],
     'odr_reduce_install': [_vp, _vp, _dp],
     'odr_reduce_unpin': [_vp],
+    'odr_reduce_cached': [_vp, _vp, _dp, _ip],
     'odr_timer_begin': [_vp],
     'odr_timer_end': [_vp, _fp],
     'odr_sgrid_create': [_vp, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, C.c_double, _dp, _dp, C.c_int32, _P(_vp)],

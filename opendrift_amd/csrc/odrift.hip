@@ -1802,6 +1802,7 @@ int odr_ctx_set_step_reduce(odr_ctx *c, int on, double wind_drift_depth, int rel
 
 int odr_reduce_scalars(odr_ctx *c, odr_particles *p, double wdd, double *out16) {
   REQUIRE(out16, "out16 NULL");
+  c->red_pinned = 0;       // (the pass below overwrites an installed row: left pinned, the movers would take THIS set's values for the all-rank ones)
   c->red_owner = nullptr;  // lon/lat extremes change with every mover: always recomputed
   int rc = reduce(c, p, wdd, 0);
   if (rc) return rc;
@@ -1843,6 +1844,16 @@ int odr_reduce_install(odr_ctx *c, odr_particles *p, const double *in16) {
 int odr_reduce_unpin(odr_ctx *c) {
   c->red_pinned = 0;
   c->red_owner = nullptr;
+  return 0;
+}
+int odr_reduce_cached(odr_ctx *c, odr_particles *p, double *out16, int32_t *state) {
+  REQUIRE(p && out16 && state, "NULL argument");
+  double r[R_N];
+  D2H(r, c->red, sizeof r);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int k = 0; k < 16; ++k) out16[k] = k < R_N ? r[k] : 0;
+  const bool mine = c->red_owner == p && ((c->red_pinned != 0) || (!p->external && c->red_epoch == p->epoch));
+  *state = (mine ? 1 : 0) | (c->red_extents ? 2 : 0) | (c->red_partial ? 4 : 0) | (c->red_pinned ? 8 : 0);
   return 0;
 }
 
@@ -2135,6 +2146,9 @@ int odr_particles_count_status(odr_ctx *c, odr_particles *p, int32_t code, int64
 
 int odr_particles_remap_status(odr_ctx *c, odr_particles *p, int32_t from, int32_t to) {
   if (p->n == 0 || from == to) return 0;
+  // renumbering one deactivation reason into another leaves the active set alone (the scan of odr_scan_status and the cached
+  // reductions stay valid); to or from 0 it activates / deactivates elements like any other call that does
+  if (from == 0 || to == 0) { p->status_epoch++; p->epoch++; }
   hipLaunchKernelGGL(k_status_remap, dim3(nblk(p->n)), dim3(BLOCK), 0, c->stream, view(p), (int)from, (int)to);
   HIPCHK(hipGetLastError());
   return 0;

@@ -1485,7 +1485,8 @@ class Particles:
     @staticmethod
     def reduction_dict(raw):
         keys = ['n_active', 'lon_min', 'lon_max', 'lat_min', 'lat_max', 'z_min', 'z_max', 'D_max',
-                'stokes_sum_max', 'wind_speed_max', 'wdf_surface_max', 'n_surface', 'hs_max', 'tp_max']
+                'stokes_sum_max', 'wind_speed_max', 'wdf_surface_max', 'n_surface', 'hs_max', 'tp_max', 'rel_wind_speed_max',
+                'mld_max']
         d = dict(zip(keys, raw))
         for k in ('lon_min', 'lat_min', 'z_min'):
             d[k] = -d[k]
@@ -1494,11 +1495,20 @@ class Particles:
     def reduce_unpin(self):
         check(self.lib.odr_reduce_unpin(self.ctx.h))
 
+    def reduce_cached(self):
+        """(raw16, state) as they stand on the device -- what the last mover read; nothing is reduced (odr_reduce_cached).
+        state: dict(valid: a mover on this set would reuse them, extents: slots 1..6 are filled, partial: formed by the step
+        launch (signs, not maxima), pinned: installed by reduce_install)."""
+        raw, st = np.empty(16), C.c_int32()
+        check(self.lib.odr_reduce_cached(self.ctx.h, self.h, raw.ctypes.data_as(_dp), C.byref(st)))
+        return raw, dict(valid=bool(st.value & 1), extents=bool(st.value & 2), partial=bool(st.value & 4), pinned=bool(st.value & 8))
+
     def reduce_scalars(self, wind_drift_depth=0.1):
         out = np.empty(16)
         check(self.lib.odr_reduce_scalars(self.ctx.h, self.h, float(wind_drift_depth), out.ctypes.data_as(_dp)))
         keys = ['n_active', 'lon_min', 'lon_max', 'lat_min', 'lat_max', 'z_min', 'z_max', 'D_max',
-                'stokes_sum_max', 'wind_speed_max', 'wdf_surface_max', 'n_surface', 'hs_max', 'tp_max']
+                'stokes_sum_max', 'wind_speed_max', 'wdf_surface_max', 'n_surface', 'hs_max', 'tp_max', 'rel_wind_speed_max',
+                'mld_max']
         return dict(zip(keys, out))
 
 
