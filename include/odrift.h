@@ -766,6 +766,18 @@ int odr_particles_vmix_skip_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out2
  * out2 = {dense launches, elements they listed (read from the device: waits for the stream)}.
  * The environment variable ODR_NO_VMIX_DENSE=1 keeps the tiled launch. */
 int odr_particles_vmix_dense_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out2);
+/* Where the dense launches took their keep ballots from.  A static-layout step launch of odr_env_coast_advect that lifts to the
+ * sea floor with the depth in its group forms them as it goes; odr_vmix uses them when nothing that changes z, the depth, the
+ * ssh, the order or the count of the elements has run in between (odr_scan_status_begin / _end and odr_ctx_guard_next_vmix
+ * leave them valid), and makes its own pass over the three arrays (k_vmix_keep) otherwise.  A list that holds every element is
+ * not filled: the mixing launch takes the indices 0 .. n - 1 itself.
+ * out3 = {dense launches on the step launch's ballots, dense launches on k_vmix_keep's, lists of every element (read from the
+ * device: waits for the stream)}.
+ * Results and the counters of odr_particles_vmix_skip_stats / _dense_stats are the same on either producer's ballots (a skipped
+ * element that holds -0.0 included: the step launch marks its wave, and the list kernels store the +0.0 a mixing call that
+ * walks a sub-step hands back).
+ * The environment variable ODR_NO_STEP_KEEP=1 (read per odr_env_coast_advect call) leaves the ballots to k_vmix_keep. */
+int odr_particles_vmix_keep_stats(odr_ctx *ctx, odr_particles *p, uint64_t *out3);
 /* counts and min/max used for the per-step log line and early-outs (:2212-2233):
  * out16 = {n_active, lon_min, lon_max, lat_min, lat_max, z_min, z_max, D_max, stokes_sum_max,
  *          wind_speed_max, wdf_surface_max, n_surface, hs_max, tp_max, rel_wind_speed_max, mld_max}

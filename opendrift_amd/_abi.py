@@ -216,6 +216,7 @@ _SIGNATURES = {
     'odr_particles_vmix_window_stats': [_vp, _vp, _P(C.c_uint64)],
     'odr_particles_vmix_skip_stats': [_vp, _vp, _P(C.c_uint64)],
     'odr_particles_vmix_dense_stats': [_vp, _vp, _P(C.c_uint64)],
+    'odr_particles_vmix_keep_stats': [_vp, _vp, _P(C.c_uint64)],
     'odr_reduce_scalars': [_vp, _vp, C.c_double, _dp],
     'odr_ctx_set_step_reduce': [_vp, C.c_int, C.c_double, C.c_int],
     'odr_reduce_local': [_vp, _vp, C.c_double, C.c_int, _dp],

@@ -183,10 +183,18 @@ struct odr_particles {
   unsigned long long vmix_window[2];         // host: static 12-level launches of k_vmix_col that gathered two K quads per particle [0], the whole column [1]
   unsigned long long vmix_tiled;             // host: launches of k_vmix_col (every one compacts its tiles) and of k_vmix_dense
   unsigned long long vmix_dense;             // host: dense mixing launches (k_vmix_dense behind the three list kernels); each counts in vmix_tiled too
+  unsigned long long vmix_keep_src[2];       // host: dense mixing launches whose keep ballots the step launch had left [0], k_vmix_keep formed [1]
   unsigned long long *vmix_redone;           // device: [0] elements the two-quad launches redid on the whole column, [1] elements the mixing launches skipped at the surface,
-                                             // [2] elements the dense launches listed, [3] two words: length of the last list, workgroups it fills (VMixKeep::hdr)
-  unsigned long long *vmix_mask;             // device, by capacity: the dense launch's keep ballots, tile counts / offsets and list (VMixKeep)
+                                             // [2] elements the dense launches listed, [3], [4] three words: length of the last list, workgroups it fills, list of
+                                             // every element (VMixKeep::hdr), [5] lists of every element (VMixKeep::idents)
+  unsigned long long *vmix_mask;             // device, by capacity: the dense launch's keep ballots, wave counts, tile offsets and list (VMixKeep)
+  unsigned char *vmix_wcnt;
   unsigned *vmix_toff, *vmix_list;
+  // the keep ballots and wave counts a static-layout step launch left in vmix_mask / vmix_wcnt (StepDesc.keep): valid for the
+  // dense mixing launch while keep_epoch == epoch and keep_n == n -- every call that changes z, the depth, the ssh or the
+  // element set bumps epoch; a re-sort, which does not, voids keep_epoch itself
+  unsigned long long keep_epoch;
+  long long keep_n;
   double *z_keep;       // odr_particles_truncate_z: the elements' own z while the sampling calls see the clipped one
   long long z_keep_n;
   bool z_truncated;

@@ -1078,6 +1078,13 @@ struct StepDesc {
   // *sflags.  k_cmp_total folds the wave counts; the pass over the status array (k_cmp_count, 32 us at 10 M elements) is not made.
   unsigned *wcount;                 // nullptr: not asked for
   unsigned long long *sflags;
+  // The keep ballots of the dense mixing launch that follows (VMixKeep, k_vmix_keep) formed by this launch, which holds z, the
+  // depth and the ssh of every element in registers at its sea-floor clause: keep[i / 64] = the wave's ballot of "the mixing
+  // launch can change this element", keepc[i / 64] = its popcount, and bit 7: some element it leaves out holds -0.0.  Static 3-D
+  // layouts only (the other instantiations carry no code for it).  The words from the launch's last wave to the end of its last tile of VMIX_TILE elements are NOT written:
+  // k_vmix_keep_scan and k_vmix_keep_fill bound their reads by n.
+  unsigned long long *keep;         // nullptr: not asked for
+  unsigned char *keepc;
 };
 
 // (The LDS field tile is a kernel of its own since round 4: k_step_tile, odr_tile.hip.h.)
@@ -1222,6 +1229,22 @@ __global__ __launch_bounds__(BLOCK, ODR_STEP_PARKS(SCHEME, PROJ) ? ODR_PARK_WAVE
         floorz = -__fadd_rn(dep, S.ssh_slot >= 0 ? pick_slot(out, S.ssh_slot) : ssh0);
       }
       if (zz < (double)floorz) { zz = (double)floorz; p.z[i] = zz; }
+      if constexpr (LY::STATIC && IS3D) {
+        // k_vmix_keep's predicate on the z this launch leaves (floorz has the bits of its Zmin): the mixing launch cannot change an
+        // element at the surface whose floor is not above it.  Every lane with an element is active here (the clauses above have
+        // closed), the lanes past the end vote 0; lane 0 holds the wave's first element.  A skipped element that holds -0.0 comes
+        // out of a mixing call that walks a sub-step as +0.0; whether the call that follows walks one is not known here, so z
+        // stays and bit 7 of the wave's count says that the wave has such an element (k_vmix_keep_fill stores the +0.0).  The
+        // words are stored at once: no register carries anything of them through the stages below.
+        if (S.keep) {
+          const bool at_top = zz == 0 && !(floorz > 0.f);
+          const unsigned long long kb = __ballot(!at_top), nz = __ballot(at_top && __double_as_longlong(zz) != 0ll);
+          if ((threadIdx.x & 63) == 0) {
+            S.keep[i >> 6] = kb;
+            S.keepc[i >> 6] = (unsigned char)((unsigned)__popcll(kb) | (nz ? 128u : 0u));
+          }
+        }
+      }
     }
     if (S.age_dt != 0.0f) {  // k_age
       const float a = __fadd_rn(age0, S.age_dt);
@@ -2212,25 +2235,31 @@ __global__ __launch_bounds__(BLOCK, ODR_VMIX_WAVES) void k_vmix_col(const DevWor
 }
 
 // ---- The dense mixing launch: the same skip (see k_vmix_col) with the compaction over the WHOLE launch instead of per tile.
-// Three small kernels in front of the mixing launch build one stable list of the elements to mix -- k_vmix_keep: the predicate,
-// a 64-bit keep ballot per 64 consecutive elements and a count per tile of VMIX_TILE; k_vmix_keep_scan: the exclusive prefix
-// over the tile counts, the total and the workgroups it fills; k_vmix_keep_fill: the kept indices, ascending (neighbours in
-// memory stay neighbours in a wave) -- and k_vmix_dense runs the one-element-per-thread routine over list[0 .. total): no
-// loop over passes, no offset list in LDS, no workgroup that waits for its slowest pass.  The host sizes the mixing launch for
-// every element without reading the total back; the workgroups past the list return at once.  No workgroup of any of these
-// kernels waits for another one.  Static configurations only (odr_vmix); everything else keeps k_vmix_col.
+// One stable list of the elements to mix is built in front of the mixing launch -- the predicate, as a 64-bit keep ballot and
+// its popcount (one byte) per 64 consecutive elements: by the step launch that ran right before (StepDesc.keep, static 3-D
+// layouts) or, when nothing valid is left of that, by k_vmix_keep; k_vmix_keep_scan: the kept elements per tile of VMIX_TILE
+// from the 16 bytes of the tile, their exclusive prefix, the total and the workgroups it fills; k_vmix_keep_fill: the kept
+// indices, ascending (neighbours in memory stay neighbours in a wave) -- and k_vmix_dense runs the one-element-per-thread
+// routine over list[0 .. total): no loop over passes, no offset list in LDS, no workgroup that waits for its slowest pass.
+// When every element is kept the scan says so (hdr[2]): the fill returns at once and thread d mixes element d.  The host sizes
+// the mixing launch for every element without reading the total back; the workgroups past the list return at once.  No
+// workgroup of any of these kernels waits for another one.  Static configurations only (odr_vmix); everything else keeps
+// k_vmix_col.
+// The step launch writes the words of its own waves only: the scan and the fill take the words of waves past the last element
+// (from (n + 63) / 64 to the end of the last tile) as 0 whoever produced them.
 struct VMixKeep {
   unsigned long long *mask;    // [16 per tile] keep ballot of elements 64 g .. 64 g + 63 (bits past the end: 0)
-  unsigned *toff;              // [tiles] k_vmix_keep: kept elements of the tile; after k_vmix_keep_scan: kept elements before it
+  unsigned char *wcnt;         // [16 per tile] popcount of mask[g]; bit 7 (the step launch's words only): an element that mask[g] leaves out holds -0.0
+  unsigned *toff;              // [tiles] after k_vmix_keep_scan: kept elements before the tile
   unsigned *list;              // [capacity] indices of the elements to mix, ascending
-  unsigned *hdr;               // [0] length of the list, [1] workgroups of BLOCK that it fills
+  unsigned *hdr;               // [0] length of the list, [1] workgroups of BLOCK that it fills, [2] 1: the list is 0 .. n - 1 and was not filled
   unsigned long long *listed;  // running sum of the list lengths (odr_particles_vmix_dense_stats)
+  unsigned long long *idents;  // lists that held every element (odr_particles_vmix_keep_stats)
 };
 __global__ __launch_bounds__(BLOCK) void k_vmix_keep(PView p, VMixKeep K, const unsigned long long *guard, double dt,
                                                       double dt_mix_cfg) {
   if (guard && *guard == 0ull) return;   // (a guarded launch that may not run changes nothing: see k_vmix_col)
   constexpr int NW = BLOCK / 64;
-  __shared__ unsigned cnt[NW];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long long base = (long long)blockIdx.x * VMIX_TILE;
   double z[VMIX_TILE_ROUNDS];
@@ -2243,7 +2272,6 @@ __global__ __launch_bounds__(BLOCK) void k_vmix_keep(PView p, VMixKeep K, const 
   // a walk of no sub-step hands z back as it came: only then a -0.0 stays (sub-step count as vmix_col_walk forms it)
   const double sgn = dt > 0 ? 1.0 : (dt < 0 ? -1.0 : 0.0);
   const bool walks = abs((int)(dt / (dt_mix_cfg * sgn))) > 0;
-  unsigned mine = 0;
 #pragma unroll
   for (int r = 0; r < VMIX_TILE_ROUNDS; ++r) {
     const long long e = base + r * BLOCK + tid;
@@ -2252,46 +2280,65 @@ __global__ __launch_bounds__(BLOCK) void k_vmix_keep(PView p, VMixKeep K, const 
     // the mixing launch would store z = +0.0 for it: all there is to do when -0.0 came in
     if (skip && walks && __double_as_longlong(z[r]) != 0ll) p.z[e] = 0.0;
     const unsigned long long keep = __ballot(e < p.n && !skip);
-    if (lane == 0) K.mask[(size_t)blockIdx.x * (VMIX_TILE / 64) + r * NW + wave] = keep;
-    mine += (unsigned)__popcll(keep);
-  }
-  if (lane == 0) cnt[wave] = mine;
-  __syncthreads();
-  if (tid == 0) {
-    unsigned t = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) t += cnt[w];
-    K.toff[blockIdx.x] = t;
+    if (lane == 0) {
+      const size_t g = (size_t)blockIdx.x * (VMIX_TILE / 64) + r * NW + wave;
+      K.mask[g] = keep; K.wcnt[g] = (unsigned char)__popcll(keep);
+    }
   }
 }
-// Exclusive prefix over the tile counts by ONE workgroup, VMIX_SCAN_ROWS rows of 1024 counts at a time (k_cmp_scan's scheme:
-// thread t owns counts t, t + 1024, ... of the batch, all of its loads in flight together; every row is scanned wave by wave
-// with shuffles, the wave totals by the first wave, which carries the running total from batch to batch).  Writes the list's
-// length and the workgroups it fills, and adds n - length to `skipped` and the length to K.listed.  A guarded launch that may
-// not run leaves a list of length 0 and the counters alone.
+// Kept elements per tile and their exclusive prefix by ONE workgroup, VMIX_SCAN_ROWS rows of 1024 tiles at a time (k_cmp_scan's
+// scheme: thread t owns tiles t, t + 1024, ... of the batch -- the 16 wave counts of a tile are one 16-byte load --, all of its
+// loads in flight together; every row is scanned wave by wave with shuffles, the wave totals by the first wave, which carries
+// the running total from batch to batch).  Writes the list's length, the workgroups it fills and whether it holds every element,
+// and adds n - length to `skipped` and the length to K.listed.  A guarded launch that may not run leaves a list of length 0 and
+// the counters alone.
 constexpr int VMIX_SCAN_ROWS = 16;   // x 1024 tiles x 1024 elements = 16.8 M elements per batch
+__device__ __forceinline__ unsigned vmix_tile_count(uint4 q) {   // sum of the 16 wave counts (bit 7 is not part of them: VMixKeep::wcnt)
+  const unsigned m = 0x7f7f7f7fu;
+  return __builtin_amdgcn_sad_u8(q.x & m, 0u, __builtin_amdgcn_sad_u8(q.y & m, 0u, __builtin_amdgcn_sad_u8(q.z & m, 0u,
+         __builtin_amdgcn_sad_u8(q.w & m, 0u, 0u))));
+}
 __global__ __launch_bounds__(1024) void k_vmix_keep_scan(VMixKeep K, long long ntiles, long long n,
                                                           const unsigned long long *guard, unsigned long long *skipped) {
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   if (guard && *guard == 0ull) {
-    if (tid == 0) { K.hdr[0] = 0u; K.hdr[1] = 0u; }
+    if (tid == 0) { K.hdr[0] = 0u; K.hdr[1] = 0u; K.hdr[2] = 0u; }
     return;
   }
   constexpr int G = VMIX_SCAN_ROWS;
   __shared__ unsigned wtot[G * 16];
+  // waves of the last tile that hold an element: nobody wrote the counts past them
+  const int last_waves = (int)(((n + 63) >> 6) - (ntiles - 1) * (VMIX_TILE / 64));
   unsigned carry = 0;                          // (the first wave's: kept elements of the batches before this one)
   for (long long k0 = 0; k0 < ntiles; k0 += (long long)G * 1024) {
     unsigned v[G], x[G];
+    uint4 q[G];
 #pragma unroll
     for (int u = 0; u < G; ++u) {
       const long long k = k0 + (long long)u * 1024 + tid;
-      v[u] = k < ntiles ? K.toff[k] : 0u;
+      q[u] = k < ntiles ? ((const uint4 *)K.wcnt)[k] : make_uint4(0u, 0u, 0u, 0u);
     }
 #pragma unroll
     for (int u = 0; u < G; ++u) {
-      x[u] = v[u];                             // inclusive scan inside the wave
+      const long long k = k0 + (long long)u * 1024 + tid;
+      if (k == ntiles - 1 && last_waves < VMIX_TILE / 64) {   // (one thread of the launch)
+        unsigned w[4] = {q[u].x, q[u].y, q[u].z, q[u].w};
 #pragma unroll
-      for (int o = 1; o < 64; o <<= 1) { const unsigned y = __shfl_up(x[u], o, 64); if (lane >= o) x[u] += y; }
+        for (int j = 0; j < 4; ++j) {
+          const int m = last_waves - 4 * j;                   // bytes of w[j] that count
+          w[j] = m >= 4 ? w[j] : (m <= 0 ? 0u : (w[j] & ((1u << (8 * m)) - 1u)));
+        }
+        q[u] = make_uint4(w[0], w[1], w[2], w[3]);
+      }
+      v[u] = vmix_tile_count(q[u]);
+    }
+#pragma unroll
+    for (int u = 0; u < G; ++u) {
+      x[u] = v[u];                             // inclusive scan inside the wave (rows past the last tile: nothing to add up)
+      if (k0 + (long long)u * 1024 < ntiles) {
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const unsigned y = __shfl_up(x[u], o, 64); if (lane >= o) x[u] += y; }
+      }
       if (lane == 63) wtot[u * 16 + wv] = x[u];
     }
     __syncthreads();
@@ -2315,37 +2362,61 @@ __global__ __launch_bounds__(1024) void k_vmix_keep_scan(VMixKeep K, long long n
     __syncthreads();                           // (the next batch writes wtot again)
   }
   if (tid == 0) {
+    const bool ident = (unsigned long long)n == carry;
     K.hdr[0] = carry;
     K.hdr[1] = (carry + (unsigned)BLOCK - 1u) / (unsigned)BLOCK;
+    K.hdr[2] = ident ? 1u : 0u;
     if (skipped && (unsigned long long)n > carry) atomicAdd(skipped, (unsigned long long)n - carry);
     if (carry) atomicAdd(K.listed, (unsigned long long)carry);
+    if (ident) atomicAdd(K.idents, 1ull);
   }
 }
-__global__ __launch_bounds__(BLOCK) void k_vmix_keep_fill(VMixKeep K, const unsigned long long *guard) {
+// (z, walks: a mixing call that walks a sub-step hands a skipped -0.0 back as +0.0.  k_vmix_keep stores that itself; the step
+// launch cannot know `walks` and marks the waves that hold such an element, whose tiles store it here -- rare)
+__global__ __launch_bounds__(BLOCK) void k_vmix_keep_fill(VMixKeep K, const unsigned long long *guard, long long n, double *z,
+                                                           int walks) {
   if (guard && *guard == 0ull) return;
   constexpr int NW = BLOCK / 64;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned long long *m = K.mask + (size_t)blockIdx.x * (VMIX_TILE / 64);
+  // (everything the workgroup reads is requested before the first test of it: one round trip, as before there was a flag)
+  const unsigned every = K.hdr[2];
   unsigned run = K.toff[blockIdx.x], off[VMIX_TILE_ROUNDS];
+  const uint4 cw = ((const uint4 *)K.wcnt)[blockIdx.x];   // (counts of waves past the end are anything: the loop at the end tests e < n)
+  unsigned long long mg[VMIX_TILE / 64];
+#pragma unroll
+  for (int g = 0; g < VMIX_TILE / 64; ++g) mg[g] = m[g];
+  // (an empty statement that reads them: left alone the compiler sinks each load behind the test that first needs it -- the flag,
+  // the two halves of the ballots, the counts: four scalar round trips one after the other, 17 us for this kernel instead of 13)
+  asm volatile("" ::"s"(every), "s"(run), "s"(cw.x), "s"(mg[0]), "s"(mg[VMIX_TILE / 64 - 1]), "s"(walks));
+  if (every) return;      // every element is kept: k_vmix_dense takes the index itself
+  const int left = (int)(((n + 63) >> 6) - (long long)blockIdx.x * (VMIX_TILE / 64));   // ballots of the tile that hold an element
   unsigned long long keep[VMIX_TILE_ROUNDS];
 #pragma unroll
-  for (int g = 0; g < VMIX_TILE / 64; ++g) {   // element order: (round, wave, lane), as k_vmix_keep formed the ballots
-    const unsigned long long mg = m[g];
-    if ((g % NW) == wave) { off[g / NW] = run; keep[g / NW] = mg; }
-    run += (unsigned)__popcll(mg);
+  for (int g = 0; g < VMIX_TILE / 64; ++g) {   // element order: (round, wave, lane), as the ballots were formed
+    if (g >= left) mg[g] = 0ull;
+    if ((g % NW) == wave) { off[g / NW] = run; keep[g / NW] = mg[g]; }
+    run += (unsigned)__popcll(mg[g]);
   }
   const unsigned long long below = (1ull << lane) - 1ull;
   const unsigned first = (unsigned)blockIdx.x * (unsigned)VMIX_TILE;   // (odr_vmix: n < 2^32)
 #pragma unroll
   for (int r = 0; r < VMIX_TILE_ROUNDS; ++r)
     if ((keep[r] >> lane) & 1ull) K.list[off[r] + (unsigned)__popcll(keep[r] & below)] = first + (unsigned)(r * BLOCK + tid);
+  if (walks && ((cw.x | cw.y | cw.z | cw.w) & 0x80808080u)) {
+#pragma unroll
+    for (int r = 0; r < VMIX_TILE_ROUNDS; ++r) {
+      const long long e = (long long)first + r * BLOCK + tid;
+      if (e < n && !((keep[r] >> lane) & 1ull) && __double_as_longlong(z[e]) != 0ll) z[e] = 0.0;   // left out: z is +0.0 or -0.0
+    }
+  }
 }
 // dynamic LDS of a k_vmix_dense<NQ> workgroup: K column [4 NQ][BLOCK] and tables [4][4 NQ] (float64)
 __host__ __device__ constexpr size_t vmix_dense_lds_bytes(int nq) {
   return sizeof(double) * ((size_t)(4 * nq) * BLOCK + 4 * (size_t)(4 * nq));
 }
-// Thread d of the first hdr[1] workgroups mixes element list[d].  The grid covers every element (the host does not know the
+// Thread d of the first hdr[1] workgroups mixes element list[d] (hdr[2] set: element d).  The grid covers every element (the host does not know the
 // list's length); the workgroups that the list fills take their places from the XCD-contiguous order among THEMSELVES
 // (pid_wg_of(hdr[1])): with the grid's order the empty tail would fall on the last XCDs.
 template <int NQ, bool TL, class VM>
@@ -2369,7 +2440,8 @@ __global__ __launch_bounds__(BLOCK, ODR_VMIX_WAVES) void k_vmix_dense(const DevW
   const unsigned d = pid_wg_of(nbd) * BLOCK + (unsigned)tid;
   const bool valid = d < total;
   // the element's index is requested with the tables, its state behind it (threads past the end read the list's first entry)
-  const long long i = list[valid ? d : 0u];
+  const unsigned dv = valid ? d : 0u;
+  const long long i = hdr[2] ? dv : list[dv];   // (wave-uniform choice: a list of every element is not filled)
   if (tid < nzp) {
     gsh[tid] = s.vg_a[tid]; gsh[NL + tid] = s.vg_b[tid]; gsh[2 * NL + tid] = s.vg_c[tid];
     gsh[3 * NL + tid] = s.zmid[tid];     // level boundaries (entries >= nzp - 1 are not read)

@@ -48,6 +48,9 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
   c->oil_owner = nullptr;
   c->vmix_levels = 0;
   c->guarded_vmix = nullptr;
+  // the keep ballots of the step launch that ran last (StepDesc.keep) describe the arrays as they are now: nothing that changes
+  // z, the depth, the ssh or the element set has run since.  (Read before this call's own bump, which voids them: it changes z.)
+  const bool step_keep = !p->external && p->keep_epoch == p->epoch && p->keep_n == p->n;
   p->status_epoch++;
   p->epoch++;  // invalidates the cached reductions (reduce())
   REQUIRE(dt_mix > 0 && dt != 0, "bad time steps");
@@ -129,12 +132,16 @@ int odr_vmix(odr_ctx *c, odr_particles *p, double t, double dt, double dt_mix, i
     const bool dense = spec && mix_at_surface == 0 && vadv != 1 && !D.noskip && !getenv("ODR_NO_VMIX_DENSE") &&
                        p->n <= 0xffffffffLL;
     VMixKeep K;
-    K.mask = p->vmix_mask; K.toff = p->vmix_toff; K.list = p->vmix_list;
-    K.hdr = (unsigned *)(p->vmix_redone + 3); K.listed = p->vmix_redone + 2;
+    K.mask = p->vmix_mask; K.wcnt = p->vmix_wcnt; K.toff = p->vmix_toff; K.list = p->vmix_list;
+    K.hdr = (unsigned *)(p->vmix_redone + 3); K.listed = p->vmix_redone + 2; K.idents = p->vmix_redone + 5;
     if (dense) {
-      hipLaunchKernelGGL(k_vmix_keep, g, b, 0, c->stream, v, K, D.guard, dt, dt_mix);
+      // the ballots and wave counts: the step launch's when they are still valid, k_vmix_keep's pass over z, depth and ssh otherwise
+      if (!step_keep) hipLaunchKernelGGL(k_vmix_keep, g, b, 0, c->stream, v, K, D.guard, dt, dt_mix);
+      p->vmix_keep_src[step_keep ? 0 : 1]++;
       hipLaunchKernelGGL(k_vmix_keep_scan, dim3(1), dim3(1024), 0, c->stream, K, (long long)g.x, (long long)p->n, D.guard, D.skipped);
-      hipLaunchKernelGGL(k_vmix_keep_fill, g, b, 0, c->stream, K, D.guard);
+      const double sg = dt > 0 ? 1.0 : (dt < 0 ? -1.0 : 0.0);
+      const int walks = abs((int)(dt / (dt_mix * sg))) > 0 ? 1 : 0;   // (as k_vmix_keep and vmix_col_walk form it)
+      hipLaunchKernelGGL(k_vmix_keep_fill, g, b, 0, c->stream, K, D.guard, (long long)p->n, v.z, walks);
       g = dim3(nblk(p->n));
       p->vmix_dense++;
     }
@@ -223,6 +230,15 @@ int odr_particles_vmix_dense_stats(odr_ctx *c, odr_particles *p, uint64_t *out2)
   D2H(&listed, p->vmix_redone + 2, sizeof listed);
   HIPCHK(hipStreamSynchronize(c->stream));
   out2[0] = p->vmix_dense; out2[1] = listed;
+  return 0;
+}
+
+int odr_particles_vmix_keep_stats(odr_ctx *c, odr_particles *p, uint64_t *out3) {
+  REQUIRE(c && p && out3, "NULL argument");
+  unsigned long long idents = 0;
+  D2H(&idents, p->vmix_redone + 5, sizeof idents);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  out3[0] = p->vmix_keep_src[0]; out3[1] = p->vmix_keep_src[1]; out3[2] = idents;
   return 0;
 }
 

@@ -246,6 +246,12 @@ int odr_env_coast_advect(odr_ctx *c, odr_particles *p, int nvars, const int32_t 
     }
   }
   if (count_in_launch) { S.wcount = p->wcount; S.sflags = c->counter + 2; }   // (k_step_grid only: the tile path left above)
+  // the keep ballots of the dense mixing launch formed by this launch (StepDesc.keep): the static 3-D layouts lift to the sea floor
+  // with the depth of the group in registers; launch_step_grid drops the request for every other instantiation and records
+  // keep_epoch / keep_n behind a launch that honours it.  ODR_NO_STEP_KEEP=1: k_vmix_keep forms them (A/B runs and tests).
+  if (S.seafloor && depth_slot >= 0 && p->vmix_mask && p->vmix_wcnt && !p->external && !getenv("ODR_NO_STEP_KEEP")) {
+    S.keep = p->vmix_mask; S.keepc = p->vmix_wcnt;
+  }
   if (N.on && (scheme > 0 || main_noise)) {
     if (scheme > 0 && N.rng_mode == ODR_RNG_HOST && !N.stage) return fail(ODR_ERR_INVALID, "no host draws for the Runge-Kutta stage calls");
     if (N.sm == ODR_STAGE_FAST && scheme > 0) odr_i_step_fast_noise(c, p, G, S, scheme, t, dt, factor, N);

@@ -104,6 +104,7 @@ static void launch_step_grid(odr_ctx *c, odr_particles *p, const EnvGroupDesc &G
         hipLaunchKernelGGL((k_step_grid<SCHEME, PROJ_LATLONG, true, NOISE, SM, LayoutC3>), g, b, 0, c->stream, c->dw, v, G, S,
                            dt, f, th, tf, c->counter, N);
         p->step_launches[1]++;
+        if (S.keep) { p->keep_epoch = p->epoch; p->keep_n = p->n; }   // (StepDesc.keep: as wcount_epoch / wcount_n)
         return;
       }
       if (layout_matches_onlevel(s, G, S, t, dt, th)) {
@@ -111,10 +112,12 @@ static void launch_step_grid(odr_ctx *c, odr_particles *p, const EnvGroupDesc &G
                            dt, f, th, tf, c->counter, N);
         p->step_launches[0]++;   // (counted with the run-time layout: odr_particles_step_layout_stats)
         p->step_launches[2]++;
+        if (S.keep) { p->keep_epoch = p->epoch; p->keep_n = p->n; }
         return;
       }
     }
   }
+  S.keep = nullptr; S.keepc = nullptr;   // (the static layouts only)
   p->step_launches[0]++;
 #define ODR_LAUNCH(PROJ, D3) hipLaunchKernelGGL((k_step_grid<SCHEME, PROJ, D3, NOISE, SM>), g, b, 0, c->stream, c->dw, v, G, S, dt, f, th, tf, c->counter, N)
   switch (odr_proj_template(s.proj)) {

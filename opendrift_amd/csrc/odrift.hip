@@ -133,11 +133,13 @@ int odr_particles_create(odr_ctx *c, int64_t capacity, odr_particles **out) {
   HIPCHK(hipMalloc((void **)&p->bcount, sizeof(unsigned) * (size_t)(nblk(capacity) + 1)));
   HIPCHK(hipMalloc((void **)&p->wcount, sizeof(unsigned) * (size_t)(nblk(capacity) + 1) * (BLOCK / 64)));
   p->wcount_epoch = ~0ull;
-  HIPCHK(hipMalloc((void **)&p->vmix_redone, 4 * sizeof(unsigned long long)));
-  HIPCHK(hipMemset(p->vmix_redone, 0, 4 * sizeof(unsigned long long)));
-  // the dense mixing launch's list (VMixKeep): 16 ballots and one count per tile of 1024 elements, one index per element
+  HIPCHK(hipMalloc((void **)&p->vmix_redone, 6 * sizeof(unsigned long long)));
+  HIPCHK(hipMemset(p->vmix_redone, 0, 6 * sizeof(unsigned long long)));
+  p->keep_epoch = ~0ull;
+  // the dense mixing launch's list (VMixKeep): 16 ballots, 16 wave counts and one offset per tile of 1024 elements, one index per element
   const size_t vtiles = ((size_t)capacity + 1023) / 1024;
   HIPCHK(hipMalloc((void **)&p->vmix_mask, sizeof(unsigned long long) * 16 * vtiles));
+  HIPCHK(hipMalloc((void **)&p->vmix_wcnt, 16 * vtiles));
   HIPCHK(hipMalloc((void **)&p->vmix_toff, sizeof(unsigned) * vtiles));
   HIPCHK(hipMalloc((void **)&p->vmix_list, sizeof(unsigned) * (size_t)capacity));
   *out = p;
@@ -160,7 +162,7 @@ int odr_particles_destroy(odr_ctx *c, odr_particles *p) {
   fr(p->bcount);
   fr(p->wcount);
   fr(p->vmix_redone);
-  fr(p->vmix_mask); fr(p->vmix_toff); fr(p->vmix_list);
+  fr(p->vmix_mask); fr(p->vmix_wcnt); fr(p->vmix_toff); fr(p->vmix_list);
   fr(p->scratch);
   fr(p->rank); fr(p->rank_words); fr(p->rank_before); fr(p->rank_bsum);
   fr(p->wg_tab); fr(p->wg_total); fr(p->wg_list); fr(p->z_keep);
@@ -2443,6 +2445,7 @@ int odr_sort_particles_ex(odr_ctx *c, odr_particles *p, int32_t sid, int keep_en
     else if (!(p->env_cok[v] && p->env_cn[v] >= p->n)) p->env_cok[v] = false;   // not carried: only a constant survives
   }
   p->status_epoch++;
+  p->keep_epoch = ~0ull;   // (the order changed; epoch is left alone: the cached reductions do not depend on the order)
   return 0;
 }
 

@@ -1462,6 +1462,14 @@ class Particles:
         check(self.lib.odr_particles_vmix_dense_stats(self.ctx.h, self.h, out))
         return dict(launches=int(out[0]), listed=int(out[1]))
 
+    def vmix_keep_stats(self):
+        """Where the dense mixing launches took their keep ballots from (odr_particles_vmix_keep_stats): the step launch that
+        ran right before, or k_vmix_keep's own pass; and the lists that held every element (not filled)."""
+        import ctypes as C
+        out = (C.c_uint64 * 3)()
+        check(self.lib.odr_particles_vmix_keep_stats(self.ctx.h, self.h, out))
+        return dict(from_step=int(out[0]), from_keep=int(out[1]), identity=int(out[2]))
+
     def reduce_global(self, combine, wind_drift_depth=0.1, relative_wind=False):
         """Sharded run: this set's raw reductions -> combine(raw16) over the ranks (counts summed, maxima maximised) ->
         installed for the movers that follow, until reduce_unpin()."""

@@ -37,7 +37,8 @@ def main():
     print('%-12s %8s %12s %12s   (us; last = the last %d dispatches of the group)' % ('group', 'calls', 'avg_all', 'avg_last', a.last))
     for g, _ in GROUPS:
         d = sorted(found[g])
-        if not d:
+        if not d:     # (k_vmix_keep: absent where the step launch left the keep ballots)
+            print('%-12s %8d %12s %12s' % (g, 0, '-', '-'))
             continue
         last = d[-a.last:]
         print('%-12s %8d %12.1f %12.1f' % (g, len(d), sum(x[1] for x in d) / len(d), sum(x[1] for x in last) / len(last)))
