@@ -666,6 +666,58 @@ int odr_radio_terminal_velocity(odr_ctx *ctx, odr_particles *p, int diameter_slo
  * as there.  ODR_ERR_STATE when the current or the depth have not been sampled or a slot has not been set. */
 int odr_radio_resuspend(odr_ctx *ctx, odr_particles *p, odr_radio *radio, int specie_slot, int diameter_slot, int rng_mode,
                         const double *diameter_noise, const double *depth_noise, uint64_t step);
+/* OpenOil's NOAA oil weathering (models/openoil/openoil.py:717-920, noaa_oil_weathering.py, csrc/odr_weather.hip.h) from an oil given as
+ * a TABLE of pseudo-components.  The state lives in a side table the particle set owns, one record and one row of mass_components
+ * per element, indexed by element ID like the reference's noaa_mass_balance (:682-693): compaction, the re-sort and the property
+ * slots do not touch it.  The record is float64 like the reference's arrays at that point of the step. */
+enum { ODR_OIL_MAXCOMP = 32 };
+enum { ODR_WEATHER_PROPERTIES = 1,        /* the emulsion's density and viscosity and fraction_evaporated (:741-759) */
+       ODR_WEATHER_EVAPORATION = 2,       /* evaporation_noaa (:822-853), elements with z == 0 */
+       ODR_WEATHER_EMULSIFICATION = 4,    /* emulsification_noaa (:855-920), elements behind the bullwinkle test */
+       ODR_WEATHER_DISPERSION = 8,        /* disperse_noaa (:792-815), every element */
+       ODR_WEATHER_BIO_HALF_TIME = 16,    /* biodegradation_half_time (:568-586) */
+       ODR_WEATHER_BIO_ADCROFT = 32 };    /* biodegradation_adcroft (:588-611) */
+typedef struct odr_oil_table {
+  int32_t ncomp;                /* 1 .. ODR_OIL_MAXCOMP */
+  int32_t mwf_n;                /* entries of max_water_fraction (one entry of the reference's max_water_fraction.json): 0, 1 or 2 */
+  /* per component, formed by the caller with the reference's NumPy expressions (adios/oil.py:155-166, noaa_oil_weathering.py:26):
+   * [0] D_S * (bp - C_2i)**2 / (D_Zb * R_cal * bp), [1] C_2i, [2] 1 / (bp - C_2i), [3] molecular_weight / 1000 */
+  double comp[4 * ODR_OIL_MAXCOMP];
+  double density, density_ref_temp, density_k;         /* rho(T) = density - density_k (T - density_ref_temp) */
+  double viscosity, viscosity_ref_temp, viscosity_B;   /* nu(T) = viscosity exp(B / T - B / viscosity_ref_temp) */
+  double bulltime, bullwinkle, y_max;                  /* adios/oil.py:123-140 */
+  double mwf_t[2], mwf_w[2];                           /* temperatures [deg C] and max water fractions */
+  double sea_water_density;                            /* PhysicsMethods.sea_water_density() (T = 10, S = 35) */
+} odr_oil_table;
+/* prepare_run (:682-693): the table and a zeroed side table for n_total elements; replaces an earlier one of the particle set, which
+ * frees it with odr_particles_destroy.  ODR_ERR_INVALID for more than ODR_OIL_MAXCOMP components, a NaN, other mwf_n. */
+int odr_oil_weathering_setup(odr_ctx *ctx, odr_particles *p, const odr_oil_table *table, int64_t n_total);
+/* seed_elements and prepare_run (:1726-1755, :686-691) for the rows [id0, id0 + n): records[n][14] in the order of
+ * odr_oil_weathering_get's names (the 14th value is padding), rows[n][ncomp] = mass_fraction * mass_oil */
+int odr_oil_weathering_seed(odr_ctx *ctx, odr_particles *p, int64_t id0, int64_t n, const double *records, const double *rows);
+/* oil_weathering_noaa over the active set (:717-790), `flags` a sum of ODR_WEATHER_*: one reduction for the call-wide decisions --
+ * no surface element or the youngest older than 24 h stops evaporation (:828-834), min(Y_max - sintef) > 0 over the elements that
+ * start to emulsify lets max_water_fraction override Y_max (:888), wave height and period come from the samples when any is > 0,
+ * else from the wind (physics_methods.py:893-943), a zero period takes the mean of the others (:936-939) -- whose results stay on
+ * the device, then ONE launch: Kelvin conversion (:722-724, kept to the launch: the sampled temperature is not rewritten), property
+ * update, evaporation, emulsification, dispersion, biodegradation.  Needs x_wind, y_wind and sea_water_temperature sampled and
+ * the property slots ODR_OIL_DENSITY / ODR_OIL_VISCOSITY set: it stores the emulsion's values there rounded to float32, for the
+ * mixing kernels.  Without ODR_WEATHER_PROPERTIES the launch works on the stored density, viscosity and fraction_evaporated (a
+ * replay from the state in front of one process).  No host synchronisation.  ODR_ERR_STATE without a table or when an element's
+ * ID has no row. */
+int odr_oil_weather(odr_ctx *ctx, odr_particles *p, double dt_seconds, int flags);
+/* one variable of the side table by element ID: out[n_total] for "mass_oil", "mass_evaporated", "mass_dispersed", "mass_biodegraded",
+ * "fraction_evaporated", "water_fraction", "interfacial_area", "density", "viscosity", "bulltime", "biodegradation_half_time_droplet",
+ * "biodegradation_half_time_slick", "oil_film_thickness"; out[n_total][ncomp] for "mass_components" (noaa_mass_balance, :689-691);
+ * out[8] for "reduction": what the last odr_oil_weather decided on (surface elements, their least age, min(Y_max - sintef), the
+ * maxima of wave height and period, the least period, sum and count of the periods > 0).  _set: all but "reduction". */
+int odr_oil_weathering_get(odr_ctx *ctx, odr_particles *p, const char *name, double *out);
+int odr_oil_weathering_set(odr_ctx *ctx, odr_particles *p, const char *name, const double *in);
+/* get_oil_budget's sums at this moment (:1241-1306): out[8] = mass_surface, mass_submerged, mass_stranded, mass_evaporated,
+ * mass_dispersed, mass_biodegraded, mass_total, elements counted.  Active elements and the deactivated store are counted, the
+ * latter with the masses, depth and status they left with (the reference forward-fills its result).  One device reduction with a
+ * fixed fold order: two runs agree bit for bit.  Waits for the stream. */
+int odr_oil_budget(odr_ctx *ctx, odr_particles *p, int32_t stranded_code, double *out);
 /* number of active-set elements currently flagged with status_code (not yet removed by odr_compact) */
 int odr_particles_count_status(odr_ctx *ctx, odr_particles *p, int32_t status_code, int64_t *n);
 /* status_categories grow in the order in which reasons FIRST OCCUR (deactivate_elements, :1778-1781): a caller hands

@@ -60,6 +60,23 @@ class RadioSetup(C.Structure):   # odr_radio_setup
                                    'desorption_depth_uncert', 'resuspension_depth', 'resuspension_depth_uncert', 'resuspension_critvel')]
 
 
+OIL_MAXCOMP = 32      # ODR_OIL_MAXCOMP
+WEATHER = {'properties': 1, 'evaporation': 2, 'emulsification': 4, 'dispersion': 8, 'half_time': 16, 'Adcroft': 32}     # ODR_WEATHER_*
+# the record of odr_oil_weathering_seed / the names of odr_oil_weathering_get
+WEATHER_RECORD = ['mass_oil', 'mass_evaporated', 'mass_dispersed', 'mass_biodegraded', 'fraction_evaporated', 'water_fraction', 'interfacial_area',
+                  'density', 'viscosity', 'bulltime', 'biodegradation_half_time_droplet', 'biodegradation_half_time_slick', 'oil_film_thickness']
+WEATHER_RECORD_N = 14
+WEATHER_REDUCTION = ['n_surface', 'min_age_surface', 'min_ydiff', 'hs_max', 'tp_max', 'tp_min', 'tp_sum', 'tp_count']
+OIL_BUDGET = ['mass_surface', 'mass_submerged', 'mass_stranded', 'mass_evaporated', 'mass_dispersed', 'mass_biodegraded', 'mass_total']
+
+
+class OilTable(C.Structure):   # odr_oil_table
+    _fields_ = [('ncomp', C.c_int32), ('mwf_n', C.c_int32), ('comp', C.c_double * (4 * OIL_MAXCOMP))] + \
+        [(k, C.c_double) for k in ('density', 'density_ref_temp', 'density_k', 'viscosity', 'viscosity_ref_temp', 'viscosity_B', 'bulltime',
+                                   'bullwinkle', 'y_max')] + \
+        [('mwf_t', C.c_double * 2), ('mwf_w', C.c_double * 2), ('sea_water_density', C.c_double)]
+
+
 class ProjDesc(C.Structure):
     _fields_ = [('kind', C.c_int32), ('a', C.c_double), ('es', C.c_double), ('lat0_deg', C.c_double),
                 ('lon0_deg', C.c_double), ('lat_ts_deg', C.c_double), ('k0', C.c_double),
@@ -167,6 +184,12 @@ _SIGNATURES = {
     'odr_radio_speciation': [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int32, C.c_double, C.c_int, _dp, _dp, _dp, _dp, C.c_uint64],
     'odr_radio_terminal_velocity': [_vp, _vp, C.c_int, C.c_int],
     'odr_radio_resuspend': [_vp, _vp, _vp, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_uint64],
+    'odr_oil_weathering_setup': [_vp, _vp, _vp, C.c_int64],
+    'odr_oil_weathering_seed': [_vp, _vp, C.c_int64, C.c_int64, _dp, _dp],
+    'odr_oil_weather': [_vp, _vp, C.c_double, C.c_int],
+    'odr_oil_weathering_get': [_vp, _vp, C.c_char_p, _dp],
+    'odr_oil_weathering_set': [_vp, _vp, C.c_char_p, _dp],
+    'odr_oil_budget': [_vp, _vp, C.c_int32, _dp],
     'odr_vertical_advection': [_vp, _vp, C.c_double, C.c_int],
     'odr_vertical_buoyancy': [_vp, _vp, C.c_double],
     'odr_store_previous': [_vp, _vp],

@@ -124,8 +124,10 @@ struct odr_ctx {
   double step_reduce_wdd = 0.1;
 };
 
+struct odr_weather;      // odr_weather.hip: OpenOil's weathering state by element ID
 struct odr_particles {
   long long cap, n, ndead, dead_cap;
+  odr_weather *weather;    // odr_oil_weathering_setup; freed with the particle set (odr_i_weather_release)
   int ice_kind;         // odr_set_element_factor
   // ranks of the present elements in ascending ID (ensemble members, odr_i_ensure_ranks)
   int *rank;
@@ -392,6 +394,7 @@ static inline int odr_proj_template(const odr::DevProj &p) {
   return p.kind;
 }
 int odr_i_ensure_ranks(odr_ctx *c, odr_particles *p);
+void odr_i_weather_release(odr_particles *p);   // odr_weather.hip
 
 // defined in odrift.hip
 bool odr_i_build_env_group(const odr_ctx *c, const int *grp, int ng, double t, EnvGroupDesc &G);

@@ -166,6 +166,7 @@ int odr_particles_destroy(odr_ctx *c, odr_particles *p) {
   fr(p->scratch);
   fr(p->rank); fr(p->rank_words); fr(p->rank_before); fr(p->rank_bsum);
   fr(p->wg_tab); fr(p->wg_total); fr(p->wg_list); fr(p->z_keep);
+  odr_i_weather_release(p);
   delete p;
   return 0;
 }

@@ -1289,6 +1289,62 @@ class Particles:
                                            _abi.RNG_HOST if host else _abi.RNG_DEVICE, *[a.ctypes.data_as(_dp) if host else None for a in d],
                                            int(step)))
 
+    def weathering_setup(self, oil, n_total, sea_water_density=None):
+        """OpenOil.prepare_run for the NOAA weathering (openoil.py:682-693): the oil as a table (weathering_table's dict) and a zeroed
+        side table for n_total elements, indexed by element ID (odr_oil_weathering_setup)."""
+        t = weathering_table(oil, sea_water_density_default() if sea_water_density is None else sea_water_density)
+        check(self.lib.odr_oil_weathering_setup(self.ctx.h, self.h, C.byref(t), int(n_total)))
+        self._weather_ncomp, self._weather_n_total = int(t.ncomp), int(n_total)
+
+    def weathering_seed(self, id0, mass_oil, mass_fraction, density, viscosity, oil_film_thickness=0.001, bulltime=0.0,
+                        biodegradation_half_time_droplet=1.0, biodegradation_half_time_slick=3.0):
+        """The rows [id0, id0 + len(mass_oil)) as seed_elements and prepare_run leave them (openoil.py:1726-1755, :686-691):
+        mass_components = mass_fraction * mass_oil, the other masses, water_fraction and interfacial_area 0."""
+        mass_oil = np.atleast_1d(np.asarray(mass_oil, np.float64))
+        n = mass_oil.size
+        rec = np.zeros((n, _abi.WEATHER_RECORD_N))
+        for name, v in (('mass_oil', mass_oil), ('density', density), ('viscosity', viscosity), ('oil_film_thickness', oil_film_thickness),
+                        ('bulltime', bulltime), ('biodegradation_half_time_droplet', biodegradation_half_time_droplet),
+                        ('biodegradation_half_time_slick', biodegradation_half_time_slick)):
+            rec[:, _abi.WEATHER_RECORD.index(name)] = v
+        rows = np.ascontiguousarray(np.asarray(mass_fraction, np.float64) * (mass_oil.reshape((n, -1))))      # (:689-691)
+        if rows.shape != (n, self._weather_ncomp):
+            raise ValueError('mass_fraction of %d components for a table of %d' % (rows.shape[1], self._weather_ncomp))
+        check(self.lib.odr_oil_weathering_seed(self.ctx.h, self.h, int(id0), n, rec.ctypes.data_as(_dp), rows.ctypes.data_as(_dp)))
+
+    def oil_weather(self, dt, processes=('properties', 'evaporation', 'emulsification', 'dispersion')):
+        """OpenOil.oil_weathering_noaa over the active set (openoil.py:717-790; odr_oil_weather): processes by name, 'half_time' /
+        'Adcroft' for biodegradation.  Density and viscosity of the emulsion go to the oil's property slots as float32."""
+        flags = 0
+        for k in processes:
+            flags |= _abi.WEATHER[k]
+        check(self.lib.odr_oil_weather(self.ctx.h, self.h, float(dt), flags))
+
+    def weathering_get(self, name):
+        """One variable of the weathering table BY ELEMENT ID (odr_oil_weathering_get): [n_total], 'mass_components' [n_total, ncomp],
+        'reduction' {name: value} of the last oil_weather call."""
+        n = 8 if name == 'reduction' else self._weather_n_total * (self._weather_ncomp if name == 'mass_components' else 1)
+        out = np.empty(n)
+        check(self.lib.odr_oil_weathering_get(self.ctx.h, self.h, name.encode(), out.ctypes.data_as(_dp)))
+        if name == 'reduction':
+            return dict(zip(_abi.WEATHER_REDUCTION, out))
+        return out.reshape(self._weather_n_total, -1) if name == 'mass_components' else out
+
+    def weathering_set(self, name, values):
+        a = np.ascontiguousarray(values, dtype=np.float64)
+        if a.size != self._weather_n_total * (self._weather_ncomp if name == 'mass_components' else 1):
+            raise ValueError('%s: %d values for a table of %d elements' % (name, a.size, self._weather_n_total))
+        check(self.lib.odr_oil_weathering_set(self.ctx.h, self.h, name.encode(), a.ctypes.data_as(_dp)))
+
+    def oil_budget(self, stranded_code):
+        """get_oil_budget's sums now (openoil.py:1241-1306; odr_oil_budget): {mass_surface, ..., mass_total}, active and deactivated
+        elements counted, and 'n', how many."""
+        out = np.empty(8)
+        check(self.lib.odr_oil_budget(self.ctx.h, self.h, int(stranded_code), out.ctypes.data_as(_dp)))
+        b = dict(zip(_abi.OIL_BUDGET, out[:7]))
+        b['n'] = int(out[7])
+        return b
+
     def vertical_advection(self, dt, at_surface=False):
         check(self.lib.odr_vertical_advection(self.ctx.h, self.h, float(dt), int(at_surface)))
 
@@ -1552,7 +1608,7 @@ for _name in ('append', 'upload', 'env_sample', 'umesh_sample', 'shape_sample', 
               'increase_age', 'deactivate_missing', 'remap_status', 'seafloor', 'deactivate', 'deactivate_outside', 'compact',
               'compact_apply', 'sort_by_cell', 'store_previous', 'oil_prepare_mixing', 'env_coast_leeway', 'egg_terminal_velocity',
               'resuspend', 'larval_update', 'larval_migrate', 'larvalx_hatch', 'larvalx_behave', 'berg_roll_over', 'berg_advect', 'ship_drift', 'radio_speciation',
-              'radio_terminal_velocity', 'radio_resuspend'):
+              'radio_terminal_velocity', 'radio_resuspend', 'oil_weather'):
     setattr(Particles, _name, _touching(getattr(Particles, _name)))
 
 
@@ -1730,6 +1786,47 @@ class Combined:
             self.close()
         except Exception:
             pass
+
+
+def weathering_table(oil, sea_water_density):
+    """odr_oil_table of an oil given as a dict (OpenOil.set_oiltype): the per-component constants of OpendriftOil.vapor_pressure
+    (adios/oil.py:155-166) and of evap_decay_constant (noaa_oil_weathering.py:26) formed here with the reference's NumPy
+    expressions, the two property curves, the emulsification constants."""
+    boiling_point = np.asarray(oil['boiling_point'], dtype=np.float64)
+    n = boiling_point.size
+    if not 1 <= n <= _abi.OIL_MAXCOMP:
+        raise ValueError('an oil of %d pseudo-components: the device table holds 1 .. %d (ODR_OIL_MAXCOMP)' % (n, _abi.OIL_MAXCOMP))
+    D_Zb = 0.97
+    R_cal = 1.987
+    D_S = 8.75 + 1.987 * np.log(boiling_point)
+    C_2i = 0.19 * boiling_point - 18
+    t = _abi.OilTable()
+    comp = np.zeros((4, _abi.OIL_MAXCOMP))
+    comp[0, :n] = D_S * (boiling_point - C_2i)**2 / (D_Zb * R_cal * boiling_point)
+    comp[1, :n] = C_2i
+    comp[2, :n] = 1. / (boiling_point - C_2i)
+    comp[3, :n] = np.asarray(oil['molecular_weight'], dtype=np.float64) / 1000.
+    comp[3, n:] = 1.0
+    t.ncomp = n
+    t.comp[:] = comp.ravel().tolist()
+    defaults = {'density_ref_temp': 288.15, 'density_k': 0.0, 'viscosity_ref_temp': 288.15, 'viscosity_B': 0.0}      # the curves are constants
+    for k in ('density', 'density_ref_temp', 'density_k', 'viscosity', 'viscosity_ref_temp', 'viscosity_B'):
+        setattr(t, k, float(oil[k] if k in oil else defaults[k]))
+    bt = oil.get('bullwinkle_time')
+    t.bulltime = -999. if bt is None or bt != bt else float(bt)        # adios/oil.py:125-130
+    t.bullwinkle = float(oil['bullwinkle_fraction'])
+    t.y_max = float(oil['emulsion_water_fraction_max'])
+    mwf = oil.get('max_water_fraction')
+    t.mwf_n = 0
+    if mwf is not None:
+        T, w = list(mwf['temperatures']), list(mwf['max_water_fraction'])
+        if len(T) != len(w) or len(T) not in (1, 2):
+            raise ValueError('max_water_fraction takes one or two temperatures with as many fractions')
+        t.mwf_n = len(T)
+        for k in range(len(T)):
+            t.mwf_t[k], t.mwf_w[k] = float(T[k]), float(w[k])
+    t.sea_water_density = float(sea_water_density)
+    return t
 
 
 class RadioSetup:
