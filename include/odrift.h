@@ -206,6 +206,24 @@ int odr_block_drop(odr_ctx *ctx, int32_t source_id, int32_t slot);
  * node records in the plane's layout, which the plane equals bit for bit; synchronous. */
 int odr_block_kplane_read(odr_ctx *ctx, int32_t source_id, int32_t slot, int32_t *krec, float *plane_out, float *records_out,
                           uint64_t cap_floats);
+/* Debugging / tests: one variable of a resident level as the preparation left it -- convolved (odr_source_set_convolution), masked,
+ * filled towards the sea floor and dilated -- gathered from the node records into a plain float32 [*nz][ny][nx] array.  *nz = 0: the
+ * level does not hold the variable.  out may be NULL (only *nz is wanted); cap_floats >= *nz * ny * nx; synchronous. */
+int odr_block_read(odr_ctx *ctx, int32_t source_id, int32_t slot, int32_t var_id, int32_t *nz, float *out, uint64_t cap_floats);
+/* StructuredReader.set_convolution_kernel + __convolve_block__ (readers/basereader/structured.py:163-192, applied :278-306): every
+ * level of the grid source uploaded AFTER this call -- odr_block_upload, _async, _device and odr_block_broadcast alike -- is
+ * convolved on the upload stream before it is masked, filled and dilated, with the arithmetic of scipy.ndimage.convolve(array,
+ * weights, mode='nearest'): one double accumulator per cell, the terms (double)value * weight added in C order of the flipped
+ * kernel, weights with |w| <= DBL_EPSILON left out, the sum rounded once to float32 (csrc/odr_convolve.hip.h).  weights: [ky][kx]
+ * doubles as the reference hands them to SciPy (an int N there means ones((N, N)) / N**2: the caller forms it), not normalised
+ * here; 1 <= ky, kx <= 15.  A 2-D variable is convolved over (y, x); a 3-D one with weights[:, :, None], i.e. over (z, y) -- the
+ * reference's behaviour.  Every variable of the level is convolved, land_binary_mask and sea_floor_depth_below_sea_level included.
+ * vars3d[n3d]: the variables the reader hands out as 3-D arrays of ONE layer ([1][ny][nx]; var_nz says 1 for them as for a 2-D
+ * array): the reference convolves such an array over (z, y) like any 3-D one, and so does the upload.  ky = kx = 0 (the other
+ * arguments ignored) switches it off.  Levels already resident stay as they are.  ODR_ERR_INVALID for a larger kernel, and at the
+ * upload of a level with ensemble members (odr_source_set_members). */
+int odr_source_set_convolution(odr_ctx *ctx, int32_t source_id, int32_t ky, int32_t kx, const double *weights, int32_t n3d,
+                               const int32_t *vars3d);
 /* drift:truncate_ocean_model_below_m (models/basemodel/environment.py:554-566): every get_environment call samples the readers
  * at max(z, -truncate_depth) while the elements keep their depth.  odr_particles_truncate_z puts the clipped depths in place for
  * the sampling calls that follow (odr_env_sample, odr_advect / odr_env_coast_advect: the Runge-Kutta stage calls are

@@ -41,6 +41,7 @@ HIST = {'lon': 1000, 'lat': 1001, 'z': 1002, 'status': 1003, 'moving': 1004, 'ag
         'wind_drift_factor': 1006, 'current_drift_factor': 1007, 'terminal_velocity': 1008}
 HIST_PROPERTY0 = 2000
 COMM_ID_BYTES = 256      # ODR_COMM_ID_BYTES
+CONVOLVE_MAX_EDGE = 15   # CONV_MAX (csrc/odr_convolve.hip.h): the largest kernel odr_source_set_convolution takes
 
 
 class StepExtras(C.Structure):   # odr_step_extras
@@ -128,6 +129,8 @@ _SIGNATURES = {
     'odr_host_unregister': [_vp, _vp],
     'odr_block_drop': [_vp, C.c_int32, C.c_int32],
     'odr_block_kplane_read': [_vp, C.c_int32, C.c_int32, _ip, _fp, _fp, C.c_uint64],
+    'odr_block_read': [_vp, C.c_int32, C.c_int32, C.c_int32, _ip, _fp, C.c_uint64],
+    'odr_source_set_convolution': [_vp, C.c_int32, C.c_int32, C.c_int32, _dp, C.c_int32, _ip],
     'odr_env_bind': [_vp, C.c_int32, C.c_int, _ip, C.c_float],
     'odr_env_sample': [_vp, _vp, C.c_int, _ip, C.c_double, _P(_fp)],
     'odr_env_download': [_vp, _vp, C.c_int32, _fp],

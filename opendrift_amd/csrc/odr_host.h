@@ -82,6 +82,10 @@ struct odr_ctx {
   int *dilate_flags;   // [NVAR][16]: "sweep k gave a cell a value" (k_blk_dilate_row stops at the fixed point)
   int *tile_flags = nullptr;   // [layer][44x44-cell tile]: the tile still holds a NaN after mask + sea-floor fill (k_blk_mask_fill)
   size_t tile_flags_n = 0;
+  // reader.convolve of a grid source (odr_source_set_convolution): weights[ky][kx] as given; ky = 0: none
+  int conv_ky[MAXSRC] = {0}, conv_kx[MAXSRC] = {0};
+  unsigned conv_3d[MAXSRC] = {0};      // bit v: variable v is a 3-D array even when it holds ONE layer
+  std::vector<double> conv_w[MAXSRC];
   // page-locked bounce buffers for copies from / to caller memory: [0] compute stream, [1] upload stream (odr_i_h2d)
   void *bounce[2];
   Staged staged[MAXSRC][MAXLEVELS];
@@ -403,6 +407,9 @@ void odr_i_proj_init(odr::DevProj &p, const odr_proj_desc *d);   // the device i
 bool odr_i_comm_on();
 int odr_i_comm_rank();
 int odr_i_comm_bcast_floats(float *dev, size_t count, int root, hipStream_t st);
+// odr_convolve.hip: the convolution of a source's levels in front of their preparation
+bool odr_i_source_convolves(const odr_ctx *c, int32_t sid);
+int odr_i_blk_convolve(odr_ctx *c, int32_t sid, int var, const float *src, float *dst, int nzv, int ny, int nx, hipStream_t st);
 void odr_i_phase_dump();   // odr_step.hip
 bool odr_i_uv_fast_source(const odr_ctx *c, int &sid, double t_lo, double t_hi);
 

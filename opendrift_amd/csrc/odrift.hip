@@ -700,6 +700,12 @@ static int stage_block(odr_ctx *c, int32_t sid, int32_t slot, double t_epoch, in
     nlayers += (size_t)nzv;
   }
   nmax = std::max(nmax, ntot);   // the whole level is staged at once (prep_all below)
+  // reader.convolve (odr_source_set_convolution): the level arrives in the SECOND staging array and the first pass of the
+  // preparation, k_blk_convolve / k_blk_convolve_zy per variable, writes it convolved into the first -- where the unconvolved level
+  // of any other source arrives.  The second array is free until k_blk_dilate_tile writes the dilated values there, behind it on
+  // the same stream: the pass adds no staging memory.
+  const bool conv = odr_i_source_convolves(c, sid);
+  if (conv) for (int k = 0; k < nvars; ++k) REQUIRE(s.members[var_ids[k]] <= 1, "source %d convolves its levels: ensemble members (variable %d) are not convolved", sid, var_ids[k]);
   // record layout: interleaved vector pairs first, then the other 3D variables, then the 2D ones; the record
   // length is padded to 16 bytes (odr_field.hip.h DevBlock)
   static const int pairs[4][2] = {{VAR_U, VAR_V}, {VAR_XWIND, VAR_YWIND}, {VAR_SX, VAR_SY}, {VAR_ICE_U, VAR_ICE_V}};
@@ -792,7 +798,7 @@ static int stage_block(odr_ctx *c, int32_t sid, int32_t slot, double t_epoch, in
     for (int k = 0; k < nvars; ++k) {
       const int v = var_ids[k], nzv = var_nz[k] > 1 ? var_nz[k] : 1;
       const size_t n = plane * (size_t)nzv;
-      float *buf = c->prep[0] + at_f;
+      float *buf = (conv ? c->prep[1] : c->prep[0]) + at_f;
       hipPointerAttribute_t at;
       bool pageable = false;
       if (!have_data) {}
@@ -801,7 +807,7 @@ static int stage_block(odr_ctx *c, int32_t sid, int32_t slot, double t_epoch, in
       if (!have_data) {}      // (arrives with the broadcast below)
       else if (pageable) { int rcb = odr_i_h2d(c, buf, data[k], sizeof(float) * n, st, 1); if (rcb) return rcb; }
       else HIPCHK(hipMemcpyAsync(buf, data[k], sizeof(float) * n, hipMemcpyDefault, st));
-      Q.src[k] = buf; Q.fix[k] = c->prep[1] + at_f;
+      Q.src[k] = c->prep[0] + at_f; Q.fix[k] = c->prep[1] + at_f;
       Q.nz[k] = nzv; Q.cum[k] = cum; Q.off[k] = off[(size_t)k]; Q.es[k] = es[(size_t)k]; Q.eo[k] = eo[(size_t)k];
       Q.fill[k] = nzv > 1 && s.members[v] <= 1;     // ("Ensemble data currently not extrapolated towards seafloor", structured.py:58-60)
       Q.dil[k] = v != VAR_LAND;
@@ -813,8 +819,12 @@ static int stage_block(odr_ctx *c, int32_t sid, int32_t slot, double t_epoch, in
     }
     Q.cum[nvars] = cum;
     if (bcast_root >= 0) {   // every variable of the level in one collective, in place, behind root's copies on this stream
-      int rcb = odr_i_comm_bcast_floats(c->prep[0], at_f, bcast_root, st);
+      int rcb = odr_i_comm_bcast_floats(conv ? c->prep[1] : c->prep[0], at_f, bcast_root, st);
       if (rcb) return rcb;
+    }
+    for (int k = 0; k < nvars && conv; ++k) {
+      int rcc = odr_i_blk_convolve(c, sid, var_ids[k], Q.fix[k], Q.src[k], Q.nz[k], ny, nx, st);
+      if (rcc) return rcc;
     }
     hipLaunchKernelGGL(k_blk_mask_fill, dim3((unsigned)((nx + BLOCK - 1) / BLOCK), (unsigned)ny, (unsigned)nvars), dim3(BLOCK), 0, st,
                        Q, c->tile_flags);
@@ -829,6 +839,7 @@ static int stage_block(odr_ctx *c, int32_t sid, int32_t slot, double t_epoch, in
     const int v = var_ids[k], nzv = var_nz[k] > 1 ? var_nz[k] : 1;
     const size_t n = plane * (size_t)nzv;
     float *buf = c->prep[0], *tmp = c->prep[1];
+    float *arrive = conv ? tmp : buf;
     // data[k]: device memory, page-locked host memory (odr_host_register / hipHostMalloc: a true asynchronous DMA), or
     // pageable host memory -- the latter through the upload stream's bounce buffer (see odr_i_h2d), which makes this
     // variable's copy synchronous for the host
@@ -837,9 +848,10 @@ static int stage_block(odr_ctx *c, int32_t sid, int32_t slot, double t_epoch, in
       bool pageable = false;
       if (hipPointerGetAttributes(&at, data[k]) != hipSuccess) { (void)hipGetLastError(); pageable = true; }
       else pageable = at.type != hipMemoryTypeDevice && at.type != hipMemoryTypeHost && at.type != hipMemoryTypeManaged;
-      if (pageable) { int rcb = odr_i_h2d(c, buf, data[k], sizeof(float) * n, st, 1); if (rcb) return rcb; }
-      else HIPCHK(hipMemcpyAsync(buf, data[k], sizeof(float) * n, hipMemcpyDefault, st));
+      if (pageable) { int rcb = odr_i_h2d(c, arrive, data[k], sizeof(float) * n, st, 1); if (rcb) return rcb; }
+      else HIPCHK(hipMemcpyAsync(arrive, data[k], sizeof(float) * n, hipMemcpyDefault, st));
     }
+    if (conv) { int rcc = odr_i_blk_convolve(c, sid, v, tmp, buf, nzv, ny, nx, st); if (rcc) return rcc; }
     const unsigned g = (unsigned)((n + BLOCK - 1) / BLOCK);
     hipLaunchKernelGGL(k_blk_mask, dim3(g), dim3(BLOCK), 0, st, buf, n);
     // ("Ensemble data currently not extrapolated towards seafloor", readers/interpolation/structured.py:58-60)
@@ -1035,6 +1047,34 @@ int odr_block_kplane_read(odr_ctx *c, int32_t sid, int32_t slot, int32_t *krec, 
   return 0;
 }
 
+// one variable of the node records as a plain [nz][ny][nx] array (odr_block_read)
+__global__ __launch_bounds__(BLOCK) void k_blk_record_var(const float *__restrict__ data, int rec, int es, int nz, size_t plane, float *__restrict__ out) {
+  const size_t q = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (q >= plane * (size_t)nz) return;
+  const size_t k = q / plane, node = q - k * plane;
+  out[q] = data[node * (size_t)rec + k * (size_t)es];
+}
+int odr_block_read(odr_ctx *c, int32_t sid, int32_t slot, int32_t var, int32_t *nz, float *out, uint64_t cap_floats) {
+  REQUIRE(sid >= 0 && sid < c->nsrc && slot >= 0 && slot < MAXLEVELS && nz, "bad source/slot");
+  REQUIRE(var >= 0 && var < NVAR, "bad variable id %d", var);
+  const DevBlock &b = c->hw.src[sid].slot[slot];
+  REQUIRE(b.valid, "no resident block for source %d slot %d", sid, slot);
+  *nz = b.data[var] ? b.var_nz[var] : 0;
+  if (!b.data[var] || !out) return 0;
+  const size_t plane = (size_t)b.ny * b.nx, n = plane * (size_t)b.var_nz[var];
+  REQUIRE(cap_floats >= n, "the variable holds %zu floats", n);
+  HIPCHK(hipSetDevice(c->device));
+  float *tmp = nullptr;
+  HIPCHK(hipMalloc((void **)&tmp, sizeof(float) * n));
+  struct Free { float *p; ~Free() { (void)hipFree(p); } } free_tmp{tmp};   // on every way out
+  hipLaunchKernelGGL(k_blk_record_var, dim3((unsigned)((n + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, c->stream, b.data[var], b.rec, b.es[var],
+                     b.var_nz[var], plane, tmp);
+  HIPCHK(hipGetLastError());
+  D2H(out, tmp, sizeof(float) * n);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return 0;
+}
+
 // A source the caller no longer uses (a gridded reader whose blocks were re-cut to a new window gets a new source): its
 // resident blocks are dropped, it leaves every priority list, and its id is handed out again by the next odr_source_*.
 int odr_source_release(odr_ctx *c, int32_t sid) {
@@ -1054,6 +1094,9 @@ int odr_source_release(odr_ctx *c, int32_t sid) {
   for (int v = 0; v < NVAR; ++v) s.const_val[v] = NAN;
   s.xmin = s.ymin = s.zmin = s.tmin = INFINITY; s.xmax = s.ymax = s.zmax = s.tmax = -INFINITY;
   c->src_free[sid] = true;
+  c->conv_ky[sid] = c->conv_kx[sid] = 0;
+  c->conv_3d[sid] = 0;
+  c->conv_w[sid].clear();
   c->src_gen[sid]++;
   if (c->red_owner) c->red_owner = nullptr;
   c->dirty = true;

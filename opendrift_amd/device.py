@@ -415,6 +415,33 @@ class Context:
                                              plane.size))
         return plane, recs
 
+    def read_block(self, sid, slot, variable):
+        """Debugging / tests (odr_block_read): one variable of a resident level as the preparation left it, float32 [ny, nx] or
+        [nz, ny, nx]; None when the level does not hold it."""
+        g = self._grids[sid]
+        nz = C.c_int32(0)
+        check(self.lib.odr_block_read(self.h, sid, slot, self._vid(variable), C.byref(nz), None, 0))
+        if nz.value == 0:
+            return None
+        out = np.empty((nz.value, g['ny'], g['nx']), dtype=np.float32)
+        check(self.lib.odr_block_read(self.h, sid, slot, self._vid(variable), C.byref(nz), out.ctypes.data_as(_fp), out.size))
+        return out[0] if nz.value == 1 else out
+
+    def set_convolution(self, sid, kernel, three_d=()):
+        """StructuredReader.set_convolution_kernel for the levels of a grid source uploaded from now on (odr_source_set_convolution).
+        kernel: the 2-D array of weights the reference hands to scipy.ndimage.convolve, or None to switch it off; three_d: the
+        variables that arrive as 3-D arrays of one layer, [1, ny, nx] (convolved over z and y like every 3-D array)."""
+        if kernel is None:
+            check(self.lib.odr_source_set_convolution(self.h, sid, 0, 0, None, 0, None))
+            return
+        w = np.ascontiguousarray(kernel, dtype=np.float64)
+        if w.ndim != 2 or w.size == 0:
+            raise ValueError('a convolution kernel is a 2-D array of weights, got shape %s' % (w.shape,))
+        if max(w.shape) > _abi.CONVOLVE_MAX_EDGE:
+            raise ValueError('convolution kernel of %d x %d weights: at most %d x %d fit' % (w.shape + (_abi.CONVOLVE_MAX_EDGE,) * 2))
+        ids, pi = _i([self._vid(v) for v in three_d]) if len(three_d) else (None, None)
+        check(self.lib.odr_source_set_convolution(self.h, sid, w.shape[0], w.shape[1], w.ctypes.data_as(_dp), len(three_d), pi))
+
     def release_source(self, sid):
         """The source is no longer used: its blocks are dropped, its id is free for the next add_* (odr_source_release)."""
         check(self.lib.odr_source_release(self.h, int(sid)))

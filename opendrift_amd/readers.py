@@ -146,12 +146,85 @@ class ContinuousReader(BaseReader):
         return env, None
 
 
+def convolution_weights(convolve):
+    """The kernel __convolve_block__ hands to scipy.ndimage.convolve (structured.py:173-178): ones((N, N)) / ones((N, N)).sum() for
+    an int N, else the argument itself as a float64 array."""
+    if isinstance(convolve, (int, np.integer)):
+        kernel = np.ones((convolve, convolve))
+        return kernel / kernel.sum()
+    return np.asarray(convolve, dtype=np.float64)
+
+
+def _convolve_nearest(a, kernel):
+    """scipy.ndimage.convolve(a, kernel[..., None] if a is 3-D else kernel, mode='nearest') restated -- the kernel over the first
+    two axes of `a`: a correlation with the kernel flipped along both axes, centred at size // 2 (one less along an axis of even
+    size), indices clamped to the edge; one float64 accumulator per cell, the terms float64(value) * weight added in C order of
+    the flipped kernel, weights with |w| <= DBL_EPSILON left out; rounded once to the array's dtype."""
+    flipped = kernel[::-1, ::-1]
+    n0, n1 = a.shape[:2]
+    c = [s // 2 - (1 if s % 2 == 0 else 0) for s in kernel.shape]
+    pad = [(c[0], kernel.shape[0] - 1 - c[0]), (c[1], kernel.shape[1] - 1 - c[1])] + [(0, 0)] * (a.ndim - 2)
+    p = np.pad(a, pad, mode='edge').astype(np.float64)
+    acc = np.zeros(a.shape, np.float64)
+    with np.errstate(invalid='ignore', over='ignore'):
+        for i in range(kernel.shape[0]):
+            for j in range(kernel.shape[1]):
+                w = float(flipped[i, j])
+                if abs(w) > np.finfo(np.float64).eps:
+                    acc = acc + p[i:i + n0, j:j + n1] * w
+        return acc.astype(a.dtype)
+
+
+def convolve_block(env, convolve):
+    """StructuredReader.__convolve_block__ (structured.py:167-192) without SciPy: every variable of the block but 'x', 'y', 'z' and
+    'time' -- land_binary_mask and sea_floor_depth_below_sea_level included -- convolved in place with the kernel of
+    set_convolution_kernel; a 2-D variable over (y, x), a 3-D variable [nz, ny, nx] with kernel[:, :, None], i.e. over (z, y): x is
+    not smoothed there (the reference's behaviour).  Returns env.  The arithmetic is the device pass's (csrc/odr_convolve.hip.h):
+    equal to scipy.ndimage.convolve bit for bit.  The one deviation: the entries of a masked array count as NaN, as in every
+    upload here; the reference convolves whatever data lie under the mask."""
+    if convolve is None:
+        return env
+    kernel = convolution_weights(convolve)
+    if kernel.ndim != 2:
+        raise ValueError('a convolution kernel is an int or a 2-D array of weights, got shape %s' % (kernel.shape,))
+    for v in env:
+        if v in ('x', 'y', 'z', 'time') or isinstance(env[v], str):
+            continue
+        if isinstance(env[v], (list, tuple)):
+            if v == 's_level_variables':
+                continue
+            raise NotImplementedError('ensemble members (%s) are not convolved: the reference fails on the list' % v)
+        a = env[v]
+        a = np.ma.filled(a, np.nan) if isinstance(a, np.ma.MaskedArray) else np.asarray(a)
+        if a.ndim in (2, 3):
+            env[v] = _convolve_nearest(a, kernel)
+    return env
+
+
 class StructuredReader(BaseReader):
     """basereader/structured.py.  A reader that sets no projection (`proj4` None or 'fakeproj') but has 2D `lon` /
     `lat` node arrays is 'unprojected' (structured.py:44-113): x/y are pixel indices, xy2lonlat is bilinear in the
     node arrays (:421-436) and lonlat2xy is the Delaunay lookup (:438-472) -- which runs on the device
     (odr_source_grid_curvilinear); on the host it is available once the reader is bound to a device context."""
     projected = True
+    convolve = None      # set_convolution_kernel
+
+    def set_convolution_kernel(self, convolve):
+        """structured.py:163-165: a convolution kernel, or the size N of a box mean, that every block of this reader is convolved
+        with before it is prepared (__convolve_block__, :167-192: scipy.ndimage.convolve(..., mode='nearest') of every variable;
+        a 3-D variable with kernel[:, :, None], i.e. over z and y) -- on the device, as the first pass of the level's preparation
+        (odr_source_set_convolution; convolve_block is the same arithmetic on the host).  An int N means np.ones((N, N)) / N**2;
+        anything else is taken as a 2-D array of weights as given, not normalised; None switches it off.  Levels that are
+        resident on the device when the kernel changes stay as they are.  ValueError for a kernel that is not 2-D or has an
+        edge longer than _abi.CONVOLVE_MAX_EDGE."""
+        if convolve is not None:
+            k = convolution_weights(convolve)
+            if k.ndim != 2 or k.size == 0:
+                raise ValueError('reader %s: a convolution kernel is an int or a 2-D array of weights, got shape %s' % (self.name, k.shape))
+            if max(k.shape) > _abi.CONVOLVE_MAX_EDGE:
+                raise ValueError('reader %s: convolution kernel of %d x %d weights, at most %d x %d fit the device pass'
+                                 % ((self.name,) + k.shape + (_abi.CONVOLVE_MAX_EDGE,) * 2))
+        self.convolve = convolve
 
     def __init__(self):
         if self.proj4 is None or self.proj4 == 'fakeproj':
@@ -1502,7 +1575,10 @@ class DeviceReaderBinding:
                 continue
             if k in self.staged:     # prefetched on the upload stream while the previous steps ran
                 self.slots[k] = self.staged.pop(k)
-                self.ctx.commit_block(self.sid, self.slots[k])
+                import time as _time
+                t_wait = _time.perf_counter()
+                self.ctx.commit_block(self.sid, self.slots[k])      # (waits for the upload stream if the level is not ready yet)
+                self.stall_s += _time.perf_counter() - t_wait
                 continue
             self._upload(k, extent, broadcast, asynchronous=False)
         # prefetch the time level the run will need next (readers whose arrays live in host memory)
@@ -1690,6 +1766,21 @@ class DeviceReaderBinding:
         meta, tens, works = self._read_and_broadcast(kn, x, y, async_op=True)
         self._dist_pre[kn] = (tens, works)
 
+    def _bind_convolution(self, block):
+        """reader.convolve (set_convolution_kernel) -> the device source, before a level is uploaded: the upload's preparation
+        convolves it (odr_source_set_convolution) whichever way it arrives -- synchronous, asynchronous, from device memory
+        (s-levels regridded to z first, as the reference convolves what get_variables returns) or by odr_block_broadcast in a
+        sharded run, where every rank holds the reader object and so the kernel."""
+        conv = getattr(self.reader, 'convolve', None)
+        if conv is not None and any(isinstance(block.get(v), (list, tuple)) or v in getattr(self, '_dist_members', {}) for v in self.variables):
+            raise NotImplementedError('reader %s convolves its blocks and hands out ensemble members: the reference fails on the '
+                                      'list of members (structured.py:184)' % self.reader.name)
+        # (a host call without device work, made per level: the kernel may change between levels, and a re-cut window is a new source)
+        if conv is not None or getattr(self, '_convolved', False):
+            one_layer = [v for v in self.variables if len(getattr(block.get(v), 'shape', ())) == 3 and block[v].shape[0] == 1]
+            self.ctx.set_convolution(self.sid, None if conv is None else convolution_weights(conv), three_d=one_layer)
+        self._convolved = conv is not None
+
     def _page_locked(self, v, arr):
         if isinstance(arr, (list, tuple)):       # ensemble members: stacked by the context
             return arr
@@ -1790,6 +1881,7 @@ class DeviceReaderBinding:
             g = self.ctx._grids[self.sid]
             if (len(by), len(bx)) != (g['ny'], g['nx']):
                 raise ValueError('reader %s changed its block shape between time levels' % r.name)
+        self._bind_convolution(block)
         free = [s for s in range(self.NSLOTS) if s not in self.slots.values() and s not in self.staged.values()]
         slot = free[0]
         t_ep = _epoch(time) if time is not None else 0.0
