@@ -454,6 +454,28 @@ int odr_oil_set_mixing_stats(odr_ctx *ctx, double mean_zb, double dv50);
  * not been set.  Enqueued on the context's stream; no host synchronisation. */
 enum { ODR_EGG_DIAMETER = 0, ODR_EGG_NEUTRAL_BUOYANCY_SALINITY = 1, ODR_EGG_DENSITY = 2, ODR_EGG_HATCHED = 3 };
 int odr_egg_terminal_velocity(odr_ctx *ctx, odr_particles *p, int diameter_slot, int salinity_slot);
+/* drift:use_tabularised_stokes_drift (models/basemodel/environment.py:844-863): sea_surface_wave_stokes_drift_{x,y}_velocity
+ * (ODR_PLAST_STOKES) and / or sea_surface_wave_significant_height (ODR_PLAST_HS) of every active element from the sampled float32
+ * x_wind / y_wind, as wave_stokes_drift_parameterised and wave_significant_height_parameterised form them
+ * (models/physics_methods.py:488-527, :530-568): float64 wind speed capped at 30, np.polyval as a float64 Horner chain, one
+ * rounding into the float32 environment (csrc/odr_plast.hip.h).  stokes_coeff: the n_stokes (1 .. 7) coefficients of the drift
+ * factor for the configured fetch, leading one first; hs_coeff: the two of the wave height.  They are np.polyfit's over the
+ * reference's tables and come from the caller.  The slots are allocated where they were not sampled.  ODR_ERR_STATE when the wind
+ * has not been sampled.  One launch on the context's stream; no host synchronisation. */
+enum { ODR_PLAST_STOKES = 1, ODR_PLAST_HS = 2 };
+int odr_stokes_from_wind(odr_ctx *ctx, odr_particles *p, const double *stokes_coeff, int n_stokes, const double *hs_coeff, int flags);
+/* What environment.py:847-858 asks before it replaces anything: out3 = the plain maxima of Stokes x, Stokes y and the wave height
+ * over the active elements (-inf: not sampled, or no active element).  Slots of the movers' reduction (odr_reduce_scalars), behind
+ * the sixteen that call hands out; ODR_ERR_INVALID while a reduction combined over the ranks of a sharded run is installed. */
+int odr_reduce_wave_maxima(odr_ctx *ctx, odr_particles *p, double *out3);
+/* PlastDrift.update_particle_depth with vertical_mixing:mixingmodel = 'analytical' (models/plastdrift.py:94-107): z of every
+ * active element is drawn anew, z = -(K / w) E with K the sampled float32 ocean_vertical_diffusivity, w the float32 terminal
+ * velocity (one float32 division, widened) and E a standard exponential: draws[i] for element i of the set (ODR_RNG_HOST: what
+ * np.random.standard_exponential(n) gave, in the order of the set) or the device generator's (ODR_RNG_DEVICE: -log1p(-u) of the
+ * uniform in [0, 1) from the element's Philox block of `step`).  A scale NumPy refuses (sign bit set and not NaN: ValueError
+ * 'scale < 0') on ANY active element: ODR_ERR_INVALID and no z of the call changed.  Elements that are not active are not
+ * touched.  ODR_ERR_STATE when the diffusivity has not been sampled.  Two launches; the host waits for the flag of the first. */
+int odr_plast_depth(odr_ctx *ctx, odr_particles *p, int rng_mode, const double *draws, uint64_t step);
 /* LarvalFish (models/larvalfish.py; Kvile et al. 2018).  The element properties of LarvalFishElement (:31-52) in the property
  * slots of odr_particles_set_property, float32 all seven: `hatched` (uint8 in the reference) holds 0 (egg) or 1 (larva).  The
  * terminal velocity of the model (:105-183) is odr_egg_terminal_velocity with these slot numbers. */

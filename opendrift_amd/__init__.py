@@ -21,4 +21,7 @@ def __getattr__(name):      # the model classes import the device binding: resol
     if name == 'LarvalFishExtended':
         from .larvalfish_extended import LarvalFishExtended
         return LarvalFishExtended
+    if name == 'PlastDrift':
+        from .plastdrift import PlastDrift
+        return PlastDrift
     raise AttributeError('module %r has no attribute %r' % (__name__, name))

@@ -169,6 +169,9 @@ _SIGNATURES = {
     'odr_oil_local_sums': [_vp, _vp, C.c_double, C.c_double, C.c_int, C.c_int, _dp, _dp],
     'odr_oil_set_mixing_stats': [_vp, C.c_double, C.c_double],
     'odr_egg_terminal_velocity': [_vp, _vp, C.c_int, C.c_int],
+    'odr_stokes_from_wind': [_vp, _vp, _dp, C.c_int, _dp, C.c_int],
+    'odr_reduce_wave_maxima': [_vp, _vp, _dp],
+    'odr_plast_depth': [_vp, _vp, C.c_int, _dp, C.c_uint64],
     'odr_resuspend': [_vp, _vp, C.c_float, _i64p],
     'odr_larval_update': [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double],
     'odr_larval_migrate': [_vp, _vp, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int],
@@ -331,6 +334,7 @@ DROPLETS = {'Johansen et al. (2015)': 1, 'Li et al. (2017)': 2}
 OIL_PROPERTIES = ['diameter', 'density', 'viscosity', 'oil_film_thickness', 'diameter_if_entrained']
 SEAFLOOR = {'none': 0, 'lift_to_seafloor': 1, 'deactivate': 2, 'previous': 3, 'settle': 4, 'settle_species': 5}     # include/odrift.h ODR_SEAFLOOR_*
 RADIO_PROPERTIES = ['diameter', 'neutral_buoyancy_salinity', 'density', 'specie']     # ODR_RADIO_*
+PLAST_STOKES, PLAST_HS = 1, 2     # include/odrift.h ODR_PLAST_*
 EGG_PROPERTIES = ['diameter', 'neutral_buoyancy_salinity', 'density', 'hatched']     # include/odrift.h ODR_EGG_*
 BERG_PROPERTIES = ['sail', 'draft', 'length', 'width', 'iceb_x_velocity', 'iceb_y_velocity']     # ODR_BERG_*
 SHIP_PROPERTIES = ['length', 'height', 'draft', 'beam', 'wind_drag_coeff', 'water_drag_coeff', 'orientation', 'ship_class']     # ODR_SHIP_*

@@ -1025,7 +1025,10 @@ __global__ __launch_bounds__(BLOCK, ODR_STEP_WAVES(PROJ)) void k_advect_grid(con
 // -------------------------------------------------------------------- reductions
 // red[] slots
 enum { R_NACT = 0, R_LONMIN, R_LONMAX, R_LATMIN, R_LATMAX, R_ZMIN, R_ZMAX, R_DMAX, R_STOKESMAX,
-       R_WSPEEDMAX, R_WDFMAX, R_NSURF, R_HSMAX, R_TPMAX, R_RELWSPEEDMAX, R_MLDMAX, R_N };
+       R_WSPEEDMAX, R_WDFMAX, R_NSURF, R_HSMAX, R_TPMAX, R_RELWSPEEDMAX, R_MLDMAX,
+       // behind the sixteen slots the reduce entry points hand out: the plain maxima of the two Stokes components (environment.py:
+       // 847-851 asks whether BOTH are 0, which the maximum of their sum does not tell; odr_reduce_wave_maxima)
+       R_SXMAX, R_SYMAX, R_N };
 
 __device__ __forceinline__ void atomic_max_d(double *addr, double v) {
   unsigned long long *a = (unsigned long long *)addr, old = *a, assumed;
@@ -1470,7 +1473,10 @@ __global__ __launch_bounds__(BLOCK) void k_reduce(PView p, double wind_drift_dep
         v[R_ZMIN] = fmax(v[R_ZMIN], -z[u]); v[R_ZMAX] = fmax(v[R_ZMAX], z[u]);
       }
       if (has_hd) v[R_DMAX] = fmax(v[R_DMAX], (double)hd[u]);
-      if (has_st) v[R_STOKESMAX] = fmax(v[R_STOKESMAX], (double)__fadd_rn(sx[u], sy[u]));
+      if (has_st) {
+        v[R_STOKESMAX] = fmax(v[R_STOKESMAX], (double)__fadd_rn(sx[u], sy[u]));
+        v[R_SXMAX] = fmax(v[R_SXMAX], (double)sx[u]); v[R_SYMAX] = fmax(v[R_SYMAX], (double)sy[u]);
+      }
       if (has_hs) v[R_HSMAX] = fmax(v[R_HSMAX], (double)hs[u]);
       if (has_tp) v[R_TPMAX] = fmax(v[R_TPMAX], (double)tp[u]);
       if (has_mld) v[R_MLDMAX] = fmax(v[R_MLDMAX], (double)mld[u]);

@@ -1881,7 +1881,9 @@ int odr_reduce_local(odr_ctx *c, odr_particles *p, double wdd, int relwind, doub
 }
 int odr_reduce_install(odr_ctx *c, odr_particles *p, const double *in16) {
   REQUIRE(in16, "in16 NULL");
-  H2D(c->red, in16, sizeof(double) * R_N);
+  double r[R_N];      // (the slots behind the sixteen are not combined over the ranks: odr_reduce_wave_maxima refuses an installed row)
+  for (int k = 0; k < R_N; ++k) r[k] = k < 16 ? in16[k] : -__builtin_inf();
+  H2D(c->red, r, sizeof r);
   HIPCHK(hipStreamSynchronize(c->stream));   // in16 is pageable
   c->red_owner = p; c->red_epoch = p->epoch; c->red_extents = true; c->red_partial = false;
   c->red_pinned = 1;      // until odr_reduce_unpin: the calls in between do not reduce again

@@ -1171,6 +1171,37 @@ class Particles:
         sea_water_temperature / sea_water_salinity and the two property slots (egg diameter, salinity of neutral buoyancy)."""
         check(self.lib.odr_egg_terminal_velocity(self.ctx.h, self.h, int(diameter_slot), int(salinity_slot)))
 
+    def stokes_from_wind(self, stokes_coeff=None, hs_coeff=None):
+        """drift:use_tabularised_stokes_drift (environment.py:844-863): the Stokes drift (stokes_coeff given: the 1 .. 7
+        coefficients of the drift factor, leading one first) and / or the significant wave height (hs_coeff given: its two) of
+        every active element from the sampled wind, in ONE launch (odr_stokes_from_wind)."""
+        flags = (_abi.PLAST_STOKES if stokes_coeff is not None else 0) | (_abi.PLAST_HS if hs_coeff is not None else 0)
+        if not flags:
+            raise ValueError('neither the coefficients of the drift factor nor those of the wave height were given')
+        (sa, ps), (ha, ph) = _d(stokes_coeff), _d(hs_coeff)
+        if ha is not None and ha.shape != (2,):
+            raise ValueError('the wave height has two coefficients, not %s' % (ha.shape,))
+        if sa is not None and (sa.ndim != 1 or not 1 <= len(sa) <= 7):
+            raise ValueError('the drift factor has 1 .. 7 coefficients, not %s' % (sa.shape,))
+        check(self.lib.odr_stokes_from_wind(self.ctx.h, self.h, ps, 0 if sa is None else len(sa), ph, flags))
+
+    def wave_maxima(self):
+        """(max Stokes x, max Stokes y, max wave height) over the active elements: the plain maxima environment.py:847-858 asks
+        about (-inf: not sampled / no active element), from the movers' reduction (odr_reduce_wave_maxima)."""
+        out = np.empty(3)
+        check(self.lib.odr_reduce_wave_maxima(self.ctx.h, self.h, out.ctypes.data_as(_dp)))
+        return tuple(float(v) for v in out)
+
+    def plast_depth(self, step=0, draws=None):
+        """PlastDrift.update_particle_depth, 'analytical' (plastdrift.py:102-107): z = -(K / terminal_velocity) E for every active
+        element.  draws: np.random.standard_exponential(n) in the reference's element order (parity mode); None: the device
+        generator.  ValueError -- and no z changed -- when K / terminal_velocity is negative for some element, as NumPy raises."""
+        if draws is not None:
+            a, pa = _d(self._host_order(draws), len(self))
+            check(self.lib.odr_plast_depth(self.ctx.h, self.h, _abi.RNG_HOST, pa, step))
+        else:
+            check(self.lib.odr_plast_depth(self.ctx.h, self.h, _abi.RNG_DEVICE, None, step))
+
     def larval_update(self, dt, stage_fraction_slot=2, hatched_slot=3, weight_slot=5, length_slot=4):
         """LarvalFish.update_fish_larvae (larvalfish.py:200-231, with fish_growth :185-198) over the active set: eggs add to
         stage_fraction and hatch at >= 1, larvae grow in weight and get their length from it.  `hatched` is uint8 in the

@@ -68,6 +68,7 @@ class OpenDriftSimulation(Configurable):
                                  "elements of one process")
         self._ctx, self._device, self._seed = None, device, seed or 0   # the device context is created on first use
         self.rng = rng                       # 'device' (Philox by ID) | 'numpy' (np.random in reference call order)
+        self._waves_on = None                # run(): drift:use_tabularised_stokes_drift acts in this run (_identically_zero)
         # arithmetic of the Runge-Kutta stage evaluations (odr_ctx_set_stage_math): 'exact' reproduces every float32 rounding
         # point of the reference inside a stage (1e-10 deg per step vs the oracle), 'fast' takes the stage step and the stage
         # sample without them (<= 2e-9 deg per step).  Runs that replay the reference's np.random stream are parity runs: exact.
@@ -967,7 +968,39 @@ class OpenDriftSimulation(Configurable):
             self.P.env_sample(names, t)
             self._sampled = names
             self._sample_host_readers(names)
+        self._parameterise_waves(names)
         self._add_uncertainty(names, current=True)
+
+    def _waves_from_wind(self):
+        """drift:use_tabularised_stokes_drift is a key of this model, is True, and the wind is sampled (environment.py:844-846)."""
+        return self._config.get('drift:use_tabularised_stokes_drift', {}).get('value') is True and 'x_wind' in self.required_variables
+
+    def _parameterise_waves(self, names):
+        """environment.py:844-863, at the reference's place: behind the fallbacks and the Kelvin normalisation of the sample, in
+        front of the uncertainties.  The Stokes drift is derived from the wind when it is not sampled or when the plain maxima of
+        BOTH components are 0 (an all-negative x with y == 0 is left alone, as there); the wave height when its maximum is 0.  A
+        variable no reader delivers and whose fallback is 0 is known to be 0 without looking; else the maxima come from the
+        movers' reduction (one read-back).  A launch of its own behind the sampling launch (odr_stokes_from_wind)."""
+        if not self._waves_from_wind() or 'x_wind' not in names or 'y_wind' not in names or self.num_elements_active() == 0:
+            return
+        sx, sy = 'sea_surface_wave_stokes_drift_x_velocity', 'sea_surface_wave_stokes_drift_y_velocity'
+        hs = 'sea_surface_wave_significant_height'
+        def zero(v):      # (a reader of any kind -- on the device, evaluated on the host, a constant -- means: look)
+            return not [n for n in self.priority_list.get(v, []) if n in self.readers] and self._no_reader_and_zero_fallback(v)
+        stokes = sx not in names or (zero(sx) and zero(sy)) or None       # None: look
+        height = hs in names and (zero(hs) or None)
+        if stokes is None or height is None:
+            mx, my, mh = self.P.wave_maxima()
+            stokes = (mx == 0 and my == 0) if stokes is None else stokes
+            height = (mh == 0) if height is None else height
+        if stokes or height:
+            if self._stokes_tables is None:      # (called outside a run: prepare_run() has not looked for them yet)
+                from . import stokes_tables as st
+                self._stokes_tables = st.find(self._stokes_tables_argument)[0]
+                if self._stokes_tables is None:
+                    raise FileNotFoundError(st.MISSING)
+            t = self._stokes_tables[self.get_config('drift:tabularised_stokes_drift_fetch')]
+            self.P.stokes_from_wind(t['stokes'] if stokes else None, t['hs'] if height else None)
 
     def _profile_level_cut(self):
         """drift:truncate_ocean_model_below_m with diffusivity profiles from a reader (environment.py:554-566): the reference asks
@@ -1266,7 +1299,16 @@ class OpenDriftSimulation(Configurable):
                            self.get_config('drift:relative_wind'), factor)
 
     def _identically_zero(self, v):
-        """No reader delivers `v` and its fallback is 0: the variable is 0 for every element without looking."""
+        """No reader delivers `v` and its fallback is 0: the variable is 0 for every element without looking -- unless it is one
+        that get_environment derives from the wind (_parameterise_waves)."""
+        on = getattr(self, '_waves_on', None)      # (decided once for the steps of a run: this is asked several times per step)
+        if (self._waves_from_wind() if on is None else on) and v in (
+                'sea_surface_wave_stokes_drift_x_velocity', 'sea_surface_wave_stokes_drift_y_velocity',
+                'sea_surface_wave_significant_height'):
+            return False
+        return self._no_reader_and_zero_fallback(v)
+
+    def _no_reader_and_zero_fallback(self, v):
         live = [n for n in self.priority_list.get(v, []) if n in self.readers and self.readers[n].sid is not None]
         return not live and v in self.required_variables and self.get_config('environment:fallback:%s' % v) == 0
 
@@ -1380,6 +1422,7 @@ class OpenDriftSimulation(Configurable):
     def _one_launch_lanes_open(self):
         """What the two one-launch lanes of run() ask alike: the stock loop body, and nothing in it that a launch cannot honour."""
         return (not os.environ.get('ODR_RUN_UNFUSED') and
+                not self._waves_from_wind() and      # (a launch of its own between the sample and the uncertainties)
                 all(getattr(type(self), m) is getattr(OpenDriftSimulation, m) for m in (
                     'get_environment', 'interact_with_coastline', 'interact_with_seafloor', 'deactivate_outside',
                     'deactivate_elements')) and
@@ -1575,6 +1618,10 @@ class OpenDriftSimulation(Configurable):
         if self._world > 1 and any(getattr(r, 'device_kind', None) == 'shape' for r, _ in self._readers_host.values()):
             raise NotImplementedError('a ShapeReader in a sharded run: the model samples it outside the launch a sharded step is '
                                       '(DESIGN.md section 8l)')
+        if self._world > 1 and self._waves_from_wind():
+            raise NotImplementedError('drift:use_tabularised_stokes_drift in a sharded run: whether the Stokes drift and the wave '
+                                      'height are derived from the wind is decided over the elements of all ranks and would need a '
+                                      'collective (DESIGN.md section 7j)')
         self._check_reader_expressions()
         steps, out_every = self._time_arguments(time_step, steps, time_step_output, duration, end_time)
         # skip_if conditionals of required_variables (:1899-1906)
@@ -1584,6 +1631,7 @@ class OpenDriftSimulation(Configurable):
                 cur = self.get_config(key)
                 if {'is': cur is val, '==': cur == val, '!=': cur != val}[op]:
                     self.required_variables.pop(vn)
+        self._waves_on = self._waves_from_wind()      # (behind the skip_if conditionals: whether the wind is sampled is settled)
         self.time = self.start_time
         self._set_extents(steps)
         self._all_at_start = bool((self._sched['t_epoch'] == _epoch(self.start_time)).all())
@@ -1696,10 +1744,12 @@ class OpenDriftSimulation(Configurable):
             except Exception as e:
                 self.ctx.set_position_class(False)
                 if stop_on_error or self.steps_calculation <= 1:
+                    self._waves_on = None
                     raise
                 logger.warning('The simulation stopped before requested end time was reached: %s', e)
                 break
         self.ctx.set_position_class(False)
+        self._waves_on = None      # (outside run() the configuration is asked again)
         self.ctx.sync()
         self.timing = self._run_timing(t_start, t_steady, time.perf_counter(), clock.phases)
         for b in self.readers.values():      # no read of the user's Reader is in flight when run() returns
@@ -2361,8 +2411,10 @@ class OceanDrift(OpenDriftSimulation):
         'sea_surface_wind_wave_significant_height': {'fallback': 0, 'skip_if': ['drift:stokes_drift_profile', '!=', 'windsea_swell']},
     }
 
-    def __init__(self, *args, **kwargs):
+    def __init__(self, *args, stokes_tables=None, **kwargs):
         super().__init__(*args, **kwargs)
+        self._stokes_tables_argument = stokes_tables     # drift:use_tabularised_stokes_drift: resolved by prepare_run (stokes_tables.py)
+        self._stokes_tables = None
         self._add_config({   # oceandrift.py:118-183
             'drift:vertical_advection': {'type': 'bool', 'default': True, 'level': CONFIG_LEVEL_BASIC, 'description': ''},
             'drift:water_column_stretching': {'type': 'bool', 'default': False, 'level': CONFIG_LEVEL_ADVANCED, 'description':
@@ -2390,6 +2442,12 @@ class OceanDrift(OpenDriftSimulation):
             'drift:stokes_drift_profile': {'type': 'enum', 'default': 'Phillips',
                                            'enum': ['monochromatic', 'exponential', 'Phillips', 'windsea_swell'],
                                            'level': CONFIG_LEVEL_ADVANCED, 'description': ''},
+            'drift:use_tabularised_stokes_drift': {'type': 'bool', 'default': False, 'level': CONFIG_LEVEL_ADVANCED, 'description':
+                                                   'Stokes drift and wave height that no reader delivers are derived from the wind '
+                                                   'by the fitted tables of drift:tabularised_stokes_drift_fetch'},
+            'drift:tabularised_stokes_drift_fetch': {'type': 'enum', 'enum': ['5000', '25000', '50000'], 'default': '25000',
+                                                     'level': CONFIG_LEVEL_ADVANCED, 'description':
+                                                     'Fetch length [m] of the tabularised Stokes drift'},
             'general:seafloor_action': {'type': 'enum', 'default': 'lift_to_seafloor',
                                         'enum': ['none', 'lift_to_seafloor', 'deactivate', 'previous'],
                                         'level': CONFIG_LEVEL_ADVANCED, 'description': ''},
@@ -2399,6 +2457,31 @@ class OceanDrift(OpenDriftSimulation):
                               'description': 'Elements are seeded at seafloor, and seeding depth (z) is neglected.'},
         })
         self._set_config_default('drift:max_speed', 2)
+
+    def _clone_arguments(self):
+        return dict(super()._clone_arguments(), stokes_tables=self._stokes_tables_argument)
+
+    def set_stokes_tables(self, stokes_tables):
+        """The coefficients of drift:use_tabularised_stokes_drift as a dict or the path of a JSON / npz file (stokes_tables.py);
+        checked here, used from the next run on."""
+        from . import stokes_tables as st
+        self._stokes_tables = st.load(stokes_tables)
+        self._stokes_tables_argument = stokes_tables
+
+    def prepare_run(self):
+        """drift:use_tabularised_stokes_drift: the coefficients are found now -- argument, ODR_STOKES_TABLES, an installed opendrift
+        -- or the run ends here, saying so."""
+        if self._waves_from_wind():
+            from . import stokes_tables as st
+            if self._stokes_tables is None or self._stokes_tables_argument is None:
+                self._stokes_tables, where = st.find(self._stokes_tables_argument)
+                if self._stokes_tables is None:
+                    raise FileNotFoundError(st.MISSING)
+                logger.debug('Coefficients of the tabularised Stokes drift from %s', where)
+            fetch = self.get_config('drift:tabularised_stokes_drift_fetch')
+            if fetch not in self._stokes_tables:
+                raise KeyError('the Stokes drift tables hold no fetch %r (they hold %s)' % (fetch, sorted(self._stokes_tables)))
+        super().prepare_run()
 
     @classmethod
     def _fuses_vertical_advection(cls):
