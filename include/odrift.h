@@ -1009,7 +1009,7 @@ int odr_history_minmax(odr_ctx *ctx, odr_history *h, int32_t var_index, double *
 int odr_density_map(odr_ctx *ctx, int64_t n_trajectories, int32_t n_times, const float *lon, const float *lat, const float *z,
                     const float *status, const float *weight, int32_t stranded_code, int32_t n_lon_edges, const double *lon_edges,
                     int32_t n_lat_edges, const double *lat_edges, double *H, double *H_submerged, double *H_stranded);
-/* device time [ms] of the kernel launches of this process's last odr_density_map, summed over its slabs (tools/bench_density.py) */
+/* device time [ms] of the kernel launches of this context's last odr_density_map, summed over its slabs (tools/bench_density.py) */
 int odr_density_last_kernel_ms(odr_ctx *ctx, float *ms);
 
 /* ---------------------------------------------------------------- projected density and concentration maps
@@ -1047,7 +1047,7 @@ int odr_density_map_proj(odr_ctx *ctx, int64_t n_trajectories, int32_t n_times, 
 int odr_species_layer_map(odr_ctx *ctx, int64_t n_trajectories, int32_t n_times, const float *lon, const float *lat, const float *z,
                           const float *specie, const odr_proj_desc *proj, int32_t n_x_edges, const double *x_edges, int32_t n_y_edges,
                           const double *y_edges, int32_t n_z, const double *z_array, int32_t n_species, double *H);
-/* device time [ms] of the kernel launches of this process's last odr_density_map_proj or odr_species_layer_map, summed over its
+/* device time [ms] of the kernel launches of this context's last odr_density_map_proj or odr_species_layer_map, summed over its
  * slabs (tools/bench_concentration.py) */
 int odr_conc_last_kernel_ms(odr_ctx *ctx, float *ms);
 /* odr_proj_extent: extent4 = (min x, max x, min y, max y) of (x, y) = proj(lon, lat) over the n positions whose projected
@@ -1085,7 +1085,7 @@ int odr_box_smooth(odr_ctx *ctx, int64_t n_planes, int32_t n0, int32_t n1, int32
  * NULL pointer other than displacement, ODR_PROJ_CURVILINEAR or an unknown kind -- checked before anything is launched. */
 int odr_ftle_map(odr_ctx *ctx, const odr_proj_desc *proj, int32_t nx, int32_t ny, const double *xs, const double *ys, double delta,
                  double duration_seconds, const float *lon, const float *lat, float *ftle, double *displacement);
-/* device time [ms] of the two kernel launches of this process's last odr_ftle_map that launched (tools/bench_ftle.py) */
+/* device time [ms] of the two kernel launches of this context's last odr_ftle_map that launched (tools/bench_ftle.py) */
 int odr_ftle_last_kernel_ms(odr_ctx *ctx, float *ms);
 
 /* ---------------------------------------------------------------- inverse geodesics, trajectory lengths
@@ -1109,7 +1109,7 @@ int odr_geod_inverse(odr_ctx *ctx, int64_t n, const double *lon1, const double *
  * anything is launched. */
 int odr_trajectory_lengths(odr_ctx *ctx, int64_t n_trajectories, int32_t n_times, const float *lon, const float *lat,
                            double dt_seconds, double *total_length, double *distances, double *speeds);
-/* device time [ms] of the kernel launches of this process's last odr_trajectory_lengths, summed over its slabs
+/* device time [ms] of the kernel launches of this context's last odr_trajectory_lengths, summed over its slabs
  * (tools/bench_trajectory_lengths.py) */
 int odr_trajectory_lengths_last_kernel_ms(odr_ctx *ctx, float *ms);
 
@@ -1140,7 +1140,7 @@ int odr_points_in_polygon(odr_ctx *ctx, int64_t n, const double *x, const double
  * before anything is launched. */
 int odr_polygon_points(odr_ctx *ctx, int32_t m, const double *lons, const double *lats, int64_t number, double *out_lon,
                        double *out_lat, int64_t *n_inside, int32_t *nx, int32_t *ny);
-/* device time [ms] of the kernel launches of this process's last odr_polygon_points (tools/bench_seed.py); 0 when it launched none */
+/* device time [ms] of the kernel launches of this context's last odr_polygon_points (tools/bench_seed.py); 0 when it launched none */
 int odr_polygon_points_last_kernel_ms(odr_ctx *ctx, float *ms);
 
 /* ---------------------------------------------------------------- unstructured (triangular-mesh) readers
@@ -1179,7 +1179,7 @@ int odr_umesh_sample(odr_ctx *ctx, odr_particles *p, odr_umesh *mesh, int32_t sl
  * that is not finite.  A point far outside the box of the mesh is answered exactly too, but visits a large share of the tree
  * (every point is about as far away); odr_umesh_sample never searches for one.  Synchronous. */
 int odr_umesh_nearest(odr_ctx *ctx, odr_umesh *mesh, int on_faces, int64_t n, const double *x, const double *y, int32_t *idx_out);
-/* device time [ms] of the launches of this process's last odr_umesh_nearest, or of the launch of its last odr_umesh_sample if
+/* device time [ms] of the launches of this context's last odr_umesh_nearest, or of the launch of its last odr_umesh_sample if
  * that came later (waits for it) */
 int odr_umesh_last_kernel_ms(odr_ctx *ctx, float *ms);
 
@@ -1209,7 +1209,7 @@ int odr_shape_contains(odr_ctx *ctx, odr_shape *shape, int64_t n, const double *
 /* stats[0 .. 7]: cells, list entries, longest list, mean list of the cells that have one, times the grid's origin was shifted to
  * keep its lines off the vertices, bytes of the index on the device, nx, ny */
 int odr_shape_stats(odr_ctx *ctx, odr_shape *shape, double *stats);
-/* device time [ms] of the launches of this process's last odr_shape_contains, or of the launch of its last odr_shape_sample if
+/* device time [ms] of the launches of this context's last odr_shape_contains, or of the launch of its last odr_shape_sample if
  * that came later (waits for it) */
 int odr_shape_last_kernel_ms(odr_ctx *ctx, float *ms);
 
@@ -1245,7 +1245,7 @@ int odr_combined_destroy(odr_ctx *ctx, odr_combined *combined);
  * ODR_ERR_INVALID for a leaf with ensemble members.  Enqueued on the context's stream. */
 int odr_combined_sample(odr_ctx *ctx, odr_particles *p, odr_combined *combined, int32_t nvars, const int32_t *var_ids, const uint8_t *first,
                         double t_epoch, int32_t n_uniform, const double *uniform_values);
-/* device time [ms] of the two launches of this process's last odr_combined_sample (waits for them) */
+/* device time [ms] of the two launches of this context's last odr_combined_sample (waits for them) */
 int odr_combined_last_kernel_ms(odr_ctx *ctx, float *ms);
 
 /* ---------------------------------------------------------------- ROMS sigma grid

@@ -6,29 +6,11 @@
 struct odr_combined {
   int n_ops;
   CombOp op[COMB_MAXOPS];
-  int *partial;      // device, [MAXSRC]: k_combined_front -> k_combined_sample
+  DevScope bufs;
+  int *partial;      // device (in bufs), [MAXSRC]: k_combined_front -> k_combined_sample
 };
 
 namespace {
-
-// odr_combined_last_kernel_ms: the launch of odr_combined_sample is bracketed by two events that are read when the time is asked for
-float g_kernel_ms = 0.f;
-hipEvent_t g_ev[2] = {nullptr, nullptr};
-bool g_pending = false;
-int g_ev_device = -1;      // the device the two events belong to
-
-int ensure_events(const odr_ctx *c) {
-  if (g_ev_device != c->device) {
-    for (hipEvent_t &e : g_ev) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-    g_pending = false;
-    g_ev_device = c->device;
-  }
-  for (hipEvent_t &e : g_ev) if (!e) HIPCHK(hipEventCreate(&e));
-  return 0;
-}
 
 // what the kernel would read of source `sid` for variable `var` at time t is there
 int leaf_ready(const odr_ctx *c, int sid, int var, double t) {
@@ -64,7 +46,7 @@ int odr_combined_create(odr_ctx *c, int32_t n_ops, const odr_combine_op *ops, od
     delete m;
     return fail(ODR_ERR_INVALID, "odr_combined_create: %s", why);
   }
-  if (hipSetDevice(c->device) != hipSuccess || hipMalloc((void **)&m->partial, sizeof(int) * MAXSRC) != hipSuccess) {
+  if (hipSetDevice(c->device) != hipSuccess || m->bufs.alloc((void **)&m->partial, sizeof(int) * MAXSRC)) {
     delete m;
     return fail(ODR_ERR_HIP, "odr_combined_create: hipMalloc of the coverage flags");
   }
@@ -76,7 +58,6 @@ int odr_combined_destroy(odr_ctx *c, odr_combined *m) {
   REQUIRE(c, "NULL argument");
   if (!m) return 0;
   HIPCHK(hipStreamSynchronize(c->stream));      // a launch may still read the flags
-  (void)hipFree(m->partial);
   delete m;
   return 0;
 }
@@ -124,33 +105,26 @@ int odr_combined_sample(odr_ctx *c, odr_particles *p, odr_combined *m, int32_t n
   }
   if (p->n == 0) return 0;
   if (int rc = flush_world(c)) return rc;
-  if (int rc = ensure_events(c)) return rc;
   // the positions in the leaves' own coordinates: [source leaf in program order][x, y][n] doubles in the set's scratch memory
   int n_leaves = 0;
   for (int k = 0; k < m->n_ops; ++k) n_leaves += m->op[k].kind == COMB_SOURCE;
   double *xy = nullptr;
   if (int rc = scratch(c, p, sizeof(double) * 2 * (size_t)std::max(n_leaves, 1) * (size_t)p->n, (void **)&xy)) return rc;
   HIPCHK(hipMemsetAsync(m->partial, 0, sizeof(int) * MAXSRC, c->stream));
-  HIPCHK(hipEventRecord(g_ev[0], c->stream));
+  KernelClock &clock = c->clock[CLOCK_COMBINED];
+  clock.reset();
+  if (int rc = clock.start(c->stream)) return rc;
   hipLaunchKernelGGL(k_combined_front, dim3(nblk(p->n)), dim3(BLOCK), 0, c->stream, c->dw, L, p->n, (const double *)p->d64[0],
                      (const double *)p->d64[1], (const double *)p->d64[2], t_epoch, m->partial, xy);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_combined_sample, dim3(nblk(p->n)), dim3(BLOCK), 0, c->stream, c->dw, L, p->n, (const double *)p->d64[0],
                      (const double *)p->d64[1], (const double *)p->d64[2], t_epoch, (const int *)m->partial, (const double *)xy);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(g_ev[1], c->stream));
-  g_pending = true;
-  return 0;
+  return clock.stop(c->stream);
 }
 
-// Device time [ms] of the two launches of this process's last odr_combined_sample (waits for them)
+// Device time [ms] of the two launches of this context's last odr_combined_sample (waits for them)
 int odr_combined_last_kernel_ms(odr_ctx *c, float *ms) {
   REQUIRE(c && ms, "NULL argument");
-  if (g_pending) {
-    HIPCHK(hipEventSynchronize(g_ev[1]));
-    HIPCHK(hipEventElapsedTime(&g_kernel_ms, g_ev[0], g_ev[1]));
-    g_pending = false;
-  }
-  *ms = g_kernel_ms;
-  return 0;
+  return c->clock[CLOCK_COMBINED].read(ms);
 }

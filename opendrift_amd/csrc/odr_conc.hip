@@ -13,25 +13,6 @@ constexpr int CONC_EXTENT_BLOCKS = 1024;               // partial records of one
 constexpr long long CONC_GRID_CHUNK = 1ll << 20;       // grid points of one k_conc_grid launch
 constexpr size_t CONC_BOX_CELLS = 1u << 24;            // cells of one odr_box_smooth pass, unless one plane is larger
 
-float g_kernel_ms = 0.f;      // odr_conc_last_kernel_ms
-
-struct ConcBuffers {      // released on every way out
-  void *hist = nullptr, *slab = nullptr, *aux = nullptr, *aux2 = nullptr;
-  double *edges = nullptr;
-  std::vector<hipEvent_t> events;      // before and after every launch
-  ~ConcBuffers() {
-    for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
-    for (void *p : {hist, slab, aux, aux2, (void *)edges}) if (p) (void)hipFree(p);
-  }
-};
-
-bool on_device(const void *ptr) {
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, ptr) == hipSuccess) return at.type == hipMemoryTypeDevice;
-  (void)hipGetLastError();      // plain pageable memory: not an error
-  return false;
-}
-
 int increasing(const double *e, int n, const char *what) {
   REQUIRE(n >= 2, "%s: %d values, fewer than two", what, n);
   for (int k = 0; k < n; ++k) REQUIRE(std::isfinite(e[k]), "%s[%d] is not finite", what, k);
@@ -52,33 +33,16 @@ int proj_ok(const odr_proj_desc *proj) {
   }
 }
 
-int mark(odr_ctx *c, ConcBuffers &B) {
-  hipEvent_t ev;
-  HIPCHK(hipEventCreate(&ev));
-  B.events.push_back(ev);
-  HIPCHK(hipEventRecord(ev, c->stream));
-  return 0;
-}
-
-int sum_marks(odr_ctx *c, ConcBuffers &B, float &total) {
-  HIPCHK(hipStreamSynchronize(c->stream));
-  total = 0.f;
-  for (size_t k = 0; k + 1 < B.events.size(); k += 2) {
-    float ms;
-    HIPCHK(hipEventElapsedTime(&ms, B.events[k], B.events[k + 1]));
-    total += ms;
-  }
-  return 0;
-}
-
 // [trajectory][time] float32 inputs, each in host or device memory (NULL: absent), handed to `launch` slab by slab of whole
 // trajectories: launch(ptr, entries) with device pointers.  The host arrays share a device buffer within the byte budget.
+// clock: starts a measurement that brackets every slab's launches (NULL: they are not timed).
 template <int NIN, class F>
-int for_slabs(odr_ctx *c, ConcBuffers &B, const float *const (&in)[NIN], long long n_trajectories, long long n_times, F &&launch) {
+int for_slabs(odr_ctx *c, DevScope &B, KernelClock *clock, const float *const (&in)[NIN], long long n_trajectories, long long n_times,
+              F &&launch) {
   bool dev[NIN];
   int n_host = 0;
   for (int k = 0; k < NIN; ++k) {
-    dev[k] = in[k] ? on_device(in[k]) : true;
+    dev[k] = in[k] ? odr_i_on_device(in[k]) : true;
     if (!dev[k]) ++n_host;
   }
   long long slab_traj = std::max<long long>(1, CONC_LAUNCH_ENTRIES / n_times);
@@ -94,7 +58,9 @@ int for_slabs(odr_ctx *c, ConcBuffers &B, const float *const (&in)[NIN], long lo
   }
   slab_traj = std::min<long long>(slab_traj, n_trajectories);
   const size_t slab_floats = (size_t)slab_traj * (size_t)n_times;
-  if (n_host) HIPCHK(hipMalloc(&B.slab, sizeof(float) * slab_floats * (size_t)n_host));
+  float *slab = nullptr;
+  if (n_host) if (int rc = B.alloc((void **)&slab, sizeof(float) * slab_floats * (size_t)n_host)) return rc;
+  if (clock) clock->reset();
   for (long long t0 = 0; t0 < n_trajectories; t0 += slab_traj) {
     const long long nt = std::min(slab_traj, n_trajectories - t0);
     const size_t off = (size_t)t0 * (size_t)n_times, count = (size_t)nt * (size_t)n_times;
@@ -103,15 +69,14 @@ int for_slabs(odr_ctx *c, ConcBuffers &B, const float *const (&in)[NIN], long lo
     for (int k = 0; k < NIN; ++k) {
       if (!in[k]) { ptr[k] = nullptr; continue; }
       if (dev[k]) { ptr[k] = in[k] + off; continue; }
-      float *d = (float *)B.slab + slab_floats * (size_t)h++;
+      float *d = slab + slab_floats * (size_t)h++;
       H2D(d, in[k] + off, sizeof(float) * count);      // waits for the stream: the launch of the slab before has read `d`
       ptr[k] = d;
     }
-    int rc = mark(c, B);
-    if (rc) return rc;
-    if ((rc = launch(ptr, (long long)count))) return rc;
+    if (clock) if (int rc = clock->start(c->stream)) return rc;
+    if (int rc = launch(ptr, (long long)count)) return rc;
     HIPCHK(hipGetLastError());
-    if ((rc = mark(c, B))) return rc;
+    if (clock) if (int rc = clock->stop(c->stream)) return rc;
   }
   return 0;
 }
@@ -141,12 +106,13 @@ int fetch_hist(odr_ctx *c, const void *hist, size_t cells_each, int n_out, doubl
 }
 
 // edges (and z bounds) on the device, the axes of the bin search
-int upload_axes(odr_ctx *c, ConcBuffers &B, ConcArgs &A, int nx, const double *xe, int ny, const double *ye, int nz, const double *zb) {
-  HIPCHK(hipMalloc((void **)&B.edges, sizeof(double) * (size_t)(nx + ny + nz)));
-  H2D(B.edges, xe, sizeof(double) * (size_t)nx);
-  H2D(B.edges + nx, ye, sizeof(double) * (size_t)ny);
-  if (nz) H2D(B.edges + nx + ny, zb, sizeof(double) * (size_t)nz);
-  A.x_edges = B.edges; A.y_edges = B.edges + nx; A.z_bounds = nz ? B.edges + nx + ny : nullptr;
+int upload_axes(odr_ctx *c, DevScope &B, ConcArgs &A, int nx, const double *xe, int ny, const double *ye, int nz, const double *zb) {
+  double *edges;
+  if (int rc = B.alloc((void **)&edges, sizeof(double) * (size_t)(nx + ny + nz))) return rc;
+  H2D(edges, xe, sizeof(double) * (size_t)nx);
+  H2D(edges + nx, ye, sizeof(double) * (size_t)ny);
+  if (nz) H2D(edges + nx + ny, zb, sizeof(double) * (size_t)nz);
+  A.x_edges = edges; A.y_edges = edges + nx; A.z_bounds = nz ? edges + nx + ny : nullptr;
   A.ax = density_axis(xe, nx); A.ay = density_axis(ye, ny);
   return 0;
 }
@@ -183,9 +149,10 @@ int odr_density_map_proj(odr_ctx *c, int64_t n_trajectories, int32_t n_times, co
   }
 
   HIPCHK(hipSetDevice(c->device));
-  ConcBuffers B;
-  HIPCHK(hipMalloc(&B.hist, 3 * cells * cell_bytes));      // (H_stranded's is written by nothing when there is no such category)
-  HIPCHK(hipMemsetAsync(B.hist, 0, 3 * cells * cell_bytes, c->stream));
+  DevScope B;      // released on every way out
+  void *hist;
+  if (int rc = B.alloc(&hist, 3 * cells * cell_bytes)) return rc;      // (H_stranded's is written by nothing when there is no such category)
+  HIPCHK(hipMemsetAsync(hist, 0, 3 * cells * cell_bytes, c->stream));
   ConcArgs A;
   memset(&A, 0, sizeof A);
   if (int rc = upload_axes(c, B, A, n_x_edges, x_edges, n_y_edges, y_edges, 0, nullptr)) return rc;
@@ -194,16 +161,16 @@ int odr_density_map_proj(odr_ctx *c, int64_t n_trajectories, int32_t n_times, co
   odr_i_proj_init(P, proj);
   const bool lds = n_x_edges + n_y_edges <= DENSITY_LDS_EDGES;
   const float *const in[5] = {lon, lat, z, status, weight};
-  int rc = for_slabs(c, B, in, n_trajectories, n_times, [&](const float *const *ptr, long long count) {
+  int rc = for_slabs(c, B, &c->clock[CLOCK_CONC], in, n_trajectories, n_times, [&](const float *const *ptr, long long count) {
     A.lon = ptr[0]; A.lat = ptr[1]; A.z = ptr[2]; A.aux = ptr[3]; A.weight = ptr[4];
     A.n = count;
-    if (weighted) launch_bin<CONC_MASKS_W, double>(c, A, P, lds, (double *)B.hist);
-    else launch_bin<CONC_MASKS, unsigned>(c, A, P, lds, (unsigned *)B.hist);
+    if (weighted) launch_bin<CONC_MASKS_W, double>(c, A, P, lds, (double *)hist);
+    else launch_bin<CONC_MASKS, unsigned>(c, A, P, lds, (unsigned *)hist);
     return 0;
   });
   if (rc) return rc;
-  if ((rc = sum_marks(c, B, g_kernel_ms))) return rc;
-  if ((rc = fetch_hist(c, B.hist, cells, nh, out, weighted))) return rc;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if ((rc = fetch_hist(c, hist, cells, nh, out, weighted))) return rc;
   if (nh == 2 && H_stranded) std::fill(H_stranded, H_stranded + cells, 0.0);
   return 0;
 }
@@ -233,9 +200,10 @@ int odr_species_layer_map(odr_ctx *c, int64_t n_trajectories, int32_t n_times, c
   if (n_trajectories == 0) { std::fill(H, H + cells, 0.0); return 0; }
 
   HIPCHK(hipSetDevice(c->device));
-  ConcBuffers B;
-  HIPCHK(hipMalloc(&B.hist, cells * sizeof(unsigned)));
-  HIPCHK(hipMemsetAsync(B.hist, 0, cells * sizeof(unsigned), c->stream));
+  DevScope B;
+  unsigned *hist;
+  if (int rc = B.alloc((void **)&hist, cells * sizeof(unsigned))) return rc;
+  HIPCHK(hipMemsetAsync(hist, 0, cells * sizeof(unsigned), c->stream));
   ConcArgs A;
   memset(&A, 0, sizeof A);
   if (int rc = upload_axes(c, B, A, n_x_edges, x_edges, n_y_edges, y_edges, n_z, z_array)) return rc;
@@ -244,22 +212,21 @@ int odr_species_layer_map(odr_ctx *c, int64_t n_trajectories, int32_t n_times, c
   odr_i_proj_init(P, proj);
   const bool lds = n_x_edges + n_y_edges <= DENSITY_LDS_EDGES;
   const float *const in[4] = {lon, lat, z, specie};
-  int rc = for_slabs(c, B, in, n_trajectories, n_times, [&](const float *const *ptr, long long count) {
+  int rc = for_slabs(c, B, &c->clock[CLOCK_CONC], in, n_trajectories, n_times, [&](const float *const *ptr, long long count) {
     A.lon = ptr[0]; A.lat = ptr[1]; A.z = ptr[2]; A.aux = ptr[3];
     A.n = count;
-    launch_bin<CONC_SPECIES, unsigned>(c, A, P, lds, (unsigned *)B.hist);
+    launch_bin<CONC_SPECIES, unsigned>(c, A, P, lds, hist);
     return 0;
   });
   if (rc) return rc;
-  if ((rc = sum_marks(c, B, g_kernel_ms))) return rc;
-  return fetch_hist(c, B.hist, cells, 1, &H, false);
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return fetch_hist(c, hist, cells, 1, &H, false);
 }
 
-// Device time of the k_conc_bin launches of this process's last odr_density_map_proj or odr_species_layer_map [ms], summed over slabs
+// Device time of the k_conc_bin launches of this context's last odr_density_map_proj or odr_species_layer_map [ms], summed over slabs
 int odr_conc_last_kernel_ms(odr_ctx *c, float *ms) {
   REQUIRE(c && ms, "NULL argument");
-  *ms = g_kernel_ms;
-  return 0;
+  return c->clock[CLOCK_CONC].read(ms);
 }
 
 // x.min(), x.max(), y.min(), y.max() of (x, y) = proj(lon, lat) over the finite projected positions.  Synchronous.
@@ -270,18 +237,19 @@ int odr_proj_extent(odr_ctx *c, const odr_proj_desc *proj, int64_t n, const floa
   double v[4] = {INFINITY, -INFINITY, INFINITY, -INFINITY};
   if (n > 0) {
     HIPCHK(hipSetDevice(c->device));
-    ConcBuffers B;
-    HIPCHK(hipMalloc(&B.aux, sizeof(double) * 4 * CONC_EXTENT_BLOCKS));
+    DevScope B;
+    double *d_part;
+    if (int rc = B.alloc((void **)&d_part, sizeof(double) * 4 * CONC_EXTENT_BLOCKS)) return rc;
     DevProj P;
     odr_i_proj_init(P, proj);
     std::vector<double> part(4 * CONC_EXTENT_BLOCKS);
     const float *const in[2] = {lon, lat};
-    int rc = for_slabs(c, B, in, n, 1, [&](const float *const *ptr, long long count) {
+    int rc = for_slabs(c, B, nullptr, in, n, 1, [&](const float *const *ptr, long long count) {
       const unsigned blocks = std::min<unsigned>(nblk(count), CONC_EXTENT_BLOCKS);
       hipLaunchKernelGGL(k_conc_extent, dim3(blocks), dim3(BLOCK), sizeof(double) * 4 * (BLOCK / 64), c->stream, P, ptr[0], ptr[1], count,
-                         (double *)B.aux);
+                         d_part);
       HIPCHK(hipGetLastError());
-      D2H(part.data(), B.aux, sizeof(double) * 4 * blocks);
+      D2H(part.data(), d_part, sizeof(double) * 4 * blocks);
       for (unsigned k = 0; k < blocks; ++k) {
         v[0] = std::fmin(v[0], part[4 * k]); v[1] = std::fmax(v[1], part[4 * k + 1]);
         v[2] = std::fmin(v[2], part[4 * k + 2]); v[3] = std::fmax(v[3], part[4 * k + 3]);
@@ -305,17 +273,18 @@ int odr_proj_grid_lonlat(odr_ctx *c, const odr_proj_desc *proj, int32_t nx, cons
   for (int k = 0; k < ny; ++k) REQUIRE(std::isfinite(ys[k]), "ys[%d] is not finite", k);
   const long long total = (long long)nx * (long long)ny, chunk = std::min(total, CONC_GRID_CHUNK);
   HIPCHK(hipSetDevice(c->device));
-  ConcBuffers B;
-  HIPCHK(hipMalloc((void **)&B.edges, sizeof(double) * (size_t)(nx + ny)));
-  HIPCHK(hipMalloc(&B.aux, sizeof(double) * 2 * (size_t)chunk));
-  H2D(B.edges, xs, sizeof(double) * (size_t)nx);
-  H2D(B.edges + nx, ys, sizeof(double) * (size_t)ny);
+  DevScope B;
+  double *axes, *dlon;
+  if (int rc = B.alloc((void **)&axes, sizeof(double) * (size_t)(nx + ny))) return rc;
+  if (int rc = B.alloc((void **)&dlon, sizeof(double) * 2 * (size_t)chunk)) return rc;
+  H2D(axes, xs, sizeof(double) * (size_t)nx);
+  H2D(axes + nx, ys, sizeof(double) * (size_t)ny);
   DevProj P;
   odr_i_proj_init(P, proj);
-  double *dlon = (double *)B.aux, *dlat = dlon + chunk;
+  double *dlat = dlon + chunk;
   for (long long k0 = 0; k0 < total; k0 += chunk) {
     const long long m = std::min(chunk, total - k0);
-    hipLaunchKernelGGL(k_conc_grid, dim3(nblk(m)), dim3(BLOCK), 0, c->stream, P, (const double *)B.edges, (const double *)(B.edges + nx),
+    hipLaunchKernelGGL(k_conc_grid, dim3(nblk(m)), dim3(BLOCK), 0, c->stream, P, (const double *)axes, (const double *)(axes + nx),
                        (int)ny, k0, m, dlon, dlat);
     HIPCHK(hipGetLastError());
     D2H(lon + k0, dlon, sizeof(double) * (size_t)m);
@@ -347,19 +316,21 @@ int odr_box_smooth(odr_ctx *c, int64_t n_planes, int32_t n0, int32_t n1, int32_t
   if (n_planes == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
   const long long per = std::max<long long>(1, std::min<long long>(n_planes, (long long)(CONC_BOX_CELLS / plane)));
-  ConcBuffers B;
-  HIPCHK(hipMalloc(&B.aux, sizeof(double) * plane * (size_t)per));
-  HIPCHK(hipMalloc(&B.aux2, sizeof(long long) * plane * (size_t)per));
+  DevScope B;
+  double *d_val;
+  long long *d_sum;
+  if (int rc = B.alloc((void **)&d_val, sizeof(double) * plane * (size_t)per)) return rc;
+  if (int rc = B.alloc((void **)&d_sum, sizeof(long long) * plane * (size_t)per)) return rc;
   const double w = 2.0 * n + 1.0;
   for (long long p0 = 0; p0 < n_planes; p0 += per) {
     const long long m = std::min(per, n_planes - p0), cells = m * (long long)plane;
-    H2D(B.aux, a + (size_t)p0 * plane, sizeof(double) * (size_t)cells);
-    hipLaunchKernelGGL((k_conc_box<true, double, long long>), dim3(nblk(cells)), dim3(BLOCK), 0, c->stream, (const double *)B.aux,
-                       (long long *)B.aux2, cells, (long long)n0, (long long)n1, (long long)n, 1.0);
-    hipLaunchKernelGGL((k_conc_box<false, long long, double>), dim3(nblk(cells)), dim3(BLOCK), 0, c->stream, (const long long *)B.aux2,
-                       (double *)B.aux, cells, (long long)n0, (long long)n1, (long long)n, w * w);
+    H2D(d_val, a + (size_t)p0 * plane, sizeof(double) * (size_t)cells);
+    hipLaunchKernelGGL((k_conc_box<true, double, long long>), dim3(nblk(cells)), dim3(BLOCK), 0, c->stream, (const double *)d_val, d_sum,
+                       cells, (long long)n0, (long long)n1, (long long)n, 1.0);
+    hipLaunchKernelGGL((k_conc_box<false, long long, double>), dim3(nblk(cells)), dim3(BLOCK), 0, c->stream, (const long long *)d_sum, d_val,
+                       cells, (long long)n0, (long long)n1, (long long)n, w * w);
     HIPCHK(hipGetLastError());
-    D2H(out + (size_t)p0 * plane, B.aux, sizeof(double) * (size_t)cells);
+    D2H(out + (size_t)p0 * plane, d_val, sizeof(double) * (size_t)cells);
   }
   return 0;
 }

@@ -8,39 +8,10 @@ namespace {
 constexpr size_t DENSITY_SLAB_BYTES = 256u << 20;      // device memory of one slab of host inputs (ODR_DENSITY_SLAB_BYTES overrides)
 constexpr long long DENSITY_LAUNCH_ENTRIES = 1ll << 30;   // entries of one launch
 
-float g_kernel_ms = 0.f;      // odr_density_last_kernel_ms
-
-struct DensityBuffers {      // released on every way out of odr_density_map
-  void *hist = nullptr, *slab = nullptr;
-  double *edges = nullptr;
-  std::vector<hipEvent_t> events;      // before and after every launch
-  ~DensityBuffers() {
-    for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
-    if (hist) (void)hipFree(hist);
-    if (slab) (void)hipFree(slab);
-    if (edges) (void)hipFree(edges);
-  }
-};
-
-bool on_device(const void *ptr) {
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, ptr) == hipSuccess) return at.type == hipMemoryTypeDevice;
-  (void)hipGetLastError();      // plain pageable memory: not an error
-  return false;
-}
-
 int edges_ok(const double *e, int n, const char *what) {
   REQUIRE(n >= 2, "%s: %d edges, fewer than two", what, n);
   for (int k = 0; k < n; ++k) REQUIRE(std::isfinite(e[k]), "%s[%d] is not finite", what, k);
   for (int k = 1; k < n; ++k) REQUIRE(e[k] > e[k - 1], "%s is not strictly increasing at %d", what, k);
-  return 0;
-}
-
-int mark(odr_ctx *c, DensityBuffers &B) {
-  hipEvent_t ev;
-  HIPCHK(hipEventCreate(&ev));
-  B.events.push_back(ev);
-  HIPCHK(hipEventRecord(ev, c->stream));
   return 0;
 }
 
@@ -81,19 +52,21 @@ int odr_density_map(odr_ctx *c, int64_t n_trajectories, int32_t n_times, const f
   const size_t cell_bytes = weighted ? sizeof(double) : sizeof(unsigned);
 
   HIPCHK(hipSetDevice(c->device));
-  DensityBuffers B;
-  HIPCHK(hipMalloc(&B.hist, 3 * cells * cell_bytes));      // (H_stranded's is written by nothing when there is no such category)
-  HIPCHK(hipMemsetAsync(B.hist, 0, 3 * cells * cell_bytes, c->stream));
-  HIPCHK(hipMalloc((void **)&B.edges, sizeof(double) * (size_t)(n_lon_edges + n_lat_edges)));
-  H2D(B.edges, lon_edges, sizeof(double) * (size_t)n_lon_edges);
-  H2D(B.edges + n_lon_edges, lat_edges, sizeof(double) * (size_t)n_lat_edges);
+  DevScope B;      // released on every way out
+  void *hist, *slab = nullptr;
+  double *edges;
+  if (int rc = B.alloc(&hist, 3 * cells * cell_bytes)) return rc;      // (H_stranded's is written by nothing when there is no such category)
+  HIPCHK(hipMemsetAsync(hist, 0, 3 * cells * cell_bytes, c->stream));
+  if (int rc = B.alloc((void **)&edges, sizeof(double) * (size_t)(n_lon_edges + n_lat_edges))) return rc;
+  H2D(edges, lon_edges, sizeof(double) * (size_t)n_lon_edges);
+  H2D(edges + n_lon_edges, lat_edges, sizeof(double) * (size_t)n_lat_edges);
 
   // slab: whole trajectories; the arrays that are host memory take slab_bytes / n_host of device memory each
   const float *in[5] = {lon, lat, z, status, weight};
   bool dev[5];
   int n_host = 0;
   for (int k = 0; k < 5; ++k) {
-    dev[k] = in[k] ? on_device(in[k]) : true;
+    dev[k] = in[k] ? odr_i_on_device(in[k]) : true;
     if (!dev[k]) ++n_host;
   }
   long long slab_traj = std::max<long long>(1, DENSITY_LAUNCH_ENTRIES / n_times);
@@ -109,13 +82,15 @@ int odr_density_map(odr_ctx *c, int64_t n_trajectories, int32_t n_times, const f
   }
   slab_traj = std::min<long long>(slab_traj, n_trajectories);
   const size_t slab_floats = (size_t)slab_traj * (size_t)n_times;
-  if (n_host) HIPCHK(hipMalloc(&B.slab, sizeof(float) * slab_floats * (size_t)n_host));
+  if (n_host) if (int rc = B.alloc(&slab, sizeof(float) * slab_floats * (size_t)n_host)) return rc;
 
   DensityArgs A;
-  A.lon_edges = B.edges; A.lat_edges = B.edges + n_lon_edges;
+  A.lon_edges = edges; A.lat_edges = edges + n_lon_edges;
   A.ax_lon = density_axis(lon_edges, n_lon_edges); A.ax_lat = density_axis(lat_edges, n_lat_edges);
   A.n_times = n_times; A.stranded_code = stranded_code;
   const bool lds = n_lon_edges + n_lat_edges <= DENSITY_LDS_EDGES;
+  KernelClock &clock = c->clock[CLOCK_DENSITY];
+  clock.reset();
   for (long long t0 = 0; t0 < n_trajectories; t0 += slab_traj) {
     const long long nt = std::min(slab_traj, n_trajectories - t0);
     const size_t off = (size_t)t0 * (size_t)n_times, count = (size_t)nt * (size_t)n_times;
@@ -124,31 +99,25 @@ int odr_density_map(odr_ctx *c, int64_t n_trajectories, int32_t n_times, const f
     for (int k = 0; k < 5; ++k) {
       if (!in[k]) { ptr[k] = nullptr; continue; }
       if (dev[k]) { ptr[k] = in[k] + off; continue; }
-      float *d = (float *)B.slab + slab_floats * (size_t)h++;
+      float *d = (float *)slab + slab_floats * (size_t)h++;
       H2D(d, in[k] + off, sizeof(float) * count);      // waits for the stream: the launch of the slab before has read `d`
       ptr[k] = d;
     }
     A.lon = ptr[0]; A.lat = ptr[1]; A.z = ptr[2]; A.status = ptr[3]; A.weight = ptr[4];
     A.n = (long long)count;
-    int rc = mark(c, B);
+    int rc = clock.start(c->stream);
     if (rc) return rc;
     if (weighted) {
-      double *h64 = (double *)B.hist;
+      double *h64 = (double *)hist;
       rc = launch<true, double>(c, A, lds, h64, h64 + cells, h64 + 2 * cells);
     } else {
-      unsigned *h32 = (unsigned *)B.hist;
+      unsigned *h32 = (unsigned *)hist;
       rc = launch<false, unsigned>(c, A, lds, h32, h32 + cells, h32 + 2 * cells);
     }
     if (rc) return rc;
-    if ((rc = mark(c, B))) return rc;
+    if ((rc = clock.stop(c->stream))) return rc;
   }
   HIPCHK(hipStreamSynchronize(c->stream));
-  g_kernel_ms = 0.f;
-  for (size_t k = 0; k + 1 < B.events.size(); k += 2) {
-    float ms;
-    HIPCHK(hipEventElapsedTime(&ms, B.events[k], B.events[k + 1]));
-    g_kernel_ms += ms;
-  }
 
   // histograms -> float64 host arrays, through the bounce buffer
   void *b;
@@ -157,7 +126,7 @@ int odr_density_map(odr_ctx *c, int64_t n_trajectories, int32_t n_times, const f
   for (int k = 0; k < nh; ++k) {
     for (size_t o = 0; o < cells; o += chunk) {
       const size_t m = std::min(chunk, cells - o);
-      HIPCHK(hipMemcpyAsync(b, (const char *)B.hist + ((size_t)k * cells + o) * cell_bytes, m * cell_bytes, hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(hipMemcpyAsync(b, (const char *)hist + ((size_t)k * cells + o) * cell_bytes, m * cell_bytes, hipMemcpyDeviceToHost, c->stream));
       HIPCHK(hipStreamSynchronize(c->stream));
       if (weighted) memcpy(out[k] + o, b, m * sizeof(double));
       else for (size_t i = 0; i < m; ++i) out[k][o + i] = (double)((const unsigned *)b)[i];
@@ -167,9 +136,8 @@ int odr_density_map(odr_ctx *c, int64_t n_trajectories, int32_t n_times, const f
   return 0;
 }
 
-// Device time of the k_density launches of the last odr_density_map of this process [ms], summed over its slabs
+// Device time of the k_density launches of the last odr_density_map of this context [ms], summed over its slabs
 int odr_density_last_kernel_ms(odr_ctx *c, float *ms) {
   REQUIRE(c && ms, "NULL argument");
-  *ms = g_kernel_ms;
-  return 0;
+  return c->clock[CLOCK_DENSITY].read(ms);
 }

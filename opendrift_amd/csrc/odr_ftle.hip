@@ -5,25 +5,6 @@
 
 namespace {
 
-float g_kernel_ms = 0.f;      // odr_ftle_last_kernel_ms
-
-struct FtleBuffers {      // released on every way out of odr_ftle_map
-  float *lon = nullptr, *lat = nullptr, *out = nullptr;
-  double *disp = nullptr, *axes = nullptr;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~FtleBuffers() {
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    for (void *q : {(void *)lon, (void *)lat, (void *)out, (void *)disp, (void *)axes}) if (q) (void)hipFree(q);
-  }
-};
-
-bool on_device(const void *ptr) {
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, ptr) == hipSuccess) return at.type == hipMemoryTypeDevice;
-  (void)hipGetLastError();      // plain pageable memory: not an error
-  return false;
-}
-
 bool kind_ok(int kind) {
   switch (kind) {
     case ODR_PROJ_LATLONG: case ODR_PROJ_STERE_EQUIT_SPHERE: case ODR_PROJ_STERE_POLAR: case ODR_PROJ_MERC: case ODR_PROJ_LCC:
@@ -50,48 +31,46 @@ int odr_ftle_map(odr_ctx *c, const odr_proj_desc *proj, int32_t nx, int32_t ny, 
   const size_t n = (size_t)nx * (size_t)ny;
 
   HIPCHK(hipSetDevice(c->device));
-  FtleBuffers B;
-  const float *dlon = lon, *dlat = lat;
-  if (!on_device(lon)) {
-    HIPCHK(hipMalloc((void **)&B.lon, sizeof(float) * n));
-    H2D(B.lon, lon, sizeof(float) * n);
-    dlon = B.lon;
+  DevScope B;      // released on every way out
+  const float *in[2] = {lon, lat};
+  for (const float *&q : in) {
+    if (odr_i_on_device(q)) continue;
+    float *up;
+    if (int rc = B.alloc((void **)&up, sizeof(float) * n)) return rc;
+    H2D(up, q, sizeof(float) * n);
+    q = up;
   }
-  if (!on_device(lat)) {
-    HIPCHK(hipMalloc((void **)&B.lat, sizeof(float) * n));
-    H2D(B.lat, lat, sizeof(float) * n);
-    dlat = B.lat;
-  }
-  HIPCHK(hipMalloc((void **)&B.axes, sizeof(double) * ((size_t)nx + (size_t)ny)));
-  H2D(B.axes, xs, sizeof(double) * (size_t)nx);
-  H2D(B.axes + nx, ys, sizeof(double) * (size_t)ny);
-  HIPCHK(hipMalloc((void **)&B.disp, sizeof(double) * 2 * n));
-  HIPCHK(hipMalloc((void **)&B.out, sizeof(float) * n));
+  double *axes, *disp;
+  float *out;
+  if (int rc = B.alloc((void **)&axes, sizeof(double) * ((size_t)nx + (size_t)ny))) return rc;
+  H2D(axes, xs, sizeof(double) * (size_t)nx);
+  H2D(axes + nx, ys, sizeof(double) * (size_t)ny);
+  if (int rc = B.alloc((void **)&disp, sizeof(double) * 2 * n)) return rc;
+  if (int rc = B.alloc((void **)&out, sizeof(float) * n)) return rc;
   DevProj P;
   odr_i_proj_init(P, proj);
 
-  for (hipEvent_t &e : B.ev) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipEventRecord(B.ev[0], c->stream));
-  hipLaunchKernelGGL(k_ftle_displacement, dim3(nblk((long long)n)), dim3(BLOCK), 0, c->stream, P, dlon, dlat, B.axes, B.axes + nx,
-                     (int)nx, (long long)n, B.disp, B.disp + n);
+  KernelClock &clock = c->clock[CLOCK_FTLE];
+  clock.reset();
+  if (int rc = clock.start(c->stream)) return rc;
+  hipLaunchKernelGGL(k_ftle_displacement, dim3(nblk((long long)n)), dim3(BLOCK), 0, c->stream, P, in[0], in[1], axes, axes + nx, (int)nx,
+                     (long long)n, disp, disp + n);
   HIPCHK(hipGetLastError());
   const unsigned tiles_x = (unsigned)((nx + FTLE_TILE_X - 1) / FTLE_TILE_X), tiles_y = (unsigned)((ny + FTLE_TILE_Y - 1) / FTLE_TILE_Y);
   // (tiles_x * tiles_y < 2^31: n < 2^31 and nx, ny >= 2 leave at most 2^28 + 2^24 tiles)
-  hipLaunchKernelGGL(k_ftle_cell, dim3(tiles_x * tiles_y), dim3(FTLE_TILE_X * FTLE_TILE_Y), 0, c->stream, B.disp, B.disp + n, (int)nx,
-                     (int)ny, tiles_x, 2 * delta, fabs(duration_seconds), B.out);
+  hipLaunchKernelGGL(k_ftle_cell, dim3(tiles_x * tiles_y), dim3(FTLE_TILE_X * FTLE_TILE_Y), 0, c->stream, disp, disp + n, (int)nx, (int)ny,
+                     tiles_x, 2 * delta, fabs(duration_seconds), out);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(B.ev[1], c->stream));
+  if (int rc = clock.stop(c->stream)) return rc;
   HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipEventElapsedTime(&g_kernel_ms, B.ev[0], B.ev[1]));
 
-  D2H(ftle, B.out, sizeof(float) * n);
-  if (displacement) D2H(displacement, B.disp, sizeof(double) * 2 * n);
+  D2H(ftle, out, sizeof(float) * n);
+  if (displacement) D2H(displacement, disp, sizeof(double) * 2 * n);
   return 0;
 }
 
-// Device time of the two launches of the last odr_ftle_map of this process that got as far as launching [ms]
+// Device time of the two launches of the last odr_ftle_map of this context that got as far as launching [ms]
 int odr_ftle_last_kernel_ms(odr_ctx *c, float *ms) {
   REQUIRE(c && ms, "NULL argument");
-  *ms = g_kernel_ms;
-  return 0;
+  return c->clock[CLOCK_FTLE].read(ms);
 }

@@ -9,37 +9,6 @@ constexpr size_t TRAJ_SLAB_BYTES = 256u << 20;         // lon and lat of one sla
 constexpr long long TRAJ_LAUNCH_ENTRIES = 1ll << 30;   // positions of one launch
 constexpr long long INVERSE_CHUNK = 1ll << 20;         // pairs of one odr_geod_inverse launch
 
-float g_kernel_ms = 0.f;      // odr_trajectory_lengths_last_kernel_ms
-
-struct Buffers {      // released on every way out
-  std::vector<void *> dev;
-  std::vector<hipEvent_t> events;      // before and after the launches of every slab
-  ~Buffers() {
-    for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
-    for (void *p : dev) (void)hipFree(p);
-  }
-  int alloc(void **p, size_t bytes) {
-    HIPCHK(hipMalloc(p, bytes));
-    dev.push_back(*p);
-    return 0;
-  }
-};
-
-bool on_device(const void *ptr) {
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, ptr) == hipSuccess) return at.type == hipMemoryTypeDevice;
-  (void)hipGetLastError();      // plain pageable memory: not an error
-  return false;
-}
-
-int mark(odr_ctx *c, Buffers &B) {
-  hipEvent_t ev;
-  HIPCHK(hipEventCreate(&ev));
-  B.events.push_back(ev);
-  HIPCHK(hipEventRecord(ev, c->stream));
-  return 0;
-}
-
 // nrows contiguous device rows of rowlen doubles -> host rows dst_pitch doubles apart, several rows per trip through the bounce buffer
 int rows_out(odr_ctx *c, double *dst, size_t dst_pitch, const double *dev, size_t nrows, size_t rowlen) {
   const size_t cap = ODR_BOUNCE_BYTES / sizeof(double);
@@ -69,7 +38,7 @@ int odr_geod_inverse(odr_ctx *c, int64_t n, const double *lon1, const double *la
   REQUIRE(n >= 0, "negative size");
   if (n == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
-  Buffers B;
+  DevScope B;      // released on every way out
   const long long chunk = std::min<long long>(n, INVERSE_CHUNK);
   double *d[7];
   for (int k = 0; k < 7; ++k) if (int rc = B.alloc((void **)&d[k], sizeof(double) * (size_t)chunk)) return rc;
@@ -101,11 +70,12 @@ int odr_trajectory_lengths(odr_ctx *c, int64_t n_trajectories, int32_t n_times, 
     REQUIRE(v > 0, "ODR_TRAJ_SLAB_BYTES=%s", s);
     budget = (size_t)v;
   }
-  g_kernel_ms = 0.f;
+  KernelClock &clock = c->clock[CLOCK_TRAJ_LENGTHS];
+  clock.reset();
   if (n_trajectories == 0) return 0;
 
   HIPCHK(hipSetDevice(c->device));
-  const bool dev[2] = {on_device(lon), on_device(lat)};
+  const bool dev[2] = {odr_i_on_device(lon), odr_i_on_device(lat)};
   const int n_seg = n_times - 1;
   const size_t row = 2 * sizeof(float) * (size_t)n_times;
   long long slab_traj = std::max<long long>(1, (long long)(budget / row));
@@ -113,7 +83,7 @@ int odr_trajectory_lengths(odr_ctx *c, int64_t n_trajectories, int32_t n_times, 
   slab_traj = std::min<long long>(slab_traj, n_trajectories);
   const size_t slab_floats = (size_t)slab_traj * (size_t)n_times, slab_seg = (size_t)slab_traj * (size_t)n_seg;
 
-  Buffers B;
+  DevScope B;      // released on every way out
   float *up[2] = {nullptr, nullptr};
   for (int k = 0; k < 2; ++k) if (!dev[k]) if (int rc = B.alloc((void **)&up[k], sizeof(float) * slab_floats)) return rc;
   double *d_dist, *d_speed = nullptr, *d_total;
@@ -133,29 +103,23 @@ int odr_trajectory_lengths(odr_ctx *c, int64_t n_trajectories, int32_t n_times, 
       ptr[k] = up[k];
     }
     const unsigned tiles_traj = (unsigned)((nr + TRAJ_TILE - 1) / TRAJ_TILE);
-    if (int rc = mark(c, B)) return rc;
+    if (int rc = clock.start(c->stream)) return rc;
     hipLaunchKernelGGL(k_traj_segments, dim3(tiles_traj * tiles_t), dim3(BLOCK), 0, c->stream, ptr[0], ptr[1], nr, (int)n_times, tiles_traj,
                        dt_seconds, nr, d_dist, d_speed);
     HIPCHK(hipGetLastError());
     hipLaunchKernelGGL(k_traj_totals, dim3(nblk(nr)), dim3(BLOCK), 0, c->stream, (const double *)d_dist, nr, n_seg, nr, d_total);
     HIPCHK(hipGetLastError());
-    if (int rc = mark(c, B)) return rc;
+    if (int rc = clock.stop(c->stream)) return rc;
     D2H(total_length + r0, d_total, sizeof(double) * (size_t)nr);
     if (distances) if (int rc = rows_out(c, distances + r0, (size_t)n_trajectories, d_dist, (size_t)n_seg, (size_t)nr)) return rc;
     if (speeds) if (int rc = rows_out(c, speeds + r0, (size_t)n_trajectories, d_speed, (size_t)n_seg, (size_t)nr)) return rc;
   }
   HIPCHK(hipStreamSynchronize(c->stream));
-  for (size_t k = 0; k + 1 < B.events.size(); k += 2) {
-    float ms;
-    HIPCHK(hipEventElapsedTime(&ms, B.events[k], B.events[k + 1]));
-    g_kernel_ms += ms;
-  }
   return 0;
 }
 
-// Device time of the launches of the last odr_trajectory_lengths of this process [ms], summed over its slabs
+// Device time of the launches of the last odr_trajectory_lengths of this context [ms], summed over its slabs
 int odr_trajectory_lengths_last_kernel_ms(odr_ctx *c, float *ms) {
   REQUIRE(c && ms, "NULL argument");
-  *ms = g_kernel_ms;
-  return 0;
+  return c->clock[CLOCK_TRAJ_LENGTHS].read(ms);
 }

@@ -45,6 +45,67 @@ int odr_i_fail(int code, const char *fmt, ...);   // records the message for odr
   } while (0)
 #define REQUIRE(c, ...) do { if (!(c)) return fail(ODR_ERR_INVALID, __VA_ARGS__); } while (0)
 
+// Device time of the launches of one unit's last call [ms] (the odr_*_last_kernel_ms entry points): start / stop bracket a launch
+// or a group of launches, read() waits for the last bracket and adds them up.  The events are created on the device that is
+// current at start() -- the context's: every caller has made it so for its launches -- and serve every later measurement.
+struct KernelClock {
+  std::vector<hipEvent_t> pool;   // [2k] start, [2k + 1] stop of bracket k; destroyed by odr_ctx_destroy
+  size_t pending = 0;             // events of the brackets closed since reset() and not read yet
+  float total = 0.f;
+  void reset() { pending = 0; total = 0.f; }
+  int start(hipStream_t st) {
+    while (pool.size() < pending + 2) {
+      hipEvent_t ev;
+      HIPCHK(hipEventCreate(&ev));
+      pool.push_back(ev);
+    }
+    HIPCHK(hipEventRecord(pool[pending], st));
+    return 0;
+  }
+  int stop(hipStream_t st) {
+    HIPCHK(hipEventRecord(pool[pending + 1], st));
+    pending += 2;
+    return 0;
+  }
+  int read(float *ms) {
+    if (pending) {
+      HIPCHK(hipEventSynchronize(pool[pending - 1]));
+      float sum = total;
+      for (size_t k = 0; k < pending; k += 2) {
+        float pair;
+        HIPCHK(hipEventElapsedTime(&pair, pool[k], pool[k + 1]));
+        sum += pair;
+      }
+      total = sum;
+      pending = 0;
+    }
+    *ms = total;
+    return 0;
+  }
+};
+enum { CLOCK_DENSITY, CLOCK_CONC, CLOCK_FTLE, CLOCK_TRAJ_LENGTHS, CLOCK_POLYGON_POINTS, CLOCK_UMESH, CLOCK_SHAPE, CLOCK_COMBINED, N_CLOCKS };
+
+// Device arrays that live as long as the scope does: the temporaries of a call, the arrays a handle owns
+struct DevScope {
+  std::vector<void *> bufs;
+  DevScope() = default;
+  DevScope(const DevScope &) = delete;
+  DevScope &operator=(const DevScope &) = delete;
+  ~DevScope() { for (void *p : bufs) (void)hipFree(p); }
+  int alloc(void **p, size_t bytes) {
+    HIPCHK(hipMalloc(p, bytes));
+    bufs.push_back(*p);
+    return 0;
+  }
+};
+
+static inline bool odr_i_on_device(const void *ptr) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, ptr) == hipSuccess) return at.type == hipMemoryTypeDevice;
+  (void)hipGetLastError();      // plain pageable memory: not an error
+  return false;
+}
+
 struct Staged { DevBlock blk; float *base; size_t bytes; unsigned long long cid[NVAR]; };   // uploaded, not yet committed (cid: odr_block_set_content_ids)
 struct Retired { void *ptr; size_t bytes; hipEvent_t ev; };       // replaced block, freed once the compute stream passed
 
@@ -126,6 +187,7 @@ struct odr_ctx {
   bool red_partial = false;  // red[] was formed by the step launch (odr_ctx_set_step_reduce): only the slots the movers' == 0 tests read, R_NSURF as a flag
   int step_reduce_on = 0, step_reduce_rel = 0;
   double step_reduce_wdd = 0.1;
+  KernelClock clock[N_CLOCKS];   // one per unit that reports the device time of its last call on this context
 };
 
 struct odr_weather;      // odr_weather.hip: OpenOil's weathering state by element ID

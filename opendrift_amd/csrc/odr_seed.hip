@@ -7,22 +7,6 @@ namespace {
 
 constexpr long long POINTS_CHUNK = 1ll << 20;      // points of one odr_points_in_polygon launch
 
-float g_kernel_ms = 0.f;      // odr_polygon_points_last_kernel_ms
-
-struct Buffers {      // released on every way out
-  std::vector<void *> dev;
-  hipEvent_t ev[2] = {nullptr, nullptr};
-  ~Buffers() {
-    for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
-    for (void *p : dev) (void)hipFree(p);
-  }
-  int alloc(void **p, size_t bytes) {
-    HIPCHK(hipMalloc(p, bytes));
-    dev.push_back(*p);
-    return 0;
-  }
-};
-
 bool all_finite(const double *a, long long n) {
   for (long long k = 0; k < n; ++k) if (!std::isfinite(a[k])) return false;
   return true;
@@ -39,7 +23,7 @@ int odr_geod_npts(odr_ctx *c, double lon1, double lat1, double lon2, double lat2
           "end points (%g, %g) and (%g, %g)", lon1, lat1, lon2, lat2);
   if (npts == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
-  Buffers B;
+  DevScope B;      // released on every way out
   double *d_line, *d_lon, *d_lat;
   if (int rc = B.alloc((void **)&d_line, sizeof(double) * 2)) return rc;
   if (int rc = B.alloc((void **)&d_lon, sizeof(double) * (size_t)npts)) return rc;
@@ -64,7 +48,7 @@ int odr_points_in_polygon(odr_ctx *c, int64_t n, const double *x, const double *
   REQUIRE(all_finite(vx, m) && all_finite(vy, m), "a vertex is not finite");
   if (n == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
-  Buffers B;
+  DevScope B;      // released on every way out
   const long long chunk = std::min<long long>(n, POINTS_CHUNK);
   double *d_x, *d_y, *d_vx, *d_vy;
   unsigned char *d_in;
@@ -105,7 +89,8 @@ int odr_polygon_points(odr_ctx *c, int32_t m, const double *lons, const double *
           *std::max_element(lats, lats + m));
   REQUIRE(status != SEED_NO_AREA, "the polygon has no area");
   REQUIRE(status != SEED_TOO_MANY, "a grid of 2^31 points or more");
-  g_kernel_ms = 0.f;
+  KernelClock &clock = c->clock[CLOCK_POLYGON_POINTS];
+  clock.reset();
   *nx = P.nx; *ny = P.ny; *n_inside = 0;
   const long long n = (long long)P.nx * P.ny;
   if (n == 0) {
@@ -114,7 +99,7 @@ int odr_polygon_points(odr_ctx *c, int32_t m, const double *lons, const double *
   }
 
   HIPCHK(hipSetDevice(c->device));
-  Buffers B;
+  DevScope B;      // released on every way out
   const int mc = (int)rx.size();
   const long long nwg = (n + SEED_BLOCK - 1) / SEED_BLOCK;
   double *d_vx, *d_vy;
@@ -127,20 +112,16 @@ int odr_polygon_points(odr_ctx *c, int32_t m, const double *lons, const double *
   if (int rc = B.alloc((void **)&d_offsets, sizeof(unsigned) * (size_t)(nwg + 1))) return rc;
   H2D(d_vx, rx.data(), sizeof(double) * (size_t)mc);
   H2D(d_vy, ry.data(), sizeof(double) * (size_t)mc);
-  for (hipEvent_t &e : B.ev) HIPCHK(hipEventCreate(&e));
-  HIPCHK(hipEventRecord(B.ev[0], c->stream));
+  if (int rc = clock.start(c->stream)) return rc;
   hipLaunchKernelGGL(k_seed_edges, dim3((unsigned)nwg), dim3(SEED_BLOCK), 0, c->stream, P, n, mc, (const double *)d_vx, (const double *)d_vy,
                      d_masks, d_counts);
   HIPCHK(hipGetLastError());
   hipLaunchKernelGGL(k_seed_scan, dim3(1), dim3(SEED_BLOCK), 0, c->stream, (const unsigned *)d_counts, nwg, d_offsets);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(B.ev[1], c->stream));
+  if (int rc = clock.stop(c->stream)) return rc;
   unsigned total = 0;
   D2H(&total, d_offsets + nwg, sizeof(unsigned));
   HIPCHK(hipStreamSynchronize(c->stream));
-  float ms;
-  HIPCHK(hipEventElapsedTime(&ms, B.ev[0], B.ev[1]));
-  g_kernel_ms = ms;
   *n_inside = total;
   if (total == 0) {
     seed_border(m, lons, lats, number, out_lon, out_lat);
@@ -151,24 +132,21 @@ int odr_polygon_points(odr_ctx *c, int32_t m, const double *lons, const double *
   double *d_lon, *d_lat;
   if (int rc = B.alloc((void **)&d_lon, sizeof(double) * (size_t)keep)) return rc;
   if (int rc = B.alloc((void **)&d_lat, sizeof(double) * (size_t)keep)) return rc;
-  HIPCHK(hipEventRecord(B.ev[0], c->stream));
+  if (int rc = clock.start(c->stream)) return rc;
   hipLaunchKernelGGL(k_seed_compact, dim3((unsigned)nwg), dim3(SEED_BLOCK), 0, c->stream, P, n, (const unsigned long long *)d_masks,
                      (const unsigned *)d_offsets, keep, d_lon, d_lat);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(B.ev[1], c->stream));
+  if (int rc = clock.stop(c->stream)) return rc;
   D2H(out_lon, d_lon, sizeof(double) * (size_t)keep);
   D2H(out_lat, d_lat, sizeof(double) * (size_t)keep);
   HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipEventElapsedTime(&ms, B.ev[0], B.ev[1]));
-  g_kernel_ms += ms;
   seed_cyclic(out_lon, keep, number);
   seed_cyclic(out_lat, keep, number);
   return 0;
 }
 
-// Device time of the launches of the last odr_polygon_points of this process [ms]
+// Device time of the launches of the last odr_polygon_points of this context [ms]
 int odr_polygon_points_last_kernel_ms(odr_ctx *c, float *ms) {
   REQUIRE(c && ms, "NULL argument");
-  *ms = g_kernel_ms;
-  return 0;
+  return c->clock[CLOCK_POLYGON_POINTS].read(ms);
 }

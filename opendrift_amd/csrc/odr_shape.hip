@@ -6,7 +6,7 @@
 struct odr_shape {
   ShGrid dev;      // off / ent / tag: device arrays
   DevProj proj;
-  std::vector<void *> bufs;
+  DevScope bufs;
   long long entries, longest, nonempty;
   int nudges;
 };
@@ -15,38 +15,12 @@ namespace {
 
 constexpr long long CONTAINS_CHUNK = 1ll << 20;      // points of one odr_shape_contains launch
 
-// odr_shape_last_kernel_ms: the launches of odr_shape_contains are timed as they run (the call is synchronous); the launch of
-// odr_shape_sample is bracketed by two events that are read when the time is asked for
-float g_kernel_ms = 0.f;
-hipEvent_t g_ev[2] = {nullptr, nullptr};
-bool g_pending = false;
-int g_ev_device = -1;      // the device the two events belong to
-
-int ensure_events(const odr_ctx *c) {
-  if (g_ev_device != c->device) {
-    for (hipEvent_t &e : g_ev) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-    g_pending = false;
-    g_ev_device = c->device;
-  }
-  for (hipEvent_t &e : g_ev) if (!e) HIPCHK(hipEventCreate(&e));
-  return 0;
-}
-
 int upload(odr_ctx *c, odr_shape *s, const void *host, size_t bytes, const void **dev) {
-  void *p = nullptr;
-  HIPCHK(hipMalloc(&p, std::max<size_t>(bytes, 16)));      // (a shape without entries still has arrays to point at)
-  s->bufs.push_back(p);
+  void *p;
+  if (int rc = s->bufs.alloc(&p, std::max<size_t>(bytes, 16))) return rc;      // (a shape without entries still has arrays to point at)
   if (bytes) H2D(p, host, bytes);
   *dev = p;
   return 0;
-}
-
-void release(odr_shape *s) {
-  for (void *p : s->bufs) (void)hipFree(p);
-  delete s;
 }
 
 }  // namespace
@@ -77,7 +51,7 @@ int odr_shape_create(odr_ctx *c, const odr_proj_desc *proj, int64_t n_edges, con
   if (!rc) rc = upload(c, s, I.ent.data(), sizeof(ShEdge) * I.ent.size(), (const void **)&s->dev.ent);
   if (!rc) rc = upload(c, s, I.tag.data(), sizeof(int) * I.tag.size(), (const void **)&s->dev.tag);
   if (rc) {
-    release(s);
+    delete s;
     return rc;
   }
   *out = s;
@@ -88,7 +62,7 @@ int odr_shape_destroy(odr_ctx *c, odr_shape *s) {
   REQUIRE(c, "NULL argument");
   if (!s) return 0;
   HIPCHK(hipStreamSynchronize(c->stream));
-  release(s);
+  delete s;
   return 0;
 }
 
@@ -120,61 +94,44 @@ int odr_shape_sample(odr_ctx *c, odr_particles *p, odr_shape *s, int first) {
   p->env_cok[v] = false;
   if (p->n == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
-  if (int rc = ensure_events(c)) return rc;
-  HIPCHK(hipEventRecord(g_ev[0], c->stream));
+  KernelClock &clock = c->clock[CLOCK_SHAPE];
+  clock.reset();
+  if (int rc = clock.start(c->stream)) return rc;
   hipLaunchKernelGGL(k_shape_sample, dim3(nblk(p->n)), dim3(BLOCK), 0, c->stream, s->proj, s->dev, first != 0 ? 1 : 0, p->n,
                      (const double *)p->d64[0], (const double *)p->d64[1], p->env[v]);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(g_ev[1], c->stream));
-  g_pending = true;
-  return 0;
+  return clock.stop(c->stream);
 }
 
 // The bare query: land_binary_mask at n points in the reader's own coordinates.  x, y, out: host.  Synchronous.
 int odr_shape_contains(odr_ctx *c, odr_shape *s, int64_t n, const double *x, const double *y, float *out) {
   REQUIRE(c && s, "NULL argument");
   REQUIRE(n >= 0 && (n == 0 || (x && y && out)), "bad arguments");
-  g_kernel_ms = 0.f;
-  g_pending = false;
+  KernelClock &clock = c->clock[CLOCK_SHAPE];
+  clock.reset();
   if (n == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
-  if (int rc = ensure_events(c)) return rc;
   const long long chunk = std::min<long long>(n, CONTAINS_CHUNK);
-  double *d_xy = nullptr;
-  float *d_out = nullptr;
-  HIPCHK(hipMalloc((void **)&d_xy, sizeof(double) * 2 * (size_t)chunk));
-  if (hipMalloc((void **)&d_out, sizeof(float) * (size_t)chunk) != hipSuccess) {
-    (void)hipFree(d_xy);
-    return fail(ODR_ERR_HIP, "hipMalloc of %lld values", chunk);
-  }
-  int rc = 0;
-  for (long long o = 0; o < n && !rc; o += chunk) {
+  DevScope B;      // released on every way out
+  double *d_xy;
+  float *d_out;
+  if (int rc = B.alloc((void **)&d_xy, sizeof(double) * 2 * (size_t)chunk)) return rc;
+  if (int rc = B.alloc((void **)&d_out, sizeof(float) * (size_t)chunk)) return rc;
+  for (long long o = 0; o < n; o += chunk) {
     const long long k = std::min(chunk, (long long)n - o);
-    rc = odr_i_h2d(c, d_xy, x + o, sizeof(double) * (size_t)k, c->stream);
-    if (!rc) rc = odr_i_h2d(c, d_xy + chunk, y + o, sizeof(double) * (size_t)k, c->stream);
-    if (rc) break;
-    (void)hipEventRecord(g_ev[0], c->stream);
+    H2D(d_xy, x + o, sizeof(double) * (size_t)k);
+    H2D(d_xy + chunk, y + o, sizeof(double) * (size_t)k);
+    if (int rc = clock.start(c->stream)) return rc;
     hipLaunchKernelGGL(k_shape_contains, dim3(nblk(k)), dim3(BLOCK), 0, c->stream, s->dev, k, (const double *)d_xy, (const double *)(d_xy + chunk), d_out);
-    if (hipGetLastError() != hipSuccess) { rc = fail(ODR_ERR_HIP, "k_shape_contains did not launch"); break; }
-    (void)hipEventRecord(g_ev[1], c->stream);
-    rc = odr_i_d2h(c, out + o, d_out, sizeof(float) * (size_t)k, c->stream);
-    float ms = 0.f;
-    if (!rc && hipEventElapsedTime(&ms, g_ev[0], g_ev[1]) == hipSuccess) g_kernel_ms += ms;
+    HIPCHK(hipGetLastError());
+    if (int rc = clock.stop(c->stream)) return rc;
+    D2H(out + o, d_out, sizeof(float) * (size_t)k);      // waits for the stream: the next chunk may overwrite d_xy
   }
-  (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(d_xy);
-  (void)hipFree(d_out);
-  return rc;
+  return 0;
 }
 
-// Device time [ms] of the launches of this process's last odr_shape_contains, or of the launch of its last odr_shape_sample
+// Device time [ms] of the launches of this context's last odr_shape_contains, or of the launch of its last odr_shape_sample
 int odr_shape_last_kernel_ms(odr_ctx *c, float *ms) {
   REQUIRE(c && ms, "NULL argument");
-  if (g_pending) {
-    HIPCHK(hipEventSynchronize(g_ev[1]));
-    HIPCHK(hipEventElapsedTime(&g_kernel_ms, g_ev[0], g_ev[1]));
-    g_pending = false;
-  }
-  *ms = g_kernel_ms;
-  return 0;
+  return c->clock[CLOCK_SHAPE].read(ms);
 }

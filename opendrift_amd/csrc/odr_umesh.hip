@@ -8,7 +8,7 @@ struct odr_umesh {
   UmMesh dev;
   DevProj proj;
   int n_nodes, n_faces;
-  std::vector<void *> bufs;      // coordinates, index and sigma arrays
+  DevScope bufs;      // coordinates, index and sigma arrays
   struct Level {
     double t;
     float *data[NVAR];
@@ -21,36 +21,14 @@ namespace {
 
 constexpr long long NEAREST_CHUNK = 1ll << 20;      // points of one odr_umesh_nearest launch
 
-// odr_umesh_last_kernel_ms: the launches of odr_umesh_nearest are timed as they run (the call is synchronous); the launch of
-// odr_umesh_sample is bracketed by two events that are read when the time is asked for
-float g_kernel_ms = 0.f;
-hipEvent_t g_ev[2] = {nullptr, nullptr};
-bool g_pending = false;
-
 bool all_finite(const double *a, long long n) {
   for (long long k = 0; k < n; ++k) if (!std::isfinite(a[k])) return false;
   return true;
 }
 
-int g_ev_device = -1;      // the device the two events belong to
-
-int ensure_events(const odr_ctx *c) {
-  if (g_ev_device != c->device) {      // (a process that opens contexts on several devices: events stay with their device)
-    for (hipEvent_t &e : g_ev) {
-      if (e) (void)hipEventDestroy(e);
-      e = nullptr;
-    }
-    g_pending = false;
-    g_ev_device = c->device;
-  }
-  for (hipEvent_t &e : g_ev) if (!e) HIPCHK(hipEventCreate(&e));
-  return 0;
-}
-
 int upload(odr_ctx *c, odr_umesh *m, const void *host, size_t bytes, const void **dev) {
-  void *p = nullptr;
-  HIPCHK(hipMalloc(&p, bytes));
-  m->bufs.push_back(p);
+  void *p;
+  if (int rc = m->bufs.alloc(&p, bytes)) return rc;
   H2D(p, host, bytes);
   *dev = p;
   return 0;
@@ -67,8 +45,7 @@ int upload_index(odr_ctx *c, odr_umesh *m, int n, const double *x, const double 
 }
 
 void release(odr_umesh *m) {
-  for (void *p : m->bufs) (void)hipFree(p);
-  for (auto &L : m->level)
+  for (auto &L : m->level)      // (replaced in place by odr_umesh_set_level: not in bufs)
     for (float *p : L.data) if (p) (void)hipFree(p);
   delete m;
 }
@@ -219,14 +196,13 @@ int odr_umesh_sample(odr_ctx *c, odr_particles *p, odr_umesh *m, int32_t slot, i
   }
   if (p->n == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
-  if (int rc = ensure_events(c)) return rc;
-  HIPCHK(hipEventRecord(g_ev[0], c->stream));
+  KernelClock &clock = c->clock[CLOCK_UMESH];
+  clock.reset();
+  if (int rc = clock.start(c->stream)) return rc;
   hipLaunchKernelGGL(k_umesh_sample, dim3(nblk(p->n)), dim3(BLOCK), 0, c->stream, m->proj, m->dev, L, p->n, (const double *)p->d64[0],
                      (const double *)p->d64[1], (const double *)p->d64[2]);
   HIPCHK(hipGetLastError());
-  HIPCHK(hipEventRecord(g_ev[1], c->stream));
-  g_pending = true;
-  return 0;
+  return clock.stop(c->stream);
 }
 
 // The bare query: the index of the node (on_faces 0) or face centre nearest to each of n points in the mesh's own coordinates.
@@ -235,48 +211,32 @@ int odr_umesh_nearest(odr_ctx *c, odr_umesh *m, int on_faces, int64_t n, const d
   REQUIRE(c && m, "NULL argument");
   REQUIRE(n >= 0 && (n == 0 || (x && y && idx_out)), "bad arguments");
   REQUIRE(!on_faces || m->n_faces > 0, "the mesh has no faces");
-  g_kernel_ms = 0.f;
-  g_pending = false;
+  KernelClock &clock = c->clock[CLOCK_UMESH];
+  clock.reset();
   if (n == 0) return 0;
   HIPCHK(hipSetDevice(c->device));
-  if (int rc = ensure_events(c)) return rc;
   const UmIndex &T = on_faces ? m->dev.face : m->dev.node;
   const long long chunk = std::min<long long>(n, NEAREST_CHUNK);
-  double *d_xy = nullptr;
-  int *d_idx = nullptr;
-  HIPCHK(hipMalloc((void **)&d_xy, sizeof(double) * 2 * (size_t)chunk));
-  if (hipMalloc((void **)&d_idx, sizeof(int) * (size_t)chunk) != hipSuccess) {
-    (void)hipFree(d_xy);
-    return fail(ODR_ERR_HIP, "hipMalloc of %lld indices", chunk);
-  }
-  int rc = 0;
-  for (long long o = 0; o < n && !rc; o += chunk) {
+  DevScope B;      // released on every way out
+  double *d_xy;
+  int *d_idx;
+  if (int rc = B.alloc((void **)&d_xy, sizeof(double) * 2 * (size_t)chunk)) return rc;
+  if (int rc = B.alloc((void **)&d_idx, sizeof(int) * (size_t)chunk)) return rc;
+  for (long long o = 0; o < n; o += chunk) {
     const long long k = std::min(chunk, n - o);
-    rc = odr_i_h2d(c, d_xy, x + o, sizeof(double) * (size_t)k, c->stream);
-    if (!rc) rc = odr_i_h2d(c, d_xy + chunk, y + o, sizeof(double) * (size_t)k, c->stream);
-    if (rc) break;
-    (void)hipEventRecord(g_ev[0], c->stream);
+    H2D(d_xy, x + o, sizeof(double) * (size_t)k);
+    H2D(d_xy + chunk, y + o, sizeof(double) * (size_t)k);
+    if (int rc = clock.start(c->stream)) return rc;
     hipLaunchKernelGGL(k_umesh_nearest, dim3(nblk(k)), dim3(BLOCK), 0, c->stream, T, k, (const double *)d_xy, (const double *)(d_xy + chunk), d_idx);
-    if (hipGetLastError() != hipSuccess) { rc = fail(ODR_ERR_HIP, "k_umesh_nearest did not launch"); break; }
-    (void)hipEventRecord(g_ev[1], c->stream);
-    rc = odr_i_d2h(c, idx_out + o, d_idx, sizeof(int) * (size_t)k, c->stream);
-    float ms = 0.f;
-    if (!rc && hipEventElapsedTime(&ms, g_ev[0], g_ev[1]) == hipSuccess) g_kernel_ms += ms;
+    HIPCHK(hipGetLastError());
+    if (int rc = clock.stop(c->stream)) return rc;
+    D2H(idx_out + o, d_idx, sizeof(int) * (size_t)k);      // waits for the stream: the next chunk may overwrite d_xy
   }
-  (void)hipStreamSynchronize(c->stream);
-  (void)hipFree(d_xy);
-  (void)hipFree(d_idx);
-  return rc;
+  return 0;
 }
 
-// Device time [ms] of the launches of this process's last odr_umesh_nearest, or of the launch of its last odr_umesh_sample
+// Device time [ms] of the launches of this context's last odr_umesh_nearest, or of the launch of its last odr_umesh_sample
 int odr_umesh_last_kernel_ms(odr_ctx *c, float *ms) {
   REQUIRE(c && ms, "NULL argument");
-  if (g_pending) {
-    HIPCHK(hipEventSynchronize(g_ev[1]));
-    HIPCHK(hipEventElapsedTime(&g_kernel_ms, g_ev[0], g_ev[1]));
-    g_pending = false;
-  }
-  *ms = g_kernel_ms;
-  return 0;
+  return c->clock[CLOCK_UMESH].read(ms);
 }

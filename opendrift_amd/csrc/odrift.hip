@@ -91,6 +91,8 @@ int odr_ctx_destroy(odr_ctx *c) {
   for (int k = 0; k < 2; ++k) if (c->bounce[k]) (void)hipHostFree(c->bounce[k]);
   (void)hipEventDestroy(c->ev0);
   (void)hipEventDestroy(c->ev1);
+  for (KernelClock &k : c->clock)      // (a measurement nobody read goes with them)
+    for (hipEvent_t ev : k.pool) (void)hipEventDestroy(ev);
   (void)hipStreamDestroy(c->own_stream);
   delete c;
   return 0;

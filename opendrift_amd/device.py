@@ -14,6 +14,11 @@ from ._abi import VARIABLES, check
 
 _dp, _fp, _ip = C.POINTER(C.c_double), C.POINTER(C.c_float), C.POINTER(C.c_int32)
 
+# the 16 slots of the movers' global reduction (Particles.reduce_scalars, Particles.reduction_dict), in the library's order
+REDUCTION_KEYS = ('n_active', 'lon_min', 'lon_max', 'lat_min', 'lat_max', 'z_min', 'z_max', 'D_max',
+                  'stokes_sum_max', 'wind_speed_max', 'wdf_surface_max', 'n_surface', 'hs_max', 'tp_max', 'rel_wind_speed_max',
+                  'mld_max')
+
 
 def _vid(v, aliases=None):
     """Device id of a variable name (ids pass through).  aliases: Context.slot_aliases."""
@@ -158,6 +163,12 @@ class Context:
 
     def sync(self):
         check(self.lib.odr_sync(self.h))
+
+    def _last_kernel_ms(self, symbol):
+        """Device time [ms] of the launches of one unit's last call on this context (the odr_*_last_kernel_ms entry points)."""
+        ms = C.c_float()
+        check(getattr(self.lib, symbol)(self.h, C.byref(ms)))
+        return ms.value
 
     def set_stream(self, stream_ptr):
         check(self.lib.odr_set_stream(self.h, C.c_void_p(stream_ptr)))
@@ -485,9 +496,7 @@ class Context:
         return tuple(out)
 
     def density_last_kernel_ms(self):
-        ms = C.c_float()
-        check(self.lib.odr_density_last_kernel_ms(self.h, C.byref(ms)))
-        return ms.value
+        return self._last_kernel_ms('odr_density_last_kernel_ms')
 
     @staticmethod
     def _traj_time_arrays(what, arrays, shape):
@@ -537,9 +546,7 @@ class Context:
         return out
 
     def conc_last_kernel_ms(self):
-        ms = C.c_float()
-        check(self.lib.odr_conc_last_kernel_ms(self.h, C.byref(ms)))
-        return ms.value
+        return self._last_kernel_ms('odr_conc_last_kernel_ms')
 
     def proj_extent(self, proj, lon, lat, n=None):
         """(min x, max x, min y, max y) of proj(lon, lat) over the positions whose projected coordinates are finite
@@ -610,9 +617,7 @@ class Context:
         return (out, disp) if displacement else out
 
     def ftle_last_kernel_ms(self):
-        ms = C.c_float()
-        check(self.lib.odr_ftle_last_kernel_ms(self.h, C.byref(ms)))
-        return ms.value
+        return self._last_kernel_ms('odr_ftle_last_kernel_ms')
 
     def geod_inv(self, lon1, lat1, lon2, lat2):
         """pyproj.Geod(ellps='WGS84').inv on the device (odr_geod_inverse): (az12, az21, dist) as float64 arrays of the broadcast
@@ -655,9 +660,7 @@ class Context:
         return (total, dist, speed) if segments else total
 
     def trajectory_lengths_last_kernel_ms(self):
-        ms = C.c_float()
-        check(self.lib.odr_trajectory_lengths_last_kernel_ms(self.h, C.byref(ms)))
-        return ms.value
+        return self._last_kernel_ms('odr_trajectory_lengths_last_kernel_ms')
 
     def geod_npts(self, lon1, lat1, lon2, lat2, npts):
         """pyproj.Geod(ellps='WGS84').npts on the device (odr_geod_npts): (lon, lat) float64 arrays of the npts points at
@@ -693,36 +696,28 @@ class Context:
         return (lon, lat, dict(n_inside=n_inside.value, nx=nx.value, ny=ny.value)) if info else (lon, lat)
 
     def polygon_points_last_kernel_ms(self):
-        ms = C.c_float()
-        check(self.lib.odr_polygon_points_last_kernel_ms(self.h, C.byref(ms)))
-        return ms.value
+        return self._last_kernel_ms('odr_polygon_points_last_kernel_ms')
 
     def umesh(self, x, y, xc=None, yc=None, proj=None, **sigma):
         """The device image of a triangular mesh (odr_umesh_create): UMesh."""
         return UMesh(self, x, y, xc, yc, proj=proj, **sigma)
 
     def umesh_last_kernel_ms(self):
-        ms = C.c_float()
-        check(self.lib.odr_umesh_last_kernel_ms(self.h, C.byref(ms)))
-        return ms.value
+        return self._last_kernel_ms('odr_umesh_last_kernel_ms')
 
     def shape(self, x1, y1, x2, y2, poly, n_polygons, proj=None, invert=False, nx=0, ny=0):
         """The device image of coastline polygons (odr_shape_create): Shape."""
         return Shape(self, x1, y1, x2, y2, poly, n_polygons, proj=proj, invert=invert, nx=nx, ny=ny)
 
     def shape_last_kernel_ms(self):
-        ms = C.c_float()
-        check(self.lib.odr_shape_last_kernel_ms(self.h, C.byref(ms)))
-        return ms.value
+        return self._last_kernel_ms('odr_shape_last_kernel_ms')
 
     def combined(self, ops):
         """The device program of a reader expression (odr_combined_create): Combined.  ops: (kind, index, (d0, d1, d2)) in postfix."""
         return Combined(self, ops)
 
     def combined_last_kernel_ms(self):
-        ms = C.c_float()
-        check(self.lib.odr_combined_last_kernel_ms(self.h, C.byref(ms)))
-        return ms.value
+        return self._last_kernel_ms('odr_combined_last_kernel_ms')
 
     def particles(self, capacity):
         return Particles(self, capacity)
@@ -1511,78 +1506,57 @@ class Particles:
     def restore_z(self):
         check(self.lib.odr_particles_restore_z(self.ctx.h, self.h))
 
+    def _counters(self, symbol, keys):
+        """One uint64 per key from a diagnostics entry point (ctx, particles, uint64 *out)."""
+        out = (C.c_uint64 * len(keys))()
+        check(getattr(self.lib, symbol)(self.ctx.h, self.h, out))
+        return dict(zip(keys, map(int, out)))
+
     def tile_stats(self):
         """Diagnostics of the LDS-tile step (odr_particles_tile_stats): launches on that path, elements they handed to the
         HBM path, rectangles cut to the LDS capacity, workgroup ranges of the current table."""
-        import ctypes as C
-        out = (C.c_uint64 * 4)()
-        check(self.lib.odr_particles_tile_stats(self.ctx.h, self.h, out))
-        return dict(launches=int(out[0]), handed_over=int(out[1]), rectangles_cut=int(out[2]), ranges=int(out[3]))
+        return self._counters('odr_particles_tile_stats', ('launches', 'handed_over', 'rectangles_cut', 'ranges'))
 
     def step_layout_stats(self):
         """Launches of the fused step kernel (odr_particles_step_layout_stats): `static` with the C3 group's compile-time
         layout between two time levels, `runtime` all others (the run-time slot layout, and the on-level static layout
         that step_onlevel_stats counts on its own)."""
-        import ctypes as C
-        out = (C.c_uint64 * 2)()
-        check(self.lib.odr_particles_step_layout_stats(self.ctx.h, self.h, out))
-        return dict(runtime=int(out[0]), static=int(out[1]))
+        return self._counters('odr_particles_step_layout_stats', ('runtime', 'static'))
 
     def step_onlevel_stats(self):
         """Launches of the fused step kernel with the C3 group's compile-time layout on a step whose time sits on a reader
         level (odr_particles_step_onlevel_stats)."""
-        import ctypes as C
-        out = (C.c_uint64 * 1)()
-        check(self.lib.odr_particles_step_onlevel_stats(self.ctx.h, self.h, out))
-        return int(out[0])
+        return self._counters('odr_particles_step_onlevel_stats', ('launches',))['launches']
 
     def vmix_layout_stats(self):
         """Launches of the mixing kernels (odr_particles_vmix_layout_stats): the K-column kernel with the run-time configuration,
         with C3's compile-time one, and the other mixing kernels."""
-        import ctypes as C
-        out = (C.c_uint64 * 3)()
-        check(self.lib.odr_particles_vmix_layout_stats(self.ctx.h, self.h, out))
-        return dict(runtime=int(out[0]), static=int(out[1]), other=int(out[2]))
+        return self._counters('odr_particles_vmix_layout_stats', ('runtime', 'static', 'other'))
 
     def vmix_kplane_stats(self):
         """Where the K-column / window mixing launches gathered the diffusivity from (odr_particles_vmix_kplane_stats): the
         levels' K planes, or the node records."""
-        import ctypes as C
-        out = (C.c_uint64 * 2)()
-        check(self.lib.odr_particles_vmix_kplane_stats(self.ctx.h, self.h, out))
-        return dict(planes=int(out[0]), records=int(out[1]))
+        return self._counters('odr_particles_vmix_kplane_stats', ('planes', 'records'))
 
     def vmix_window_stats(self):
         """The static 12-level K-column launches (odr_particles_vmix_window_stats): those that gathered two K quads per
         particle, those that gathered the whole column, and the elements the two-quad launches redid on the whole column."""
-        import ctypes as C
-        out = (C.c_uint64 * 3)()
-        check(self.lib.odr_particles_vmix_window_stats(self.ctx.h, self.h, out))
-        return dict(windowed=int(out[0]), full=int(out[1]), redone=int(out[2]))
+        return self._counters('odr_particles_vmix_window_stats', ('windowed', 'full', 'redone'))
 
     def vmix_skip_stats(self):
         """The tiled K-column launches (odr_particles_vmix_skip_stats) and the elements they skipped at the surface: z == 0
         on entry with no mixing and no vertical advection at the surface, for which the launch stores z = +0.0 anyway."""
-        import ctypes as C
-        out = (C.c_uint64 * 2)()
-        check(self.lib.odr_particles_vmix_skip_stats(self.ctx.h, self.h, out))
-        return dict(launches=int(out[0]), skipped=int(out[1]))
+        return self._counters('odr_particles_vmix_skip_stats', ('launches', 'skipped'))
 
     def vmix_dense_stats(self):
         """The dense mixing launches (odr_particles_vmix_dense_stats: the compaction over the whole launch, static
         configurations whose settings allow the skip) and the elements their lists held."""
-        import ctypes as C
-        out = (C.c_uint64 * 2)()
-        check(self.lib.odr_particles_vmix_dense_stats(self.ctx.h, self.h, out))
-        return dict(launches=int(out[0]), listed=int(out[1]))
+        return self._counters('odr_particles_vmix_dense_stats', ('launches', 'listed'))
 
     def vmix_keep_stats(self):
         """Where the dense mixing launches took their keep ballots from (odr_particles_vmix_keep_stats): the step launch that
         ran right before, or k_vmix_keep's own pass; and the lists that held every element (not filled)."""
-        import ctypes as C
-        out = (C.c_uint64 * 3)()
-        check(self.lib.odr_particles_vmix_keep_stats(self.ctx.h, self.h, out))
-        return dict(from_step=int(out[0]), from_keep=int(out[1]), identity=int(out[2]))
+        return self._counters('odr_particles_vmix_keep_stats', ('from_step', 'from_keep', 'identity'))
 
     def reduce_global(self, combine, wind_drift_depth=0.1, relative_wind=False):
         """Sharded run: this set's raw reductions -> combine(raw16) over the ranks (counts summed, maxima maximised) ->
@@ -1606,10 +1580,7 @@ class Particles:
 
     @staticmethod
     def reduction_dict(raw):
-        keys = ['n_active', 'lon_min', 'lon_max', 'lat_min', 'lat_max', 'z_min', 'z_max', 'D_max',
-                'stokes_sum_max', 'wind_speed_max', 'wdf_surface_max', 'n_surface', 'hs_max', 'tp_max', 'rel_wind_speed_max',
-                'mld_max']
-        d = dict(zip(keys, raw))
+        d = dict(zip(REDUCTION_KEYS, raw))
         for k in ('lon_min', 'lat_min', 'z_min'):
             d[k] = -d[k]
         return d
@@ -1628,10 +1599,7 @@ class Particles:
     def reduce_scalars(self, wind_drift_depth=0.1):
         out = np.empty(16)
         check(self.lib.odr_reduce_scalars(self.ctx.h, self.h, float(wind_drift_depth), out.ctypes.data_as(_dp)))
-        keys = ['n_active', 'lon_min', 'lon_max', 'lat_min', 'lat_max', 'z_min', 'z_max', 'D_max',
-                'stokes_sum_max', 'wind_speed_max', 'wdf_surface_max', 'n_surface', 'hs_max', 'tp_max', 'rel_wind_speed_max',
-                'mld_max']
-        return dict(zip(keys, out))
+        return dict(zip(REDUCTION_KEYS, out))
 
 
 _SLOW_MS = float(os.environ.get('ODR_SLOW_CALLS', 0) or 0)
@@ -1691,8 +1659,26 @@ for _name in ('download', 'download_f32', 'env_download', 'get_property', 'reduc
     setattr(Particles, _name, _reading(getattr(Particles, _name)))
 
 
-class ShipTable:
+class _Handle:
+    """A device object of a context behind `ptr`, released by the library's DESTROY(ctx, ptr) -- by close(), or with the last
+    reference as long as the context is still open."""
+    DESTROY = None
+
+    def close(self):
+        if self.ptr and self.ctx.h:
+            getattr(self.ctx.lib, self.DESTROY)(self.ctx.h, self.ptr)
+        self.ptr = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class ShipTable(_Handle):
     """Device copy of ShipDrift's class tables (odr_ship_table_create / _destroy)."""
+    DESTROY = 'odr_ship_table_destroy'
 
     def __init__(self, ctx, table):
         t = np.ascontiguousarray(table, dtype=np.float64)
@@ -1704,21 +1690,12 @@ class ShipTable:
         check(ctx.lib.odr_ship_table_classes(self.ptr, C.byref(n)))
         self.n_classes = n.value      # (the library keeps the count with the table)
 
-    def close(self):
-        if self.ptr and self.ctx.h:
-            self.ctx.lib.odr_ship_table_destroy(self.ctx.h, self.ptr)
-        self.ptr = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class UMesh:
+class UMesh(_Handle):
     """Device image of a triangular mesh (odr_umesh_create / _destroy): the search indices over the nodes and the face centres,
     the box of the nodes, the sigma and depth arrays, and up to three resident time levels."""
+    DESTROY = 'odr_umesh_destroy'
     SIGMA = ('siglay', 'siglev', 'siglay_center', 'siglev_center', 'h', 'h_center')
 
     def __init__(self, ctx, x, y, xc=None, yc=None, proj=None, **sigma):
@@ -1766,21 +1743,12 @@ class UMesh:
         check(self.ctx.lib.odr_umesh_nearest(self.ctx.h, self.ptr, int(bool(on_faces)), len(x), px, py, out.ctypes.data_as(_ip)))
         return out
 
-    def close(self):
-        if self.ptr and self.ctx.h:
-            self.ctx.lib.odr_umesh_destroy(self.ctx.h, self.ptr)
-        self.ptr = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class Shape:
+class Shape(_Handle):
     """Device image of coastline polygons (odr_shape_create / _destroy): the uniform grid over the box of the rings and the
     per-cell lists of edges and corner toggles."""
+    DESTROY = 'odr_shape_destroy'
     STATS = ('cells', 'entries', 'longest_list', 'mean_list', 'nudges', 'bytes', 'nx', 'ny')
 
     def __init__(self, ctx, x1, y1, x2, y2, poly, n_polygons, proj=None, invert=False, nx=0, ny=0):
@@ -1808,20 +1776,11 @@ class Shape:
         check(self.ctx.lib.odr_shape_stats(self.ctx.h, self.ptr, a.ctypes.data_as(_dp)))
         return dict(zip(self.STATS, a.tolist()))
 
-    def close(self):
-        if self.ptr and self.ctx.h:
-            self.ctx.lib.odr_shape_destroy(self.ctx.h, self.ptr)
-        self.ptr = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
-class Combined:
+class Combined(_Handle):
     """The flattened program of a reader expression (odr_combined_create / _destroy; csrc/odr_combine.hip.h)."""
+    DESTROY = 'odr_combined_destroy'
 
     def __init__(self, ctx, ops):
         ops = list(ops)
@@ -1834,16 +1793,6 @@ class Combined:
         self.ctx, self.ptr = ctx, C.c_void_p()
         check(ctx.lib.odr_combined_create(ctx.h, len(ops), arr, C.byref(self.ptr)))
 
-    def close(self):
-        if self.ptr and self.ctx.h:
-            self.ctx.lib.odr_combined_destroy(self.ctx.h, self.ptr)
-        self.ptr = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def weathering_table(oil, sea_water_density):
@@ -1887,8 +1836,9 @@ def weathering_table(oil, sea_water_density):
     return t
 
 
-class RadioSetup:
+class RadioSetup(_Handle):
     """Device copy of RadionuclideDrift's species setup with the counters ntransformations (odr_radio_create / _destroy)."""
+    DESTROY = 'odr_radio_destroy'
     SPECIES = ('lmm', 'lmmcation', 'lmmanion', 'polymer', 'particle_rev', 'sediment_rev', 'particle_slow', 'sediment_slow',
                'particle_irrev', 'sediment_irrev')
 
@@ -1919,16 +1869,6 @@ class RadioSetup:
         check(self.ctx.lib.odr_radio_counts(self.ctx.h, self.ptr, c.ctypes.data_as(C.POINTER(C.c_int64)), int(bool(reset))))
         return c.reshape(_abi.RADIO_MAX_SPECIES, _abi.RADIO_MAX_SPECIES)[:self.nspecies, :self.nspecies].copy()
 
-    def close(self):
-        if self.ptr and self.ctx.h:
-            self.ctx.lib.odr_radio_destroy(self.ctx.h, self.ptr)
-        self.ptr = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class History:
