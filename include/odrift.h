@@ -1183,6 +1183,48 @@ int odr_umesh_nearest(odr_ctx *ctx, odr_umesh *mesh, int on_faces, int64_t n, co
  * that came later (waits for it) */
 int odr_umesh_last_kernel_ms(odr_ctx *ctx, float *ms);
 
+/* ---------------------------------------------------------------- SCHISM-style mesh reader (three-node inverse-distance mean)
+ * The reference's reader_schism_native (readers/reader_schism_native.py): a time level is a cloud of points -- the nodes for a 2-D
+ * variable, node x vertical level at the level's own zcor for a 3-D one -- and a value is the inverse-distance mean over the
+ * THREE nearest points of that cloud (ReaderBlockUnstruct.interpolate :982-1056), blended linearly between the two time levels
+ * that bracket the time (:614-642).  The searches are exact and use one 2-D index for both kinds of cloud (csrc/odr_schism.hip.h,
+ * DESIGN.md 8p).
+ * odr_schism_create: x, y [n_nodes] host float64 in the mesh's own coordinates (proj; NULL: geographic); n_levels: vertical levels
+ * of the 3-D variables (0: none); hull_x, hull_y [n_hull]: the vertices of the convex hull of the nodes in ring order -- coverage
+ * is strict inclusion in that ring by odr_shape's predicate.  ODR_ERR_INVALID: fewer than 3 nodes or hull vertices, a position
+ * that is not finite, more than 128 levels, ODR_PROJ_OB_TRAN / ODR_PROJ_CURVILINEAR.  odr_schism_destroy waits for the context's
+ * stream. */
+typedef struct odr_schism odr_schism;
+int odr_schism_create(odr_ctx *ctx, const odr_proj_desc *proj, int32_t n_nodes, const double *x, const double *y, int32_t n_levels,
+                      int32_t n_hull, const double *hull_x, const double *hull_y, odr_schism **out);
+int odr_schism_destroy(odr_ctx *ctx, odr_schism *mesh);
+/* The vertical coordinate of the time level in `slot` (0 .. 3): zcor [n_nodes][n_levels] host float32, negative down, NaN for the
+ * levels below the sea bed of a node.  Synchronous.  ODR_ERR_INVALID: a slot outside 0 .. 3, a mesh without levels, fewer than
+ * three finite entries. */
+int odr_schism_set_zcor(odr_ctx *ctx, odr_schism *mesh, int32_t slot, double t_epoch, const float *zcor);
+/* Variable var_id (ODR_VAR_*) of the time level in `slot`: host float32 [n_nodes] (n_levels 0) or [n_nodes][n_levels] (n_levels =
+ * the mesh's).  Synchronous.  ODR_ERR_INVALID: a slot outside 0 .. 3, another level count. */
+int odr_schism_set_level(odr_ctx *ctx, odr_schism *mesh, int32_t slot, double t_epoch, int32_t var_id, int32_t n_levels, const float *data);
+/* For every element of the particle set, in ONE launch: lonlat2xy; the hull test; the three nearest nodes if a 2-D variable is
+ * asked; the three nearest points of the cloud of each time level if a 3-D variable is asked; per variable
+ * (fac * data).sum / fac.sum with fac = 1 / max(distance, 1e-10) in float64 at either level and before * (1 - w) + after * w;
+ * x / y vector pairs rotated from the mesh's CRS to east / north unless it is geographic; the merge into the element's
+ * environment slot as odr_umesh_sample does it.  slot_after < 0: the values of slot_before alone.  nvars: 1 .. 8.  Enqueued on
+ * the context's stream.  ODR_ERR_INVALID: a slot outside 0 .. 3, w outside 0 .. 1, nvars outside 1 .. 8, a variable id given
+ * twice; ODR_ERR_STATE: a level does not hold one of the variables, or a 3-D variable's level is without zcor. */
+int odr_schism_sample(odr_ctx *ctx, odr_particles *p, odr_schism *mesh, int32_t slot_before, int32_t slot_after, double w, int32_t nvars,
+                      const int32_t *var_ids, const int32_t *first_flags);
+/* The bare query (tests, tools/bench_schism.py): the three nearest points of (x[i], y[i]) among the nodes (z NULL), or of
+ * (x[i], y[i], z[i]) among node x level at the zcor of `slot`, ascending: idx_out [n][3] (the node; for a 3-D query the position in
+ * the flattened [node][level] array with the NaN entries removed, as the reference numbers its cloud), dist_out [n][3] =
+ * sqrt((dx dx + dy dy) + dz dz) in float64 without contraction; exact.  -1 / inf for a point that is not finite.  visits_out [n]
+ * (may be NULL): tree nodes whose distance was formed.  Host arrays.  Synchronous. */
+int odr_schism_nearest3(odr_ctx *ctx, odr_schism *mesh, int32_t slot, int64_t n, const double *x, const double *y, const double *z,
+                        int64_t *idx_out, double *dist_out, int32_t *visits_out);
+/* device time [ms] of the launches of this context's last odr_schism_nearest3, or of the launch of its last odr_schism_sample if
+ * that came later (waits for it) */
+int odr_schism_last_kernel_ms(odr_ctx *ctx, float *ms);
+
 /* ---------------------------------------------------------------- coastline polygons (shape reader)
  * The reference's reader_shape.Reader (readers/reader_shape.py): land_binary_mask = shapely.contains_xy(unary_union(polys), x, y),
  * here an exact crossing-number test behind a uniform grid whose cost per point is the local density of edges

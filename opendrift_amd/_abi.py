@@ -290,6 +290,13 @@ _SIGNATURES = {
     'odr_umesh_sample': [_vp, _vp, _vp, C.c_int32, C.c_int32, _ip, _ip],
     'odr_umesh_nearest': [_vp, _vp, C.c_int, C.c_int64, _dp, _dp, _ip],
     'odr_umesh_last_kernel_ms': [_vp, _fp],
+    'odr_schism_create': [_vp, _P(ProjDesc), C.c_int32, _dp, _dp, C.c_int32, C.c_int32, _dp, _dp, _P(_vp)],
+    'odr_schism_destroy': [_vp, _vp],
+    'odr_schism_set_zcor': [_vp, _vp, C.c_int32, C.c_double, _fp],
+    'odr_schism_set_level': [_vp, _vp, C.c_int32, C.c_double, C.c_int32, C.c_int32, _fp],
+    'odr_schism_sample': [_vp, _vp, _vp, C.c_int32, C.c_int32, C.c_double, C.c_int32, _ip, _ip],
+    'odr_schism_nearest3': [_vp, _vp, C.c_int32, C.c_int64, _dp, _dp, _dp, _P(C.c_int64), _dp, _ip],
+    'odr_schism_last_kernel_ms': [_vp, _fp],
     'odr_shape_create': [_vp, _P(ProjDesc), C.c_int64, _dp, _dp, _dp, _dp, _ip, C.c_int32, C.c_int32, C.c_int32, C.c_int, _P(_vp)],
     'odr_shape_destroy': [_vp, _vp],
     'odr_shape_sample': [_vp, _vp, _vp, C.c_int],
@@ -302,6 +309,7 @@ _SIGNATURES = {
     'odr_combined_last_kernel_ms': [_vp, _fp],
 }
 UMESH_MAX_VARIABLES, UMESH_LEVELS = 8, 3      # odr_umesh_sample, odr_umesh_set_level
+SCHISM_LEVELS, SCHISM_MAX_VERTICAL = 4, 128   # odr_schism_set_level, odr_schism_create (UMESH_MAXSIGMA)
 EXPORTS = sorted(list(_SIGNATURES) + ['odr_last_error', 'odr_version'])
 
 _lib = None

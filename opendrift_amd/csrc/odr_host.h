@@ -83,7 +83,8 @@ struct KernelClock {
     return 0;
   }
 };
-enum { CLOCK_DENSITY, CLOCK_CONC, CLOCK_FTLE, CLOCK_TRAJ_LENGTHS, CLOCK_POLYGON_POINTS, CLOCK_UMESH, CLOCK_SHAPE, CLOCK_COMBINED, N_CLOCKS };
+enum { CLOCK_DENSITY, CLOCK_CONC, CLOCK_FTLE, CLOCK_TRAJ_LENGTHS, CLOCK_POLYGON_POINTS, CLOCK_UMESH, CLOCK_SHAPE, CLOCK_COMBINED, CLOCK_SCHISM,
+       N_CLOCKS };
 
 // Device arrays that live as long as the scope does: the temporaries of a call, the arrays a handle owns
 struct DevScope {

@@ -705,6 +705,13 @@ class Context:
     def umesh_last_kernel_ms(self):
         return self._last_kernel_ms('odr_umesh_last_kernel_ms')
 
+    def schism(self, x, y, hull_x, hull_y, n_levels=0, proj=None):
+        """The device image of a SCHISM-style mesh (odr_schism_create): SchismMesh."""
+        return SchismMesh(self, x, y, hull_x, hull_y, n_levels=n_levels, proj=proj)
+
+    def schism_last_kernel_ms(self):
+        return self._last_kernel_ms('odr_schism_last_kernel_ms')
+
     def shape(self, x1, y1, x2, y2, poly, n_polygons, proj=None, invert=False, nx=0, ny=0):
         """The device image of coastline polygons (odr_shape_create): Shape."""
         return Shape(self, x1, y1, x2, y2, poly, n_polygons, proj=proj, invert=invert, nx=nx, ny=ny)
@@ -847,6 +854,17 @@ class Particles:
             raise ValueError('%d variables and %d first flags' % (len(ids), len(first)))
         fl, pf = _i([int(bool(f)) for f in first])
         check(self.lib.odr_umesh_sample(self.ctx.h, self.h, mesh.ptr, int(slot), len(ids), pi, pf))
+
+    def schism_sample(self, mesh, slot_before, slot_after, w, variables, first):
+        """The inverse-distance mean over the three nearest points of the mesh's resident levels at every element, blended as
+        before * (1 - w) + after * w (slot_after None: the level `slot_before` alone), merged into the environment slots in one
+        launch (odr_schism_sample): a finite value is taken where first[k] or where the slot holds nothing finite."""
+        ids, pi = _i([self.ctx._vid(v) for v in variables])
+        if len(first) != len(ids):
+            raise ValueError('%d variables and %d first flags' % (len(ids), len(first)))
+        fl, pf = _i([int(bool(f)) for f in first])
+        check(self.lib.odr_schism_sample(self.ctx.h, self.h, mesh.ptr, int(slot_before), -1 if slot_after is None else int(slot_after),
+                                         float(w), len(ids), pi, pf))
 
     def shape_sample(self, shape, first):
         """land_binary_mask of the polygons at every element, merged into the environment slot in one launch (odr_shape_sample):
@@ -1628,7 +1646,7 @@ def _touching(fn):
     return wrapper
 
 
-for _name in ('append', 'upload', 'env_sample', 'umesh_sample', 'shape_sample', 'combined_sample', 'env_upload', 'env_add_noise', 'advect', 'env_coast_advect',
+for _name in ('append', 'upload', 'env_sample', 'umesh_sample', 'schism_sample', 'shape_sample', 'combined_sample', 'env_upload', 'env_add_noise', 'advect', 'env_coast_advect',
               'update_positions', 'advect_wind', 'stokes_drift', 'advect_sea_ice', 'set_property', 'leeway_capsize', 'leeway', 'hdiffusion', 'movers',
               'vmix', 'vmix_analytic', 'vmix_oil', 'vertical_advection', 'vertical_buoyancy', 'coastline', 'coastline_crossing',
               'increase_age', 'deactivate_missing', 'remap_status', 'seafloor', 'deactivate', 'deactivate_outside', 'compact',
@@ -1742,6 +1760,56 @@ class UMesh(_Handle):
         out = np.empty(len(x), np.int32)
         check(self.ctx.lib.odr_umesh_nearest(self.ctx.h, self.ptr, int(bool(on_faces)), len(x), px, py, out.ctypes.data_as(_ip)))
         return out
+
+
+
+class SchismMesh(_Handle):
+    """Device image of a SCHISM-style mesh (odr_schism_create / _destroy): the search index over the nodes, the grid over the
+    ring of their convex hull, and up to four resident time levels -- zcor [nodes, levels] and the variables' planes."""
+    DESTROY = 'odr_schism_destroy'
+
+    def __init__(self, ctx, x, y, hull_x, hull_y, n_levels=0, proj=None):
+        (x, px), (y, py) = _d(np.ravel(x)), _d(np.ravel(y))
+        (hx, phx), (hy, phy) = _d(np.ravel(hull_x)), _d(np.ravel(hull_y))
+        if len(x) != len(y) or len(hx) != len(hy):
+            raise ValueError('%d x and %d y node coordinates, %d x and %d y hull vertices' % (len(x), len(y), len(hx), len(hy)))
+        self.n_nodes, self.n_levels = len(x), int(n_levels)
+        pd = proj_desc(proj)
+        self.ctx, self.ptr = ctx, C.c_void_p()
+        check(ctx.lib.odr_schism_create(ctx.h, None if pd is None else C.byref(pd), self.n_nodes, px, py, self.n_levels, len(hx), phx, phy,
+                                        C.byref(self.ptr)))
+
+    def set_zcor(self, slot, t_epoch, zcor):
+        """The vertical coordinate of the time level in `slot`: [nodes, levels] float32, NaN below the sea bed."""
+        zcor = np.ascontiguousarray(zcor, dtype=np.float32)
+        if zcor.shape != (self.n_nodes, self.n_levels) or not self.n_levels:      # the library reads the whole array
+            raise ValueError('zcor of shape %s on a mesh of %d nodes and %d levels' % (zcor.shape, self.n_nodes, self.n_levels))
+        check(self.ctx.lib.odr_schism_set_zcor(self.ctx.h, self.ptr, int(slot), float(t_epoch), zcor.ctypes.data_as(_fp)))
+
+    def set_level(self, slot, t_epoch, variable, data):
+        """One variable of one time level becomes resident in `slot`: data [nodes] or [nodes, levels] float32."""
+        data = np.ascontiguousarray(data, dtype=np.float32)
+        if data.shape not in ((self.n_nodes,), (self.n_nodes, self.n_levels)):
+            raise ValueError('%s of shape %s on a mesh of %d nodes and %d levels' % (variable, data.shape, self.n_nodes, self.n_levels))
+        check(self.ctx.lib.odr_schism_set_level(self.ctx.h, self.ptr, int(slot), float(t_epoch), self.ctx._vid(variable),
+                                                data.shape[1] if data.ndim == 2 else 0, data.ctypes.data_as(_fp)))
+
+    def nearest3(self, x, y, z=None, slot=0, visits=False):
+        """(idx [n, 3] int64, dist [n, 3]) of the three nearest points of each (x, y) among the nodes, or of each (x, y, z) among
+        node x level at the zcor of `slot`, ascending (odr_schism_nearest3); -1 / inf for a point that is not finite.
+        visits=True: also the tree nodes each query formed a distance to."""
+        (x, px), (y, py) = _d(np.ravel(x)), _d(np.ravel(y))
+        if len(x) != len(y):
+            raise ValueError('%d x and %d y' % (len(x), len(y)))
+        pz = None
+        if z is not None:
+            z, pz = _d(np.ravel(z))
+            if len(z) != len(x):
+                raise ValueError('%d x and %d z' % (len(x), len(z)))
+        idx, dist, seen = np.empty((len(x), 3), np.int64), np.empty((len(x), 3)), np.empty(len(x), np.int32)
+        check(self.ctx.lib.odr_schism_nearest3(self.ctx.h, self.ptr, int(slot), len(x), px, py, pz, idx.ctypes.data_as(C.POINTER(C.c_int64)),
+                                               dist.ctypes.data_as(_dp), seen.ctypes.data_as(_ip) if visits else None))
+        return (idx, dist, seen) if visits else (idx, dist)
 
 
 

@@ -1064,7 +1064,7 @@ class OpenDriftSimulation(Configurable):
     def _unbound_off_list_readers(self):
         """Readers added but not bound yet (no device context so far) that will be among _host_bindings()."""
         return [n for n, (r, _) in self._readers_host.items() if n not in self.readers and n not in self.discarded_readers and
-                (getattr(r, 'device_kind', None) in ('umesh', 'shape', 'combined') or
+                (getattr(r, 'device_kind', None) in ('umesh', 'schism', 'shape', 'combined') or
                  (getattr(r, 'device_kind', None) is None and isinstance(r, ContinuousReader)))]
 
     def _check_reader_expressions(self):
@@ -1089,7 +1089,7 @@ class OpenDriftSimulation(Configurable):
                                           'vertical mixing: a combined reader yields no vertical profiles (the reference\'s does not '
                                           'forward them either)' % r.name)
         sources = {id(r): r for _, (r, _) in self._readers_host.items()
-                   if getattr(r, 'device_kind', None) not in ('combined', 'umesh', 'shape') and
+                   if getattr(r, 'device_kind', None) not in ('combined', 'umesh', 'schism', 'shape') and
                    not (getattr(r, 'device_kind', None) is None and isinstance(r, ContinuousReader))}
         sources.update(leaves)
         if len(sources) > 16:
@@ -1615,6 +1615,18 @@ class OpenDriftSimulation(Configurable):
         if self._world > 1 and any(getattr(r, 'device_kind', None) == 'umesh' for r, _ in self._readers_host.values()):
             raise NotImplementedError('an UnstructuredReader in a sharded run: its time levels are not broadcast to the ranks '
                                       '(DESIGN.md section 8k)')
+        for name, (r, _) in self._readers_host.items():
+            if getattr(r, 'device_kind', None) != 'schism':
+                continue
+            if self._world > 1:
+                raise NotImplementedError('SchismReader %s in a sharded run: its time levels are not broadcast to the ranks '
+                                          '(DESIGN.md section 8p)' % r.name)
+            mixing = 'drift:vertical_mixing' in self._config and self.get_config('drift:vertical_mixing') and \
+                self.get_config('vertical_mixing:diffusivitymodel') == 'environment'
+            if mixing and name in self.priority_list.get('ocean_vertical_diffusivity', []):
+                raise NotImplementedError('SchismReader %s would be the source of the ocean_vertical_diffusivity profiles of vertical '
+                                          'mixing: vertical profiles from this reader are not built (not functional in the reference '
+                                          'either, reader_schism_native.py:1046-1049)' % r.name)
         if self._world > 1 and any(getattr(r, 'device_kind', None) == 'shape' for r, _ in self._readers_host.values()):
             raise NotImplementedError('a ShapeReader in a sharded run: the model samples it outside the launch a sharded step is '
                                       '(DESIGN.md section 8l)')

@@ -852,6 +852,237 @@ class UnstructuredReader(BaseReader):
         return out
 
 
+class SchismReader(BaseReader):
+    """In-memory reader on a triangular mesh that INTERPOLATES, the reference's reader for SCHISM output
+    (readers/reader_schism_native.py): every time level is a cloud of points -- the nodes for a 2-D variable, node x vertical level
+    at the level's own `zcor` for a 3-D one -- a value is the inverse-distance mean over the three nearest points of that cloud
+    (ReaderBlockUnstruct.interpolate, :982-1056), and the values of the two time levels that bracket the time are blended
+    linearly (:614-642).
+
+    x, y [N]: node coordinates in the mesh's CRS (`proj4`; None: geographic, as the reference assumes).  node_arrays: {variable:
+    [nt, N] | [N] (static) | [nt, N, L] (3-D, SCHISM's own axis order)}; zcor [nt, N, L]: the vertical coordinate, negative down,
+    NaN or masked for the levels below the sea bed of a node, +-inf becomes 15.0 (:942-943).  All are kept as float32, which is
+    what model files hold; NaN or masked data is no data, and a NaN neighbour makes the mean NaN (a dry node in the reference).
+
+    use_3d follows :129-143 and :246-248: None means 3-D when a 3-D array and zcor are given; 3-D without zcor raises the
+    reference's ValueError; a geographic mesh switches it off (metres and degrees do not mix in one distance), and 3-D arrays are
+    then refused: the caller gives depth-averaged ones.
+
+    Coverage is strict inclusion in the convex hull of the nodes (basereader/unstructured.py:76-144), tested with ShapeReader's
+    crossing rule; the reference tests with shapely, so a point exactly ON the hull's edge may fall on the other side here.
+
+    On the device (`device_kind = 'schism'`) a whole get_environment call -- projection, hull test, the exact three-nearest search
+    in 2-D and per time level in 3-D, weights, time blend, rotation of vector pairs, merge by priority -- is one launch
+    (odr_schism_sample).  `get_variables_interpolated` answers on the host with scipy's cKDTree and NumPy, written
+    from the reference's expressions; it needs no device.
+
+    Refused by name: land_binary_mask (the reference's branch for it calls a class that does not exist, :996; ShapeReader serves
+    the land mask), +proj=ob_tran, set_convolution_kernel (the reference's __convolve_block__ convolves node lists as if they
+    were images), ensemble lists, more than 128 vertical levels.  The valid range of a standard name (:632-642) is not applied:
+    no reader of this package applies one."""
+    device_kind = 'schism'
+    STATIC_VARIABLES = ('sea_floor_depth_below_sea_level', 'land_binary_mask')      # :478
+
+    def __init__(self, x, y, times, node_arrays, zcor=None, proj4=None, use_3d=None, name='schism_reader'):
+        self.proj4 = '+proj=latlong' if proj4 is None else proj4
+        self.name = name
+        pd = projection.parse_proj4(self.proj4)        # NotImplementedError: not on the device path
+        if pd.get('kind') == 'ob_tran':
+            raise NotImplementedError('a mesh on a rotated pole (+proj=ob_tran) is not on the device path')
+        self.x, self.y = (np.ascontiguousarray(a, dtype=np.float64).ravel() for a in (x, y))
+        N = len(self.x)
+        if len(self.y) != N:
+            raise ValueError('%d x and %d y node coordinates' % (N, len(self.y)))
+        if N < 3:
+            raise ValueError('a mesh of %d nodes: a value is the mean over the three nearest' % N)
+        if not (np.isfinite(self.x).all() and np.isfinite(self.y).all()):
+            raise ValueError('a mesh coordinate is not finite')
+        self.xmin, self.xmax, self.ymin, self.ymax = float(self.x.min()), float(self.x.max()), float(self.y.min()), float(self.y.max())
+        self.times = list(times) if times is not None else []
+        if not self.times:
+            raise ValueError('times must hold at least one time level')
+        if any(b <= a for a, b in zip(self.times, self.times[1:])):
+            raise ValueError('times must increase')
+        self.start_time, self.end_time = self.times[0], self.times[-1]
+        self.time_step = (self.times[1] - self.times[0]) if len(self.times) > 1 else None
+        nt = len(self.times)
+        self.node_arrays = {}
+        for v, a in (node_arrays or {}).items():
+            if v == 'land_binary_mask':
+                raise NotImplementedError('land_binary_mask on a SCHISM mesh: the reference interpolates it with a class that does not '
+                                          'exist (Nearest2DInterpolator); ShapeReader serves the land mask')
+            if isinstance(a, (list, tuple)):
+                raise NotImplementedError('ensemble members (%s) on a SCHISM mesh are not built' % v)
+            a = np.ascontiguousarray(np.ma.filled(np.ma.asarray(a, dtype=np.float32), np.nan), dtype=np.float32)
+            if not (a.shape == (N,) or (a.ndim in (2, 3) and a.shape[:2] == (nt, N))):
+                raise ValueError('variable %s of shape %s: expected [%d], [%d, %d] or [%d, %d, levels]' % (v, a.shape, N, nt, N, nt, N))
+            self.node_arrays[v] = a
+        levels = sorted({a.shape[2] for a in self.node_arrays.values() if a.ndim == 3})
+        if len(levels) > 1:
+            raise ValueError('the 3-D variables disagree on the number of vertical levels: %s' % levels)
+        self.n_levels = levels[0] if levels else 0
+        if self.n_levels > _abi.SCHISM_MAX_VERTICAL:
+            raise NotImplementedError('%d vertical levels: the device columns hold at most %d (UMESH_MAXSIGMA)' % (self.n_levels, _abi.SCHISM_MAX_VERTICAL))
+        three_d = [v for v, a in self.node_arrays.items() if a.ndim == 3]
+        self.use_3d = use_3d
+        if self.use_3d is None:      # :129-134
+            self.use_3d = bool(three_d) and zcor is not None
+        if self.use_3d and three_d and zcor is None:      # :136-143
+            raise ValueError('variable zcor must be present to be able to use 3D currents')
+        self.geographic = pd.get('kind', 'latlong') == 'latlong' or not (self.x > 360.).any()      # :246; a latlong proj4 decides too
+        if self.geographic and self.use_3d:      # :246-248
+            self.use_3d = False
+        if three_d and not self.use_3d:
+            raise NotImplementedError('3-D variables %s on a reader that does not use 3-D data (%s): give depth-averaged [nt, N] arrays'
+                                      % (sorted(three_d), 'a geographic mesh: metres and degrees do not make one distance'
+                                         if self.geographic else 'use_3d is off, or zcor is missing'))
+        self.zcor = None
+        if self.use_3d and three_d:
+            z = np.array(np.ma.filled(np.ma.asarray(zcor, dtype=np.float32), np.nan), dtype=np.float32, order='C')
+            if z.shape != (nt, N, self.n_levels):
+                raise ValueError('zcor of shape %s: expected [%d, %d, %d]' % (z.shape, nt, N, self.n_levels))
+            z[np.isinf(z)] = np.float32(15.0)      # :942-943
+            short = [k for k in range(nt) if np.isfinite(z[k]).sum() < 3]
+            if short:
+                raise ValueError('time level %d of zcor holds fewer than three finite entries: a value is the mean over the three '
+                                 'nearest points' % short[0])
+            self.zcor = z
+        self.variables = list(self.node_arrays)
+        from scipy.spatial import ConvexHull      # Qhull, as the reference (_build_boundary_polygon_)
+        ring = ConvexHull(np.c_[self.x, self.y]).vertices
+        self.hull_x, self.hull_y = np.ascontiguousarray(self.x[ring]), np.ascontiguousarray(self.y[ring])
+        self._hull = ShapeReader([np.c_[self.hull_x, self.hull_y]], proj4_str=self.proj4)      # its crossing rule, its box
+        self._tree2, self._trees3 = None, {}
+        super().__init__()
+
+    nearest_time = UnstructuredReader.nearest_time
+    rotation_angle = UnstructuredReader.rotation_angle
+    modulate_longitude = UnstructuredReader.modulate_longitude
+
+    def set_convolution_kernel(self, convolve):
+        raise NotImplementedError('set_convolution_kernel on a SCHISM mesh: the reference\'s __convolve_block__ convolves node lists as '
+                                  'if they were images')
+
+    def levels_of(self, variable):
+        """Vertical levels of a variable's array (0: a 2-D variable); ValueError when the reader does not have it."""
+        if variable not in self.node_arrays:
+            raise ValueError('Variable not available: %s\nAvailable parameters are: %s' % (variable, self.variables))
+        a = self.node_arrays[variable]
+        return a.shape[2] if a.ndim == 3 else 0
+
+    def level(self, variable, k):
+        """The array of time level k: [N] or [N, L]."""
+        self.levels_of(variable)
+        a = self.node_arrays[variable]
+        return a if a.ndim == 1 else a[k]
+
+    def covers_positions(self, x, y):
+        """Strictly inside the convex hull of the nodes, by ShapeReader's rule; x + y not finite is outside."""
+        x, y = np.atleast_1d(np.asarray(x, dtype=np.float64)), np.atleast_1d(np.asarray(y, dtype=np.float64))
+        xmin, xmax, ymin, ymax = self._hull.box
+        with np.errstate(invalid='ignore'):
+            ok = np.isfinite(x + y) & (x >= xmin) & (x <= xmax) & (y >= ymin) & (y <= ymax)
+        if ok.any():
+            ok[ok] = self._hull.contains(x[ok], y[ok])
+        return ok
+
+    def cloud(self, k):
+        """(x_3d, y_3d, z_3d) of time level k: node x level flattened with the masked entries removed (convert_3d_to_array)."""
+        keep = ~np.isnan(self.zcor[k])
+        return np.repeat(self.x, self.n_levels).reshape(keep.shape)[keep], np.repeat(self.y, self.n_levels).reshape(keep.shape)[keep], \
+            self.zcor[k][keep]
+
+    def nearest3(self, x, y, z=None, k=0):
+        """(dist [n, 3], idx [n, 3]) of scipy's cKDTree.query(..., 3) over the nodes (z None) or over the cloud of time level k."""
+        from scipy.spatial import cKDTree
+        if z is None:
+            if self._tree2 is None:
+                self._tree2 = cKDTree(np.vstack((self.x, self.y)).T)
+            return self._tree2.query(np.vstack((x, y)).T, 3)
+        if k not in self._trees3:
+            if len(self._trees3) >= 4:
+                self._trees3.clear()
+            self._trees3[k] = cKDTree(np.vstack(self.cloud(k)).T)
+        return self._trees3[k].query(np.vstack((x, y, z)).T, 3)
+
+    def interpolate_level(self, variables, k, x, y, z):
+        """ReaderBlockUnstruct.interpolate for time level k: {variable: float64 values} at positions in mesh coordinates.  A
+        position or depth that is not finite has no neighbours: NaN."""
+        x, y, z = (np.asarray(a, dtype=np.float64) for a in (x, y, z))
+        out, found = {}, {}
+        for v in variables:
+            L = self.levels_of(v)
+            fin = np.isfinite(x + y + z) if L else np.isfinite(x + y)
+            if bool(L) not in found:
+                found[bool(L)] = self.nearest3(x[fin], y[fin], z[fin] if L else None, k)
+            dist, i = found[bool(L)]
+            dist = dist.copy()
+            dist[dist < 1.e-10] = 1.e-10
+            fac = 1. / dist
+            data = self.level(v, k)
+            if L:
+                data = data[~np.isnan(self.zcor[k])]
+            out[v] = np.full(len(x), np.nan)
+            out[v][fin] = (fac * data.take(i)).sum(-1) / fac.sum(-1)
+        return out
+
+    def get_variables_interpolated(self, variables, time, lon, lat, z, rotate=True):
+        """What the device launch gives an element with an empty slot, on the host: {variable: float32}; NaN outside the hull or
+        outside the time coverage; vector pairs rotated to east / north unless the mesh is geographic."""
+        lon, lat = np.atleast_1d(np.asarray(lon, dtype=np.float64)), np.atleast_1d(np.asarray(lat, dtype=np.float64))
+        n = len(lon)
+        variables = list(variables)
+        out = {v: np.full(n, np.nan, np.float32) for v in variables}
+        for v in variables:
+            self.levels_of(v)
+        if not self.covers_time(time):
+            return out
+        latlong = projection.parse_proj4(self.proj4).get('kind', 'latlong') == 'latlong'
+        x, y = (self.modulate_longitude(lon), lat) if latlong else self.lonlat2xy(lon, lat)
+        return self.get_variables(variables, time, x, y, z, rotate=rotate)
+
+    def get_variables(self, requested_variables, time=None, x=None, y=None, z=None, rotate=True):
+        """The same at positions x, y in the mesh's own coordinates (what a host-evaluated reader is asked)."""
+        variables = [requested_variables] if isinstance(requested_variables, str) else list(requested_variables)
+        x, y = np.atleast_1d(np.asarray(x, dtype=np.float64)), np.atleast_1d(np.asarray(y, dtype=np.float64))
+        n = len(x)
+        out = {v: np.full(n, np.nan, np.float32) for v in variables}
+        for v in variables:
+            self.levels_of(v)
+        time = self.start_time if time is None else time
+        if not self.covers_time(time):
+            return out
+        z = 0.0 if z is None else z
+        latlong = projection.parse_proj4(self.proj4).get('kind', 'latlong') == 'latlong'
+        ok = self.covers_positions(x, y)
+        if not ok.any():
+            return out
+        zz = np.broadcast_to(np.asarray(z, dtype=np.float64), (n,))[ok]
+        kb, ka, w = self.time_weight(time, variables)
+        env = self.interpolate_level(variables, kb, x[ok], y[ok], zz)
+        if ka is not None:
+            after = self.interpolate_level(variables, ka, x[ok], y[ok], zz)
+            # (a masked array from here on: __check_variable_array__ stores it as float32)
+            env = {v: (env[v] * (1 - w) + after[v] * w).astype(np.float32) for v in variables}
+        if rotate and not latlong:
+            for vx, vy in VECTOR_PAIRS_XY:
+                if vx in env and vy in env:
+                    rot = self.rotation_angle(x[ok], y[ok])
+                    u, w_ = env[vx], env[vy]
+                    env[vx], env[vy] = u * np.cos(rot) - w_ * np.sin(rot), u * np.sin(rot) + w_ * np.cos(rot)
+        for v in variables:
+            out[v][ok] = env[v]
+        return out
+
+    def time_weight(self, time, variables):
+        """(index before, index after or None, weight_after) of _get_variables_interpolated_ :472-481, :618-620: no blend at a
+        level exactly, with one level only, or when every requested variable is static."""
+        _, t_before, t_after, _, kb, ka = self.nearest_time(time)
+        if t_after is None or time == t_before or all(v in self.STATIC_VARIABLES for v in variables):
+            return kb, None, 0.0
+        return kb, ka, (time - t_before).total_seconds() / (t_after - t_before).total_seconds()
+
+
 def _polygon_rings(geom):
     """[[exterior, hole, ...], ...] of one entry of ShapeReader's `polygons`: an (n, 2) array, a pair (exterior, [holes]), or
     anything with the __geo_interface__ / GeoJSON shape of a Polygon or MultiPolygon (a Feature is unwrapped)."""
@@ -1220,6 +1451,8 @@ def check_device_expression(reader):
         dk = getattr(r, 'device_kind', None)
         if dk in ('umesh', 'shape'):
             raise NotImplementedError('reader expression %s: operators on a mesh or shape reader (%s) are not built' % (name, r.name))
+        if dk == 'schism':
+            raise NotImplementedError('reader expression %s: operators on a SchismReader (%s) are not built' % (name, r.name))
         if dk is None and isinstance(r, ContinuousReader):
             raise NotImplementedError('reader expression %s: leaf %s is a ContinuousReader evaluated on the host; the device '
                                       'program takes gridded, constant, analytic, landmask and timeseries readers' % (name, r.name))
@@ -1373,6 +1606,12 @@ class DeviceReaderBinding:
             self.mesh = ctx.umesh(reader.x, reader.y, reader.xc, reader.yc, proj=projection.parse_proj4(reader.proj4),
                                   **{k: getattr(reader, k) for k in ('siglay', 'siglev', 'siglay_center', 'siglev_center', 'h', 'h_center')})
             self.mesh_slots = {}     # time index -> slot of the mesh (at most three resident)
+        elif kind == 'schism':
+            # as an unstructured mesh: no source of the priority-list walk, sampled in a launch of its own behind it (sample_mesh)
+            self.sid = None
+            self.mesh = ctx.schism(reader.x, reader.y, reader.hull_x, reader.hull_y, n_levels=reader.n_levels if reader.zcor is not None else 0,
+                                   proj=projection.parse_proj4(reader.proj4))
+            self.mesh_slots = {}     # time index -> slot of the mesh (at most four resident)
         elif kind == 'shape':
             # coastline polygons: as a mesh, sampled in a launch of its own behind the priority-list walk (sample_shape)
             self.sid = None
@@ -1401,7 +1640,7 @@ class DeviceReaderBinding:
                     self.uniform.append(leaf)
         else:
             self.sid = None  # created with the first block (the grid comes with it)
-        if kind and kind not in ('umesh', 'shape', 'combined') and reader.start_time is not None:
+        if kind and kind not in ('umesh', 'schism', 'shape', 'combined') and reader.start_time is not None:
             ctx.set_time_coverage(self.sid, _epoch(reader.start_time), _epoch(reader.end_time), reader.always_valid)
 
     def _static_ids(self):
@@ -1609,6 +1848,8 @@ class DeviceReaderBinding:
         """The time levels NEAREST to the given instants become resident on the mesh: at most three distinct ones, uploaded
         synchronously, every variable of the binding."""
         r = self.reader
+        if r.device_kind == 'schism':
+            return self._ensure_schism_levels(times)
         need = sorted({r.nearest_time(t)[3] for t in times if r.covers_time(t)})
         for k in [k for k in self.mesh_slots if k not in need]:
             self.mesh_slots.pop(k)
@@ -1625,6 +1866,40 @@ class DeviceReaderBinding:
                 self.mesh.set_level(slot, t, v, r.level(v, k), r.placement(v)[1])
             self.mesh_slots[k] = slot
 
+    def _ensure_schism_levels(self, times):
+        """The time levels that BRACKET the given instants become resident on the SCHISM mesh: zcor and every variable of the
+        binding, uploaded synchronously.  Four slots serve a step of up to one level spacing; a longer one is refused."""
+        r = self.reader
+        need = sorted({k for t in times if r.covers_time(t) for k in r.nearest_time(t)[4:6]})
+        if len(need) > _abi.SCHISM_LEVELS:
+            raise ReaderLevelsError('reader %s: one model time step needs %d time levels resident, at most %d fit: the step is '
+                                    'longer than the spacing of the reader\'s time levels' % (r.name, len(need), _abi.SCHISM_LEVELS))
+        for k in [k for k in self.mesh_slots if k not in need]:
+            self.mesh_slots.pop(k)
+        free = [s for s in range(_abi.SCHISM_LEVELS) if s not in self.mesh_slots.values()]
+        for k in need:
+            if k in self.mesh_slots:
+                continue
+            slot = free.pop(0)
+            t = _epoch(r.times[k])
+            if r.zcor is not None:
+                self.mesh.set_zcor(slot, t, r.zcor[k])
+            for v in self.variables:
+                self.mesh.set_level(slot, t, v, r.level(v, k))
+            self.mesh_slots[k] = slot
+
+    def _sample_schism(self, P, variables, first, time):
+        r = self.reader
+        kb, ka, w = r.time_weight(time, variables)
+        if kb not in self.mesh_slots or (ka is not None and ka not in self.mesh_slots):
+            self._ensure_schism_levels([time])
+        pairs = [p for p in VECTOR_PAIRS_XY if p[0] in variables and p[1] in variables]
+        ordered = [v for p in pairs for v in p] + [v for v in variables if not any(v in p for p in pairs)]
+        flag = dict(zip(variables, first))
+        for o in range(0, len(ordered), _abi.UMESH_MAX_VARIABLES):
+            vs = ordered[o:o + _abi.UMESH_MAX_VARIABLES]
+            P.schism_sample(self.mesh, self.mesh_slots[kb], None if ka is None else self.mesh_slots[ka], w, vs, [flag[v] for v in vs])
+
     def sample_mesh(self, P, variables, first, time):
         """The mesh's values for the particle set P at `time`, merged into its environment slots by priority (first[k]: the mesh
         heads the list of variable k) -- on the device, in launches of at most eight variables.  The slot is chosen here by the
@@ -1632,6 +1907,8 @@ class DeviceReaderBinding:
         r = self.reader
         if not r.covers_time(time):
             return
+        if r.device_kind == 'schism':      # two bracketing levels and their weight: one launch (odr_schism_sample)
+            return self._sample_schism(P, variables, first, time)
         k = r.nearest_time(time)[3]
         if k not in self.mesh_slots:
             self._ensure_mesh_levels([time])
