@@ -362,7 +362,7 @@ int odr_particles_set_property(odr_ctx *ctx, odr_particles *p, int slot, int64_t
                                const float *host);
 int odr_particles_get_property(odr_ctx *ctx, odr_particles *p, int slot, float *host);
 /* copy of property `slot` as it is now, on the device, for the next odr_history_record (ODR_HIST_PROPERTIES_FROM_SNAPSHOT);
- * valid until the set is appended to, compacted or sorted */
+ * valid until the set is appended to, compacted or sorted; a record of more elements than the copy holds reads the live slot */
 int odr_particles_snapshot_property(odr_ctx *ctx, odr_particles *p, int slot);
 /* The Leeway loop body between two compactions in ONE launch: Environment.get_environment of `var_ids` at t_epoch
  * (environment.py:499-923; the list must hold x/y_wind and x/y_sea_water_velocity) + drift:current_uncertainty /

@@ -3973,18 +3973,22 @@ __global__ __launch_bounds__(BLOCK) void k_hist_extract(const float *__restrict_
   out[k] = buf[((long long)t * ntraj + tr) * stride + v];
 }
 
-// var.min(skipna=True) / var.max(skipna=True) over the buffer (:2412-2414); red = {max(-x), max(x)}
+// var.min(skipna=True) / var.max(skipna=True) over the buffer (:2412-2414); red = {max(-x), max(x), 1 when a value that is
+// not NaN was seen}: -inf in red[0] / red[1] is also what a variable holding only +inf / only -inf leaves there
 __global__ __launch_bounds__(BLOCK) void k_hist_minmax(const float *__restrict__ buf, long long nrec, int stride, int v,
                                                        double *red) {
   double mn = -__builtin_inf(), mx = -__builtin_inf();
+  int seen = 0;
   for (long long k = (long long)blockIdx.x * BLOCK + threadIdx.x; k < nrec; k += (long long)gridDim.x * BLOCK) {
     float x = buf[k * stride + v];
-    if (x == x) { mn = fmax(mn, -(double)x); mx = fmax(mx, (double)x); }
+    if (x == x) { seen = 1; mn = fmax(mn, -(double)x); mx = fmax(mx, (double)x); }
   }
   mn = wave_max(mn); mx = wave_max(mx);
-  if ((threadIdx.x & 63) == 0) {
-    if (mn > -__builtin_inf()) atomic_max_d(&red[0], mn);
-    if (mx > -__builtin_inf()) atomic_max_d(&red[1], mx);
+  const bool wave_seen = __ballot(seen) != 0ull;
+  if ((threadIdx.x & 63) == 0 && wave_seen) {
+    atomic_max_d(&red[0], mn);
+    atomic_max_d(&red[1], mx);
+    red[2] = 1.0;
   }
 }
 

@@ -1655,6 +1655,7 @@ int odr_particles_snapshot_property(odr_ctx *c, odr_particles *p, int slot) {
     p->aux_snap_cap[slot] = p->cap;
   }
   if (p->n) HIPCHK(hipMemcpyAsync(p->aux_snap[slot], p->aux[slot], sizeof(float) * (size_t)p->n, hipMemcpyDeviceToDevice, c->stream));
+  p->aux_snap_n[slot] = p->n;
   return 0;
 }
 
@@ -2514,7 +2515,7 @@ struct odr_history {
   int flush_nt;
   hipStream_t copy_stream;
   hipEvent_t recorded, flushed;
-  double *red;           // 2 doubles
+  double *red;           // 3 doubles: max(-x), max(x), values seen
   long long id_base;     // element ID of trajectory row 0 (odr_history_set_id_base)
 };
 
@@ -2540,7 +2541,7 @@ int odr_history_create(odr_ctx *c, int64_t n_trajectories, int32_t n_times, int3
   h->ntraj = n_trajectories; h->ntimes = n_times; h->nvars = nvars; h->stride = (nvars + 3) & ~3;
   for (int k = 0; k < nvars; ++k) h->codes[k] = var_codes[k];
   HIPCHK(hipMalloc((void **)&h->buf, sizeof(float) * (size_t)n_times * (size_t)n_trajectories * (size_t)h->stride));
-  HIPCHK(hipMalloc((void **)&h->red, 2 * sizeof(double)));
+  HIPCHK(hipMalloc((void **)&h->red, 3 * sizeof(double)));
   HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
   HIPCHK(hipEventCreateWithFlags(&h->recorded, hipEventDisableTiming));
   HIPCHK(hipEventCreateWithFlags(&h->flushed, hipEventDisableTiming));
@@ -2596,7 +2597,7 @@ int odr_history_record(odr_ctx *c, odr_particles *p, odr_history *h, int32_t tim
     else {
       const int slot = cde - ODR_HIST_PROPERTY0;
       REQUIRE(slot >= 0 && slot < 9, "history variable %d: no such property slot", cde);
-      src = ((position_from_previous & ODR_HIST_PROPERTIES_FROM_SNAPSHOT) && p->aux_snap[slot] && p->aux_snap_cap[slot] >= p->n) ? p->aux_snap[slot] : p->aux[slot];
+      src = ((position_from_previous & ODR_HIST_PROPERTIES_FROM_SNAPSHOT) && p->aux_snap[slot] && p->aux_snap_n[slot] >= p->n) ? p->aux_snap[slot] : p->aux[slot];
     }
     if (!src) return fail(ODR_ERR_STATE, "history variable %d has not been sampled / set", cde);
     H.src[k] = src; H.kind[k] = kind;
@@ -2687,15 +2688,15 @@ int odr_history_reset(odr_ctx *c, odr_history *h) {
 // var.min(skipna=True), var.max(skipna=True) over the whole buffer (:2409-2414); NaN when nothing was written
 int odr_history_minmax(odr_ctx *c, odr_history *h, int32_t var_index, double *minval, double *maxval) {
   REQUIRE(h && var_index >= 0 && var_index < h->nvars && minval && maxval, "bad arguments");
-  double init[2] = {-INFINITY, -INFINITY}, r[2];
+  double init[3] = {-INFINITY, -INFINITY, 0.0}, r[3];
   H2D(h->red, init, sizeof init);
   long long nrec = (long long)h->ntimes * h->ntraj;
   hipLaunchKernelGGL(k_hist_minmax, dim3(2048), dim3(BLOCK), 0, c->stream, h->buf, nrec, h->stride, var_index, h->red);
   HIPCHK(hipGetLastError());
   D2H(r, h->red, sizeof r);
   HIPCHK(hipStreamSynchronize(c->stream));
-  *minval = r[0] == -INFINITY ? NAN : -r[0];
-  *maxval = r[1] == -INFINITY ? NAN : r[1];
+  *minval = r[2] == 0.0 ? NAN : -r[0];   // the flag decides, not the -inf: a variable may hold nothing but +inf (or -inf)
+  *maxval = r[2] == 0.0 ? NAN : r[1];
   return 0;
 }
 

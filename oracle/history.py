@@ -18,18 +18,22 @@ import numpy as np
 
 
 class HistoryOracle:
-    def __init__(self, n_trajectories, n_times, variables):
+    def __init__(self, n_trajectories, n_times, variables, id_base=0):
+        """id_base: the element ID of trajectory row 0 -- the buffer of one rank of a run sharded by ID holds the rows of
+        the IDs [id_base, id_base + n_trajectories) and ignores every other element."""
         self.variables = list(variables)
+        self.n_trajectories, self.id_base = int(n_trajectories), int(id_base)
         self.buf = {v: np.full((n_trajectories, n_times), np.nan, dtype=np.float32) for v in self.variables}
 
     def record(self, time_index, ID, status, values, only_deactivated=False):
         """values: dict variable -> array over the elements present (any dtype)."""
-        ID = np.asarray(ID)
-        sel = np.asarray(status) != 0 if only_deactivated else np.ones(len(ID), bool)
+        row = np.asarray(ID).astype(np.int64) - self.id_base
+        sel = np.asarray(status) != 0 if only_deactivated else np.ones(len(row), bool)
+        sel = sel & (row >= 0) & (row < self.n_trajectories)
         if not sel.any():
             return
         for v in self.variables:
-            self.buf[v][ID[sel], time_index] = np.asarray(values[v])[sel]   # NumPy casts to float32 on assignment
+            self.buf[v][row[sel], time_index] = np.asarray(values[v])[sel]   # NumPy casts to float32 on assignment
 
     def minmax(self, variable):
         a = self.buf[variable]

@@ -138,6 +138,57 @@ def test_result_buffer_follows_state_to_buffer_semantics():
     assert o2.result_minmax['lon'] == o.result_minmax['lon']
 
 
+def test_result_buffer_backfill_across_a_buffer_boundary():
+    """time_step_output = 3 * time_step: an element that strands between two output times is written into the NEXT output
+    time (backfill).  When that column is a multiple of export_buffer_length the record arrives with the buffer full: it
+    is handed over first and the record lands in slot 0 of the next one.  The result must not depend on the buffer
+    length: 1 (every backfill crosses), 2, the number of output times, and more than that."""
+    g = golden('c4_stere_rk4_hdiff_strand.npz')
+    names = ['x_sea_water_velocity', 'y_sea_water_velocity', 'x_wind', 'y_wind',
+             'sea_surface_wave_stokes_drift_x_velocity', 'sea_surface_wave_stokes_drift_y_velocity', 'land_binary_mask']
+    every = 3
+
+    def run(**kw):
+        o = OceanDrift(loglevel=50, seed=0, rng='numpy')
+        o.add_reader(_grid_reader(g, names, proj4=synth.NORKYST_PROJ4))
+        o.set_config('drift:advection_scheme', 'runge-kutta4')
+        o.set_config('environment:constant:horizontal_diffusivity', 10)
+        o.set_config('general:coastline_action', 'stranding')
+        np.random.seed(0)
+        o.seed_elements(lon=g['lon'][0], lat=g['lat'][0], time=T0, wind_drift_factor=float(g['wdf']))
+        return o, o.run(time_step=900, steps=6, export_variables=['z', 'x_wind', 'age_seconds'], **kw)
+
+    variables = ('lon', 'lat', 'z', 'status', 'x_wind', 'age_seconds')
+    _, each = run()                                      # one output per step: tells the step that stranded an element
+    nout = 6 // every + 1
+    assert each['lon'].shape[1] == 7
+    runs = [run(time_step_output=every * 900, export_buffer_length=n) for n in (1, 2, nout, nout + 5)]
+    o0, r0 = runs[0]
+    assert len(r0['time']) == nout and all(r0[v].shape == (each['lon'].shape[0], nout) and r0[v].dtype == np.float32 for v in variables)
+    for o, r in runs[1:]:
+        for v in variables:
+            assert np.array_equal(r[v], r0[v], equal_nan=True), v
+            assert o.result_minmax[v] == o0.result_minmax[v], v
+    for v in variables:
+        assert o0.result_minmax[v] == (np.nanmin(r0[v]), np.nanmax(r0[v])), v
+    # the output times themselves are the columns 0, 3, 6 of the run that writes every step
+    present = np.isfinite(each['lon'][:, ::every])
+    for v in variables:
+        assert np.array_equal(r0[v][present], each[v][:, ::every][present]), v
+    # elements stranded by a step that is no output step, written into a column that is a multiple of 2 (and of 1)
+    last = lambda a: a.shape[1] - 1 - np.argmax(np.isfinite(a[:, ::-1]), axis=1)
+    gone = np.flatnonzero(np.isnan(each['lon'][:, -1]) & np.isfinite(each['lon'][:, 0]))
+    step = last(each['lon'])[gone]                       # the step whose coastline check deactivated the element
+    col = step // every + 1
+    crossing = gone[(step % every != 0) & (col % 2 == 0) & (col < nout)]
+    assert len(crossing) > 0
+    for e, k, c in zip(gone, step, col):
+        if k % every != 0 and c < nout:                  # backfilled: the state of step k in column c, NaN behind it
+            for v in variables:
+                assert r0[v][e, c] == each[v][e, k] and np.isnan(r0[v][e, c + 1:]).all(), (v, e, k, c)
+            assert r0['status'][e, c] > 0 and last(r0['lon'][e:e + 1])[0] == c
+
+
 def test_device_rng_run_is_reproducible_and_order_independent():
     g = golden('c3_grid3d_rk4_vmix.npz')
     names = ['x_sea_water_velocity', 'y_sea_water_velocity', 'upward_sea_water_velocity',

@@ -31,6 +31,25 @@ def test_nothing_to_write_is_a_no_op():
     assert np.isnan(h.buf['z']).all()
 
 
+def test_id_base_selects_a_window_of_ids():
+    """The buffer of one rank of a sharded run: row r holds element id_base + r; an element outside
+    [id_base, id_base + n_trajectories) is not written, whichever side it lies on."""
+    ID = np.array([7, 2, 5, 3, 9, 4])
+    status = np.array([0, 1, 0, 0, 1, 1], np.int32)
+    vals = dict(lon=ID + 0.5, status=status)
+    h = HistoryOracle(3, 2, ['lon', 'status'], id_base=3)            # rows 0..2 = IDs 3, 4, 5
+    h.record(0, ID, status, vals)
+    assert h.buf['lon'][:, 0].tolist() == [3.5, 4.5, 5.5] and np.isnan(h.buf['lon'][:, 1]).all()
+    h.record(1, ID, status, vals, only_deactivated=True)             # of IDs 2, 9, 4 only 4 lies in the window
+    assert np.isnan(h.buf['status'][[0, 2], 1]).all() and h.buf['status'][1, 1] == 1.0 and h.buf['lon'][1, 1] == 4.5
+    h = HistoryOracle(3, 1, ['lon'], id_base=0)                      # IDs at or above n_trajectories are dropped
+    h.record(0, ID, status, vals)
+    assert np.isnan(h.buf['lon'][[0, 1], 0]).all() and h.buf['lon'][2, 0] == 2.5
+    h = HistoryOracle(3, 1, ['lon'], id_base=20)                     # nothing in the window: nothing written
+    h.record(0, ID, status, vals)
+    assert np.isnan(h.buf['lon']).all() and np.isnan(h.minmax('lon')).all()
+
+
 def _replay_slots(g, record, flush):
     """The calls of run()'s _state_to_buffer (opendrift_amd/oceandrift.py) for the recorded states of golden c15: at an
     output step every element present goes to that output time, in between only the deactivated ones go to the NEXT one;
